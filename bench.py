@@ -2,11 +2,18 @@
 """bench.py -- particle-steps/s of the device-resident MD step loop on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--config 3|4] [--scaling weak|strong] [--frequency k]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one full velocity-Verlet step (first half-kick + drift, pair forces, second half-kick, thermostat)
-of every particle.  --gpus N > 1 with no WORLD_SIZE in the environment: the script starts its N ranks itself (one
-process per GPU, the torch.distributed.run environment) and relays rank 0's JSON line; under a launcher that set
-WORLD_SIZE, N has to be that world size.
+of every particle.  A plain run sets up, equilibrates, warms up, times the K steps and prints the headline line;
+--full adds what takes extra work: per-kernel event timing inside the timed region (roofline, valu_roofline,
+kickdrift_roofline, step_breakdown_ms), the fp64 rate probe, the measured-traffic lookup and the CPU baselines.
+--dump-outputs DIR writes what the timed path returned after its last step (a fixed, seeded sample of the particles'
+x, v, f and images, plus U, W, K) as DIR/<name>.npy in float64.
+
+--gpus N > 1 with no WORLD_SIZE in the environment: the script starts its N ranks itself (one process per GPU, the
+torch.distributed.run environment) and relays rank 0's JSON line; under a launcher that set WORLD_SIZE, N has to be
+that world size.
 
   --config 3 (default)  BASELINE.json configs[2], the configuration the metric is quoted on: 1,048,576 monodisperse
                         Lennard-Jones particles, rho = 0.897, r_cut = list cutoff = 2.5, dt = 0.001, NVT (Bussi
@@ -97,6 +104,11 @@ def parse():
                     help="k > 0: form U and W every k-th step inside the timed region (the reference's thermo cadence, "
                          "src/simulation.jl:118-136: one md_run call of k steps per report, the last of them with energies); "
                          "0 (default): on the timed region's last step only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel timings and rooflines, the fp64 probe, "
+                         "the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the timed path's outputs as DIR/<name>.npy (float64)")
     return ap.parse_args()
 
 
@@ -109,6 +121,25 @@ def make_inputs(n, seed_shift=0):
     v = initialize_velocities(kT, np.random.default_rng(67890 + seed_shift), n, dim)
     return dict(n=n, dim=dim, box=box, x=x, v=v, f=np.zeros_like(x), img=np.zeros((n, dim), dtype=np.int32),
                 diam=np.ones(n), kT=kT, rho=rho)
+
+
+DUMP_ROWS = 262144          # particles kept by --dump-outputs: 4 arrays x 2^18 x 3 doubles = 25 MB at most
+DUMP_SEED = 20260101
+
+
+def dump_outputs(path, x, v, f, img, uwk):
+    """The device state a caller downloads after the timed run, on a fixed seeded sample of particle indices (the same
+    sample for the same particle count), and the thermo values md_run returned for the last step."""
+    n = x.shape[0]
+    if n > DUMP_ROWS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    else:
+        idx = np.arange(n)
+    os.makedirs(path, exist_ok=True)
+    arrays = {"sample_index": idx, "x": x[idx], "v": v[idx], "f": f[idx], "images": img[idx],
+              "thermo_U_W_K": np.asarray(uwk, dtype=np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def host_cores():
@@ -370,10 +401,11 @@ def main():
     run(a.equil)           # melt the lattice so the timed region sees a liquid, untimed
     run(a.warmup)
     st0 = dev.stats()
-    # kernel durations: HIP events on the handle's stream around every 7th step-kernel launch of the timed region
-    # (every launch would cost ~8 % of the throughput being measured; 7 is coprime to the prune cadence, so ordinary
-    # and prune steps are sampled in proportion)
-    dev.profile(0 if os.environ.get("MDHIP_BENCH_NOPROF", "0") == "1" else 7)
+    # --full: kernel durations from HIP events on the handle's stream around every 7th step-kernel launch of the timed
+    # region (every launch would cost ~8 % of the throughput being measured; 7 is coprime to the prune cadence, so
+    # ordinary and prune steps are sampled in proportion).  A plain run times the steps without events.
+    if a.full:
+        dev.profile(0 if os.environ.get("MDHIP_BENCH_NOPROF", "0") == "1" else 7)
     barrier()
     t0 = time.perf_counter()
     if a.frequency > 0:
@@ -387,59 +419,26 @@ def main():
     barrier()
     el = time.perf_counter() - t0
     st1 = dev.stats()
-    dev.profile(False)
+    if a.full:
+        dev.profile(False)
 
     if dist is not None:
         t = torch.tensor([el], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
+    if a.dump_outputs:
+        # every rank takes part in the gather of the slab path; rank 0 writes
+        xs, vs, fs, ims = dev.gather_global() if use_domain else dev.download()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, xs, vs, fs, ims, uwk)
+        del xs, vs, fs, ims
+
     value = total_particles * a.steps / el
     fused = bool(st1.get("fused", 0))
     step_bytes = STEP_BYTES[ensemble]
-    # Kernel durations of the timed region: every prune-step launch is timed, the ordinary launches every 7th.  The
-    # roofline object's kernel_ms is the CALL-WEIGHTED average over both kinds, weighted with the numbers of ordinary and
-    # prune steps the timed region actually ran.
-    n_ord_timed = max(1, st1["force_launches"])
-    ord_ms = st1["force_ms"] / n_ord_timed
-    n_prune_timed = st1.get("prune_launches_timed", 0)
-    prune_ms = (st1.get("prune_ms", 0.0) / n_prune_timed) if n_prune_timed > 0 else None
     prunes_region = st1["prunes"] - st0["prunes"]
     steps_region = a.steps
-    if prune_ms is not None and prunes_region > 0:
-        kern_ms = (ord_ms * max(0, steps_region - prunes_region) + prune_ms * prunes_region) / steps_region
-    else:
-        kern_ms = ord_ms
-    launches = n_ord_timed + n_prune_timed
-    rebuilds_region = st1["rebuilds"] - st0["rebuilds"]
-    rebuild_ms = (st1.get("rebuild_ms", 0.0) / st1["rebuilds_timed"]) if st1.get("rebuilds_timed", 0) > 0 else None
-    # the dominant kernel: fused loop -> k_step_tile is the whole step EXCEPT the cell binning (32 B per particle of
-    # SURVEY.md section 8(d)'s figure: R x 24 + W cell id / permutation 8), which the list build does every ~41 steps and
-    # this kernel never moves; classic loop -> k_force_tile with its own 96 B per particle
-    per_particle = (step_bytes - BINNING_BYTES) if fused else FORCE_KERNEL_BYTES
-    achieved = (per_particle * n_local) / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-    traffic, traffic_src = (None, None)
-    if not use_domain and n_arg == 1048576:
-        traffic, traffic_src = measured_traffic()
-    # fp64-VALU co-roofline (SURVEY.md section 8(d) asks for both): issue slots the pair loop needs for the row
-    # entries it walks, against the measured v_fma_f64 rate of this GPU
-    pr = n_prune_timed
-    walked = None
-    if st1.get("walked_inner", 0) > 0 or st1.get("walked_outer", 0) > 0:
-        w_in = st1["walked_inner"] if st1["walked_inner"] > 0 else st1["walked_outer"]
-        walked = (w_in * max(0, steps_region - prunes_region) + st1["walked_outer"] * prunes_region) / steps_region
-    probe_slots, probe_gf = fp64_probe(local_rank) if rank == 0 else (None, None)
-    valu = None
-    if walked and kern_ms > 0:
-        need = walked / 64.0 * VALU_SLOTS_PER_CANDIDATE          # wave64 issue slots per launch
-        ach = need / (kern_ms * 1e-3)
-        valu = {"bound": "fp64 VALU issue", "slots_per_candidate": VALU_SLOTS_PER_CANDIDATE,
-                "candidates_walked_per_particle": walked / n_local, "achieved_slots_per_s": ach,
-                "peak_slots_per_s_measured": probe_slots, "peak_slots_per_s_spec": FP64_SPEC_SLOTS,
-                "frac_of_measured": (ach / probe_slots) if probe_slots else None, "frac_of_spec": ach / FP64_SPEC_SLOTS,
-                "probe_gflops_fp64_fma": probe_gf,
-                "note": "pair loop only (ISA-counted, scripts/isa_budget.py); staging, epilogue and the padded lanes of "
-                        "short rows are not counted as useful work"}
     workload = (f"BASELINE configs[3]: N={total_particles} LJ 3D rho=0.897 r_cut=2.5 dt=0.001 NVE, cube cut into "
                 f"{world} slab(s) along x" if cfg4 else
                 f"BASELINE configs[2]: N={n_arg} monodisperse LJ 3D rho=0.897 r_cut=2.5 dt=0.001 "
@@ -478,14 +477,57 @@ def main():
             "global_particles": total_particles,
             "avg_list_candidates": st1["avg_neighbors"],
             "tiled_force_kernel": bool(st1["tiled"]),
-            "prunes_in_timed_region": st1["prunes"] - st0["prunes"],
+            "prunes_in_timed_region": prunes_region,
             "max_tile_halo": st1["max_halo"],
             # the reference accumulates U and W every step; here they are formed on reporting steps only (identical
             # outputs at `frequency` cadence).  The energy-reporting variant of the kernel is ~25 % slower.
             "energies_every_step": a.frequency == 1,
             "thermo_frequency": a.frequency if a.frequency > 0 else a.steps,
         },
-        "roofline": {
+    }
+    if a.full:
+        # Kernel durations of the timed region: every prune-step launch is timed, the ordinary launches every 7th.  The
+        # roofline object's kernel_ms is the CALL-WEIGHTED average over both kinds, weighted with the numbers of ordinary
+        # and prune steps the timed region actually ran.
+        n_ord_timed = max(1, st1["force_launches"])
+        ord_ms = st1["force_ms"] / n_ord_timed
+        n_prune_timed = st1.get("prune_launches_timed", 0)
+        prune_ms = (st1.get("prune_ms", 0.0) / n_prune_timed) if n_prune_timed > 0 else None
+        if prune_ms is not None and prunes_region > 0:
+            kern_ms = (ord_ms * max(0, steps_region - prunes_region) + prune_ms * prunes_region) / steps_region
+        else:
+            kern_ms = ord_ms
+        launches = n_ord_timed + n_prune_timed
+        rebuilds_region = st1["rebuilds"] - st0["rebuilds"]
+        rebuild_ms = (st1.get("rebuild_ms", 0.0) / st1["rebuilds_timed"]) if st1.get("rebuilds_timed", 0) > 0 else None
+        # the dominant kernel: fused loop -> k_step_tile is the whole step EXCEPT the cell binning (32 B per particle of
+        # SURVEY.md section 8(d)'s figure: R x 24 + W cell id / permutation 8), which the list build does every ~41 steps
+        # and this kernel never moves; classic loop -> k_force_tile with its own 96 B per particle
+        per_particle = (step_bytes - BINNING_BYTES) if fused else FORCE_KERNEL_BYTES
+        achieved = (per_particle * n_local) / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+        traffic, traffic_src = (None, None)
+        if not use_domain and n_arg == 1048576:
+            traffic, traffic_src = measured_traffic()
+        # fp64-VALU co-roofline (SURVEY.md section 8(d) asks for both): issue slots the pair loop needs for the row
+        # entries it walks, against the measured v_fma_f64 rate of this GPU
+        pr = n_prune_timed
+        walked = None
+        if st1.get("walked_inner", 0) > 0 or st1.get("walked_outer", 0) > 0:
+            w_in = st1["walked_inner"] if st1["walked_inner"] > 0 else st1["walked_outer"]
+            walked = (w_in * max(0, steps_region - prunes_region) + st1["walked_outer"] * prunes_region) / steps_region
+        probe_slots, probe_gf = fp64_probe(local_rank) if rank == 0 else (None, None)
+        valu = None
+        if walked and kern_ms > 0:
+            need = walked / 64.0 * VALU_SLOTS_PER_CANDIDATE          # wave64 issue slots per launch
+            ach = need / (kern_ms * 1e-3)
+            valu = {"bound": "fp64 VALU issue", "slots_per_candidate": VALU_SLOTS_PER_CANDIDATE,
+                    "candidates_walked_per_particle": walked / n_local, "achieved_slots_per_s": ach,
+                    "peak_slots_per_s_measured": probe_slots, "peak_slots_per_s_spec": FP64_SPEC_SLOTS,
+                    "frac_of_measured": (ach / probe_slots) if probe_slots else None, "frac_of_spec": ach / FP64_SPEC_SLOTS,
+                    "probe_gflops_fp64_fma": probe_gf,
+                    "note": "pair loop only (ISA-counted, scripts/isa_budget.py); staging, epilogue and the padded lanes of "
+                            "short rows are not counted as useful work"}
+        out["roofline"] = {
             "bound": "hbm",
             "achieved": achieved,
             "peak": HBM_PEAK_GBPS,
@@ -513,38 +555,39 @@ def main():
                            if fused else "the force kernel's own share"),
             "bytes_per_launch": per_particle * n_local,
             "kernel_sources_sha256_16": kernel_hash(),
-        },
-        "valu_roofline": valu,
+        }
+        out["valu_roofline"] = valu
         # the classic loop's stream kernel (pending rescale + half-kick + drift + displacement check): HBM-bound
-        "kickdrift_roofline": {
+        kd_ms = st1["kickdrift_ms"] / max(1, st1["kickdrift_launches"])
+        out["kickdrift_roofline"] = {
             "bound": "hbm", "bytes_per_launch": KICKDRIFT_BYTES * n_local,
-            "kernel_ms": (st1["kickdrift_ms"] / max(1, st1["kickdrift_launches"])),
-            "achieved": (KICKDRIFT_BYTES * n_local) / max(1e-12, st1["kickdrift_ms"] / max(1, st1["kickdrift_launches"]) * 1e-3) / 1e9,
+            "kernel_ms": kd_ms,
+            "achieved": (KICKDRIFT_BYTES * n_local) / max(1e-12, kd_ms * 1e-3) / 1e9,
             "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-            "frac": (KICKDRIFT_BYTES * n_local) / max(1e-12, st1["kickdrift_ms"] / max(1, st1["kickdrift_launches"]) * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-        } if st1["kickdrift_launches"] > 0 else None,
-        "step_roofline": {
-            "headline": True,
-            "algorithmic_bytes_per_particle_step": step_bytes,
-            "achieved_GBps": value / world * step_bytes / 1e9,
-            "frac_of_8TBps": value / world * step_bytes / 1e9 / HBM_PEAK_GBPS,
-            "target_frac": 0.40,
-        },
+            "frac": (KICKDRIFT_BYTES * n_local) / max(1e-12, kd_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+        } if st1["kickdrift_launches"] > 0 else None
+    out["step_roofline"] = {
+        "headline": True,
+        "algorithmic_bytes_per_particle_step": step_bytes,
+        "achieved_GBps": value / world * step_bytes / 1e9,
+        "frac_of_8TBps": value / world * step_bytes / 1e9 / HBM_PEAK_GBPS,
+        "target_frac": 0.40,
+    }
+    if a.full:
         # where the timed region went (per step, ms): kernels as timed above, list builds from the library's own events
-        "step_breakdown_ms": {
+        out["step_breakdown_ms"] = {
             "ordinary_kernel": ord_ms, "prune_kernel": prune_ms,
             "list_build": rebuild_ms, "list_builds_in_timed_region": rebuilds_region,
             "list_build_per_step": (rebuild_ms * rebuilds_region / steps_region) if rebuild_ms is not None else None,
             "kernels_per_step": kern_ms,
             "wall_per_step": el * 1e3 / a.steps,
-        },
-        "thermo_last_step": {"U_per_particle": uwk[0] / total_particles, "T": 2.0 * uwk[2] / nf, "W": uwk[1]},
-    }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+        }
+    out["thermo_last_step"] = {"U_per_particle": uwk[0] / total_particles, "T": 2.0 * uwk[2] / nf, "W": uwk[1]}
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         many, one = cpu_baseline(inp, a.cpu_steps if n_arg <= 1048576 else max(4, a.cpu_steps // 4), dt)
         out["cpu_baseline"] = many
         out["cpu_baseline_1thread"] = one
-    elif rank == 0:
+    elif a.full and rank == 0:
         out["cpu_baseline"] = None
         out["cpu_baseline_1thread"] = None
     dev.close()

@@ -321,3 +321,30 @@ def test_bench_launcher_starts_one_process_per_rank(tmp_path):
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0"],
                        env=e2, capture_output=True, text=True, timeout=120)
     assert p.returncode == 2 and "WORLD_SIZE=1" in p.stderr
+
+
+def test_bench_dump_outputs_is_a_fixed_float64_sample(tmp_path):
+    """bench.py --dump-outputs: the same particle sample for the same particle count, float64 files, at most 64 MB in
+    all for the metric's 2^20 particles; systems of at most 2^18 particles are written whole."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 1 << 20
+    x = np.arange(3 * n, dtype=np.float64).reshape(n, 3)
+    img = np.ones((n, 3), dtype=np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), x, -x, 2 * x, img, (1.0, 2.0, 3.0))
+    total = 0
+    for name in ("sample_index", "x", "v", "f", "images", "thermo_U_W_K"):
+        a = np.load(tmp_path / "a" / (name + ".npy"))
+        b = np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / (name + ".npy"))
+    assert total <= 64 * 2**20
+    idx = np.load(tmp_path / "a" / "sample_index.npy").astype(np.int64)
+    assert idx.size == bench.DUMP_ROWS and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "x.npy"), x[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "thermo_U_W_K.npy"), [1.0, 2.0, 3.0])
+    small = np.zeros((1000, 3))
+    bench.dump_outputs(str(tmp_path / "s"), small, small, small, np.zeros((1000, 3), np.int32), (0.0, 0.0, 0.0))
+    assert np.array_equal(np.load(tmp_path / "s" / "sample_index.npy"), np.arange(1000))
