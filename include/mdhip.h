@@ -147,6 +147,21 @@ int md_run_brownian(md_ctx *ctx, int64_t nsteps, double dt, double ktemp, uint64
 int md_snapshot_begin(md_ctx *ctx);
 int md_snapshot_end(md_ctx *ctx, double *x, int32_t *images);
 
+/* Radial distribution function, sampled on the device (new relative to the reference, whose users histogram dumped
+ * trajectories on the host).  md_rdf_setup allocates the sampler, uploads the squared bin edges
+ * e2[k] = (k*delta)^2, delta = r_max / nbins, and zeroes the histogram; calling it again starts over.  Needs
+ * 1 <= nbins <= 8192, r_max > 0 and every face distance >= 3*r_max (the rule md_create applies to the list cutoff);
+ * a slab-decomposition handle is refused.  md_rdf_sample adds one sample of the current positions -- wrapped exactly
+ * as md_download returns them -- to the histogram, on the handle's stream, without waiting; it changes nothing the
+ * handle computes afterwards.  The unordered pair {a, b}, a < b, with del = (x_b + t) - x_a (t = the periodic
+ * translation bringing b next to a) and d2 = (del0*del0 + del1*del1) + del2*del2, goes into bin k iff
+ * e2[k] <= d2 < e2[k+1].  md_rdf_read waits and returns counts[nbins], summed over the samples since setup or the last
+ * md_rdf_reset, and their number; md_rdf_reset zeroes both and keeps the setup.                                   */
+int md_rdf_setup(md_ctx *ctx, double r_max, int nbins);
+int md_rdf_sample(md_ctx *ctx);
+int md_rdf_read(md_ctx *ctx, int64_t *counts, int64_t *nsamples);
+int md_rdf_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

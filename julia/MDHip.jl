@@ -15,7 +15,8 @@ import CodecZstd                                    # compress=true: src/io.jl:2
 
 export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, PseudoHS, Polydisperse,
        initialize_state, initialize_velocities, run_simulation!, LinearRamp, ExponentialRamp, fire_minimize!, minimize!,
-       LennardJonesShifted, LennardJonesForceShifted, LennardJonesXPLOR, device_spec
+       LennardJonesShifted, LennardJonesForceShifted, LennardJonesXPLOR, device_spec, RadialDistribution, compute_rdf,
+       gofr, write_rdf
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -265,6 +266,73 @@ function snapshot_end(dev::Device)
     return X, IM
 end
 
+# ---- g(r), sampled on the device (md_rdf_*; same normalisation and file format as analysis.py) ----------------------
+"RadialDistribution(r_max, nbins; every=1): pair counts on nbins bins of width r_max/nbins, accumulated until reset!"
+mutable struct RadialDistribution
+    r_max::Float64
+    nbins::Int
+    every::Int
+    edges::Vector{Float64}
+    r::Vector{Float64}
+    counts::Vector{Int64}
+    nsamples::Int64
+    n_particles::Int
+    volume::Float64
+    dimension::Int
+end
+function RadialDistribution(r_max, nbins; every::Int=1)
+    (r_max > 0 && isfinite(r_max)) || error("r_max must be finite and > 0")
+    1 <= nbins <= 8192 || error("nbins must be in 1..8192")
+    every >= 1 || error("every must be >= 1")
+    edges = Float64.(0:nbins) .* (r_max / nbins)
+    return RadialDistribution(Float64(r_max), nbins, every, edges, (edges[1:end-1] .+ edges[2:end]) ./ 2,
+                              zeros(Int64, nbins), 0, 0, 0.0, 3)
+end
+reset!(rdf::RadialDistribution) = (rdf.counts .= 0; rdf.nsamples = 0; rdf)
+
+function rdf_setup!(dev::Device, rdf::RadialDistribution)
+    check(dev, ccall((:md_rdf_setup, LIB), Cint, (Ptr{Cvoid}, Float64, Cint), dev.h, rdf.r_max, rdf.nbins))
+end
+rdf_sample!(dev::Device) = check(dev, ccall((:md_rdf_sample, LIB), Cint, (Ptr{Cvoid},), dev.h))
+rdf_reset!(dev::Device) = check(dev, ccall((:md_rdf_reset, LIB), Cint, (Ptr{Cvoid},), dev.h))
+function rdf_collect!(dev::Device, rdf::RadialDistribution, unitcell)
+    counts = zeros(Int64, rdf.nbins); ns = Ref{Int64}(0)
+    check(dev, ccall((:md_rdf_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}), dev.h, counts, ns))
+    rdf.counts .+= counts; rdf.nsamples += ns[]
+    rdf.n_particles = dev.n; rdf.volume = abs(det(unitcell)); rdf.dimension = size(unitcell, 1)
+    return rdf
+end
+
+"g_k = counts_k / (nsamples N (N-1) / (2V) V_k), V_k the shell volume (area in 2-D): 1 for an ideal gas"
+function gofr(rdf::RadialDistribution)
+    (rdf.nsamples == 0 || rdf.n_particles < 2) && return zeros(rdf.nbins)
+    e = rdf.edges; N = rdf.n_particles
+    Vk = rdf.dimension == 3 ? (4π / 3) .* (e[2:end] .^ 3 .- e[1:end-1] .^ 3) : π .* (e[2:end] .^ 2 .- e[1:end-1] .^ 2)
+    return rdf.counts ./ (rdf.nsamples * N * (N - 1.0) / (2.0 * rdf.volume) .* Vk)
+end
+
+function write_rdf(path, rdf::RadialDistribution)
+    g = gofr(rdf)
+    open(path, "w") do io
+        println(io, "# r g(r) count")
+        for k in 1:rdf.nbins
+            @printf(io, "%.6f %.6f %d\n", rdf.r[k], g[k], rdf.counts[k])
+        end
+    end
+end
+
+"compute_rdf(state, params, r_max, nbins): one device sample of g(r) of state's positions"
+function compute_rdf(state::SimulationState, params::Parameters, r_max, nbins)
+    rdf = RadialDistribution(r_max, nbins)
+    dev = state.system.device
+    X = pack(state.system.positions, state.dimension)
+    check(dev, ccall((:md_upload, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                     dev.h, X, C_NULL, C_NULL, state.images, C_NULL))
+    rdf_setup!(dev, rdf)
+    rdf_sample!(dev)
+    return rdf_collect!(dev, rdf, state.unitcell)
+end
+
 # ---- output: src/io.jl ---------------------------------------------------------------------------------------------
 function generate_log_times(; max_iter::Int=10000, logn::Int=40, logbase::Float64=1.35)   # src/io.jl:17-36
     dtime = Int[]
@@ -347,19 +415,22 @@ function open_files(pathname, traj_name, thermo_name)                           
 end
 
 """
-run_simulation!(state, params, ensemble, total_steps, frequency, pathname; traj_name, thermo_name, compress, log_times)
+run_simulation!(state, params, ensemble, total_steps, frequency, pathname; traj_name, thermo_name, compress, log_times, rdf)
 -- src/simulation.jl:40-178 (NVE / NVT) and :181-308 (Brownian).  Mutates `state`, returns nothing.  The step loop
 runs device-resident inside libmdhip; this driver cuts the run into segments that end on the reference's output
 steps (step % frequency == 0, 0-based), draws the thermostat's random numbers on the host in the reference's
-order, and writes the thermo line, the LAMMPS frames, the log-spaced snapshots and final.xyz.
+order, and writes the thermo line, the LAMMPS frames, the log-spaced snapshots and final.xyz.  With rdf a
+RadialDistribution, g(r) is sampled on the device at every rdf.every-th output step and written to pathname/rdf.txt.
 """
 function run_simulation!(state::SimulationState, params::Parameters, ensemble::Ensemble, total_steps::Int,
                          frequency::Int, pathname::String; traj_name::String="trajectory.xyz",
-                         thermo_name::String="thermo.txt", compress::Bool=false, log_times::Bool=false)
+                         thermo_name::String="thermo.txt", compress::Bool=false, log_times::Bool=false,
+                         rdf::Union{Nothing,RadialDistribution}=nothing)
     dev = state.system.device; d = state.dimension; n = params.n_particles
     brownian = ensemble isa Brownian
     configure!(dev, params.potential)
     upload!(dev, state; velocities=!brownian)
+    rdf === nothing || rdf_setup!(dev, rdf)
     trajectory_file, thermo_file = open_files(pathname, traj_name, thermo_name)
     open(io -> println(io, "# Step Energy Temperature Pressure"), thermo_file, "a")
     volume = abs(det(state.unitcell))                                                # src/simulation.jl:7-9
@@ -429,6 +500,9 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
             state.system.energy_and_forces.energy = uwk[1]; state.system.energy_and_forces.virial = uwk[2]
             push!(pending, (trajectory_file, last, "a"))                           # src/simulation.jl:139-151
         end
+        if rdf !== nothing && mod(last, frequency) == 0 && mod(last ÷ frequency, rdf.every) == 0
+            rdf_sample!(dev)                         # only where the loop stops anyway: no extra segment cut
+        end
         if log_times && snap_i <= length(snapshot_times) && snapshot_times[snap_i] == last   # :153-171
             push!(pending, (joinpath(pathname, "snapshot.$(last)"), last, "w"))
             snap_i += 1
@@ -442,6 +516,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
     state.images .= IM
     # finalize_simulation!: src/simulation.jl:11-36
     write_to_file(joinpath(pathname, "final.xyz"), total_steps, state.unitcell, n, X, state.diameters, d; mode="w")
+    if rdf !== nothing
+        rdf_collect!(dev, rdf, state.unitcell)
+        write_rdf(joinpath(pathname, "rdf.txt"), rdf)
+    end
     compress && isfile(trajectory_file) && compress_zstd(trajectory_file)
     return nothing
 end

@@ -24,6 +24,7 @@ EXPORTS = [
     "md_dom_counts", "md_set_stream", "md_dom_async_begin", "md_dom_step_a", "md_dom_step_b", "md_dom_step_c",
     "md_dom_async_end", "md_dom_comm_unique_id", "md_dom_comm_init", "md_dom_run_window", "md_dom_rebuild",
     "md_dom_enable_pruning", "md_dom_max_disp0", "md_dom_invalidate_inner",
+    "md_rdf_setup", "md_rdf_sample", "md_rdf_read", "md_rdf_reset",
 ]
 
 
@@ -131,6 +132,14 @@ def load():
     L.md_dom_enable_pruning.argtypes = [vp, C.c_int]
     L.md_dom_max_disp0.argtypes = [vp, dp]
     L.md_dom_invalidate_inner.argtypes = [vp]
+    L.md_rdf_setup.argtypes = [vp, C.c_double, C.c_int]
+    L.md_rdf_setup.restype = C.c_int
+    L.md_rdf_sample.argtypes = [vp]
+    L.md_rdf_sample.restype = C.c_int
+    L.md_rdf_read.argtypes = [vp, i64p, i64p]
+    L.md_rdf_read.restype = C.c_int
+    L.md_rdf_reset.argtypes = [vp]
+    L.md_rdf_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -10,6 +10,7 @@
 
 #include "md_kernels.hpp"
 #include "md_domain.hpp"
+#include "md_rdf.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -267,6 +268,21 @@ struct md_ctx {
         hipStream_t stream = nullptr;
         bool last = true; // the launch that completes the step: host-side bookkeeping happens here
     } part;
+
+    // radial distribution function (md_rdf_*): a grid of its own, scratch for the sort, the histogram
+    struct Rdf {
+        bool on = false;
+        double r_max = 0.0;
+        int nbins = 0;
+        RdfGrid grid{};
+        int64_t nsamples = 0;
+        DBuf<double> e2;                  // nbins + 1 squared bin edges
+        DBuf<unsigned long long> hist;    // nbins
+        DBuf<double4> wrec, srec;         // n: wrapped records {x, y, z, id}, in slot order / in cell order
+        DBuf<uint32_t> keys_in, keys_out, vals_in, vals_out;
+        DBuf<int32_t> cell_start, cell_end, work;
+        DBuf<char> sort_tmp;
+    } rdf;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1772,6 +1788,160 @@ int md_neighbor_pairs(md_ctx *ctx, int32_t *pairs, int64_t cap, int64_t *count)
         HIPCHK(hipMemcpyAsync(pairs, out.p, (size_t)ncopy * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Radial distribution function (md_rdf.hpp): a sample reads the state and writes only the rdf scratch, so the step
+// loop, the list and the cell order are exactly what they would have been without it.
+int md_rdf_setup(md_ctx *ctx, double r_max, int nbins)
+{
+#pragma clang fp contract(off)
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_rdf_setup: not available on a slab-decomposition handle");
+    if (!(r_max > 0.0) || !std::isfinite(r_max)) throw HipError("md_rdf_setup: r_max must be finite and > 0");
+    if (nbins < 1 || nbins > MD_RDF_MAX_BINS) {
+        char b[160];
+        snprintf(b, sizeof b, "md_rdf_setup: nbins must be in 1..%d, got %d", MD_RDF_MAX_BINS, nbins);
+        throw HipError(b);
+    }
+    for (int c = 0; c < ctx->dim; ++c)
+        if (ctx->perp[c] < 3.0 * r_max) {
+            char b[320];
+            snprintf(b, sizeof b,
+                     "md_rdf_setup: r_max = %.17g is too large: the face distance %.17g of lattice direction %d must be "
+                     ">= 3*r_max (limit r_max <= %.17g)",
+                     r_max, ctx->perp[c], c, ctx->perp[c] / 3.0);
+            throw HipError(b);
+        }
+    md_ctx::Rdf &R = ctx->rdf;
+    R.on = false;
+    RdfGrid &g = R.grid;
+    const int64_t n = ctx->n;
+    // cells at least r_max wide between their faces (fractional cut, as configure_grid does for the list), at least 3
+    // per direction (every pair within r_max is then visited once, with its minimum image); no more cells than about
+    // two per particle -- wider cells are still correct, only the walk grows
+    for (int c = 0; c < 3; ++c) {
+        g.nc[c] = 1;
+        if (c >= ctx->dim) continue;
+        int k = (int)std::min(std::floor(ctx->perp[c] / r_max), 4096.0);
+        while (k > 3 && ctx->perp[c] / k < r_max) --k;
+        g.nc[c] = std::max(k, 3);
+    }
+    auto ncells = [&] { return (int64_t)g.nc[0] * g.nc[1] * g.nc[2]; };
+    const int64_t cell_cap = std::max<int64_t>(2 * n, 27);
+    while (ncells() > cell_cap) {
+        int c = 0;
+        for (int d = 1; d < ctx->dim; ++d)
+            if (g.nc[d] > g.nc[c]) c = d;
+        if (g.nc[c] <= 3) break;
+        --g.nc[c];
+    }
+    g.ncell = (int)ncells();
+    for (int c = 0; c < 9; ++c) {
+        g.A[c] = ctx->A[c];
+        g.Ainv[c] = ctx->Ainv[c];
+    }
+    // squared bin edges: e2[k] = (k delta)^2, delta = r_max / nbins; the table decides every bin
+    std::vector<double> e2(nbins + 1);
+    const double delta = r_max / nbins;
+    for (int k = 0; k <= nbins; ++k) {
+        double rk = (double)k * delta;
+        e2[k] = rk * rk;
+    }
+    hipStream_t st = ctx->stream;
+    R.e2.alloc(nbins + 1);
+    R.hist.alloc(nbins);
+    R.wrec.alloc(n);
+    R.srec.alloc(n);
+    R.keys_in.alloc(n);
+    R.keys_out.alloc(n);
+    R.vals_in.alloc(n);
+    R.vals_out.alloc(n);
+    R.cell_start.alloc((size_t)g.ncell + 1);
+    R.cell_end.alloc((size_t)g.ncell + 1);
+    R.work.alloc(1);
+    size_t tmp_bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, R.keys_in.p, R.keys_out.p, R.vals_in.p, R.vals_out.p, (size_t)n,
+                                     0u, (unsigned)std::max(1, ceil_log2((uint64_t)g.ncell)), st));
+    R.sort_tmp.alloc(tmp_bytes);
+    HIPCHK(hipMemcpyAsync(R.e2.p, e2.data(), sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(R.hist.p, 0, sizeof(unsigned long long) * nbins, st));
+    size_t lds = sizeof(double) * (nbins + 1) + sizeof(uint32_t) * nbins;
+    if (ctx->dim == 3)
+        HIPCHK(hipFuncSetAttribute((const void *)k_rdf_hist<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    else
+        HIPCHK(hipFuncSetAttribute((const void *)k_rdf_hist<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIPCHK(hipStreamSynchronize(st)); // (the edge table is a host vector)
+    R.r_max = r_max;
+    R.nbins = nbins;
+    R.nsamples = 0;
+    R.on = true;
+    API_END
+}
+
+int md_rdf_sample(md_ctx *ctx)
+{
+    API_BEGIN
+    require_state(ctx, "md_rdf_sample");
+    md_ctx::Rdf &R = ctx->rdf;
+    if (!R.on) throw HipError("md_rdf_sample: no setup (call md_rdf_setup first)");
+    const int n = (int)ctx->n;
+    const RdfGrid &g = R.grid;
+    hipStream_t st = ctx->stream;
+    DevState s = ctx->dev(ctx->cur);
+    if (ctx->dim == 3)
+        k_rdf_key<3><<<nblocks(n), MD_BLOCK, 0, st>>>(n, s, ctx->grid, g, R.wrec.p, R.keys_in.p, R.vals_in.p);
+    else
+        k_rdf_key<2><<<nblocks(n), MD_BLOCK, 0, st>>>(n, s, ctx->grid, g, R.wrec.p, R.keys_in.p, R.vals_in.p);
+    HIPCHK(hipGetLastError());
+    size_t tmp_bytes = R.sort_tmp.n;
+    HIPCHK(rocprim::radix_sort_pairs(R.sort_tmp.p, tmp_bytes, R.keys_in.p, R.keys_out.p, R.vals_in.p, R.vals_out.p,
+                                     (size_t)n, 0u, (unsigned)std::max(1, ceil_log2((uint64_t)g.ncell)), st));
+    HIPCHK(hipMemsetAsync(R.cell_start.p, 0, sizeof(int32_t) * (g.ncell + 1), st));
+    HIPCHK(hipMemsetAsync(R.cell_end.p, 0, sizeof(int32_t) * (g.ncell + 1), st));
+    HIPCHK(hipMemsetAsync(R.work.p, 0, sizeof(int32_t), st));
+    k_rdf_gather<<<nblocks(n), MD_BLOCK, 0, st>>>(n, R.keys_out.p, R.vals_out.p, R.wrec.p, R.srec.p, R.cell_start.p,
+                                                  R.cell_end.p);
+    HIPCHK(hipGetLastError());
+    // one wave per home cell at a time, cells handed out by the work counter; the grid only needs to fill the chip
+    const int waves_per_block = MD_RDF_BLOCK / 64;
+    const int nblk = (int)std::min<int64_t>((g.ncell + waves_per_block - 1) / waves_per_block, 1024);
+    const size_t lds = sizeof(double) * (R.nbins + 1) + sizeof(uint32_t) * R.nbins;
+    const float inv_delta = (float)(R.nbins / R.r_max);
+    if (ctx->dim == 3)
+        k_rdf_hist<3><<<nblk, MD_RDF_BLOCK, lds, st>>>(g, R.nbins, inv_delta, R.e2.p, R.srec.p, R.cell_start.p,
+                                                      R.cell_end.p, R.work.p, R.hist.p);
+    else
+        k_rdf_hist<2><<<nblk, MD_RDF_BLOCK, lds, st>>>(g, R.nbins, inv_delta, R.e2.p, R.srec.p, R.cell_start.p,
+                                                      R.cell_end.p, R.work.p, R.hist.p);
+    HIPCHK(hipGetLastError());
+    ++R.nsamples;
+    API_END
+}
+
+int md_rdf_read(md_ctx *ctx, int64_t *counts, int64_t *nsamples)
+{
+    API_BEGIN
+    md_ctx::Rdf &R = ctx->rdf;
+    if (!R.on) throw HipError("md_rdf_read: no setup (call md_rdf_setup first)");
+    std::vector<unsigned long long> h(R.nbins);
+    HIPCHK(hipMemcpyAsync(h.data(), R.hist.p, sizeof(unsigned long long) * R.nbins, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (counts)
+        for (int k = 0; k < R.nbins; ++k) counts[k] = (int64_t)h[k];
+    if (nsamples) *nsamples = R.nsamples;
+    API_END
+}
+
+int md_rdf_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    md_ctx::Rdf &R = ctx->rdf;
+    if (!R.on) throw HipError("md_rdf_reset: no setup (call md_rdf_setup first)");
+    HIPCHK(hipMemsetAsync(R.hist.p, 0, sizeof(unsigned long long) * R.nbins, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    R.nsamples = 0;
     API_END
 }
 

@@ -169,6 +169,26 @@ class MDDevice:
     def scale_velocities(self, s):
         self._chk(self._L.md_scale_velocities(self._h, float(s)))
 
+    # -- radial distribution function -----------------------------------------------------
+    def rdf_setup(self, r_max, nbins):
+        """Allocate the device g(r) sampler (md_rdf_setup): nbins bins of width r_max / nbins, histogram zeroed."""
+        self._chk(self._L.md_rdf_setup(self._h, float(r_max), int(nbins)))
+        self._rdf_nbins = int(nbins)
+
+    def rdf_sample(self):
+        """Add one sample of the current positions to the device histogram (does not wait, changes no state)."""
+        self._chk(self._L.md_rdf_sample(self._h))
+
+    def rdf_read(self):
+        """(counts int64[nbins], nsamples): unordered pair counts summed over the samples since setup / reset."""
+        counts = np.zeros(max(getattr(self, "_rdf_nbins", 0), 1), dtype=np.int64)
+        ns = C.c_int64()
+        self._chk(self._L.md_rdf_read(self._h, counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(ns)))
+        return counts[: getattr(self, "_rdf_nbins", 0)], ns.value
+
+    def rdf_reset(self):
+        self._chk(self._L.md_rdf_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

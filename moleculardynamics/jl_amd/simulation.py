@@ -10,6 +10,7 @@ import os
 import numpy as np
 
 from . import _lib
+from . import analysis as _analysis
 from . import io as _io
 from .thermostat import draw_bussi
 from .types import NVE, NVT, Brownian
@@ -33,8 +34,12 @@ def _configure_device(state, params):
 
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
-                   thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True):
-    """Python spelling of run_simulation! (mutates `state`, returns None)."""
+                   thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None):
+    """Python spelling of run_simulation! (mutates `state`, returns None).
+
+    rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
+    (step % frequency == 0); the counts are added to it at the end and written to pathname/rdf.txt.  Sampling happens
+    only where the loop stops anyway and changes nothing else the run produces."""
     brownian = isinstance(ensemble, Brownian)
     os.makedirs(pathname, exist_ok=True)
     trajectory_file, thermo_file = _io.open_files(pathname, traj_name, thermo_name)
@@ -54,6 +59,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     # Brownian method (src/simulation.jl:181-308): the device's noise stream is keyed by one draw of state.rng;
     # the virial is sampled every 10th step and averaged at the output steps (:253-266)
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
+    if rdf is not None:
+        _analysis._start(dev, rdf)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -122,6 +129,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             if write_trajectory:
                 pending.append((trajectory_file, last, "a"))
                 want_frame = True
+        if rdf is not None and last % frequency == 0 and (last // frequency) % rdf.every == 0:
+            dev.rdf_sample()
         if snapshot_times is not None and snap_i < len(snapshot_times) and snapshot_times[snap_i] == last:
             pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w"))
             want_frame = True
@@ -141,6 +150,9 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     # finalize_simulation!: src/simulation.jl:11-36
     _io.write_to_file(os.path.join(pathname, "final.xyz"), total_steps, state.unitcell, n, x, state.diameters, dim,
                       mode="w")
+    if rdf is not None:
+        _analysis._collect(dev, rdf, n, state.unitcell)
+        rdf.write(os.path.join(pathname, "rdf.txt"))
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
