@@ -162,6 +162,38 @@ int md_rdf_sample(md_ctx *ctx);
 int md_rdf_read(md_ctx *ctx, int64_t *counts, int64_t *nsamples);
 int md_rdf_reset(md_ctx *ctx);
 
+/* Self dynamics, sampled on the device (new relative to the reference, whose users compute them on the host from the
+ * log-time LAMMPS frames with unwrapped columns).  A frame is exactly what md_download returns at that moment: the
+ * wrapped x and the image counts n, in particle-id order, written by the same gather into buffers the sampler owns.
+ * For one origin frame t0 and one current frame t, particle i contributes
+ *   dn_c  = (double)n_c(t) - (double)n_c(t0)                                     (exact)
+ *   del_c = (x_c(t) - x_c(t0)) + ((U_c0*dn_0 + U_c1*dn_1) + U_c2*dn_2)         (2-D: no third term)
+ *   d2    = (del_0*del_0 + del_1*del_1) + del_2*del_2,   d4 = d2*d2
+ *   s(q)  = sum over the axes c = 0..d-1, in order, of cos(q*del_c)            (for each of the nq wavenumbers)
+ * with every operation rounded on its own (no fma).  U_cr is the unit cell's row c, column r.  For a diagonal cell the
+ * off-diagonal products are zeros, so del_c is x_c(t) - x_c(t0) + L_c*dn_c bit for bit (d2 sees at most the sign of a
+ * zero).  The wrapped coordinates are differenced before the lattice translation is added, so no precision is lost to
+ * large unwrapped coordinates; the reference's p + boxmat*img (a BLAS product) has no pinned order and is not restated.
+ * The van Hove histogram counts d2 in bin k iff e2[k] <= d2 < e2[k+1], e2[k] = (k*delta)*(k*delta), delta =
+ * r_max/nbins, a host table built as md_rdf_setup builds it; d2 >= e2[nbins] is not counted.  Counts are integers.
+ * The sums {sum d2, sum d4, sum s(q_0), ..., sum s(q_nq-1)} are fp64, reduced over particle ids in a tree fixed by N
+ * (wave, then block partials in block order, then one block) without floating-point atomics: the same pair of frames
+ * gives the same bits on any handle, whatever its list history.  Each sample's totals are added into its row's running
+ * sums in stream order.
+ *
+ * md_dyn_setup allocates nslots origin slots (nslots*N*d*12 bytes) and nrows rows, zeroed; calling it again starts over.
+ * Needs 1 <= nslots <= 64, nrows >= 1, 0 <= nq <= 16 finite q, 0 <= nbins <= 8192 and, when nbins > 0, a finite
+ * r_max > 0.  md_dyn_origin stores the current frame in `slot`; md_dyn_sample exports the current frame once and adds
+ * `count` samples, frame vs slots[i] into rows[i]; neither waits, and neither changes anything the handle computes
+ * afterwards.  md_dyn_read waits and returns nsamples[nrows], sums[nrows*(2+nq)] and, if hist is not NULL,
+ * hist[nrows*nbins]; md_dyn_reset zeroes the rows and keeps the setup and the stored origins.  A slab-decomposition
+ * handle, a slot or row out of range, an empty slot and any call before md_dyn_setup are refused.               */
+int md_dyn_setup(md_ctx *ctx, int nslots, int nrows, const double *q, int nq, double r_max, int nbins);
+int md_dyn_origin(md_ctx *ctx, int slot);
+int md_dyn_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int count);
+int md_dyn_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *hist);
+int md_dyn_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

@@ -16,7 +16,7 @@ import CodecZstd                                    # compress=true: src/io.jl:2
 export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, PseudoHS, Polydisperse,
        initialize_state, initialize_velocities, run_simulation!, LinearRamp, ExponentialRamp, fire_minimize!, minimize!,
        LennardJonesShifted, LennardJonesForceShifted, LennardJonesXPLOR, device_spec, RadialDistribution, compute_rdf,
-       gofr, write_rdf
+       gofr, write_rdf, SelfDynamics, msd, alpha2, fs, van_hove, write_dynamics, write_van_hove
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -333,14 +333,170 @@ function compute_rdf(state::SimulationState, params::Parameters, r_max, nbins)
     return rdf_collect!(dev, rdf, state.unitcell)
 end
 
+# ---- self dynamics, sampled on the device (md_dyn_*; same schedule, normalisation and file formats as analysis.py) ------
+"""
+SelfDynamics(; q=(2π,), r_max=nothing, nbins=0, lags=nothing, origin_every=nothing): MSD, alpha2, F_s(q,t) and the van
+Hove function, accumulated across run_simulation! calls until reset!.  lags=nothing is the log-time schedule of
+`log_times=true` (origins at every multiple of maxlog = floor(1.35^40), samples at j*maxlog + l for the 39 distinct
+l = floor(1.35^i)); explicit lags need origin_every = E (origins at m*E, samples at m*E + l, ceil(max l / E) slots
+round-robin, at most 64).  Samples are taken before a new origin is stored at the same step.
+"""
+mutable struct SelfDynamics
+    q::Vector{Float64}
+    r_max::Float64
+    nbins::Int
+    lags::Vector{Int}
+    origin_every::Int               # 0: the log-time schedule
+    nslots::Int
+    nsamples::Vector{Int64}
+    sums::Matrix{Float64}           # (2 + nq) x nlags: sum d2, sum d4, sum s(q) per q
+    hist::Matrix{Int64}             # nbins x nlags
+    edges::Vector{Float64}
+    r::Vector{Float64}
+    n_particles::Int
+    dimension::Int
+    dt::Float64
+end
+const DYN_MAXLOG = floor(Int, 1.35^40)
+_log_stops() = generate_log_times(; save=false)
+function SelfDynamics(; q=(2π,), r_max=nothing, nbins::Int=0, lags=nothing, origin_every=nothing)
+    qv = Float64.(collect(q))
+    length(qv) <= 16 || error("at most 16 wavenumbers q")
+    all(isfinite, qv) || error("every q must be finite")
+    0 <= nbins <= 8192 || error("nbins must be in 0..8192")
+    rm = 0.0
+    if nbins > 0
+        (r_max !== nothing && r_max > 0 && isfinite(r_max)) || error("r_max must be finite and > 0 when nbins > 0")
+        rm = Float64(r_max)
+    end
+    if lags === nothing
+        origin_every === nothing || error("origin_every needs explicit lags (the default is the log-time schedule)")
+        lv = [s for s in _log_stops() if s <= DYN_MAXLOG]; E = 0; nslots = 1
+    else
+        lv = Int.(collect(lags))
+        (!isempty(lv) && all(>=(1), lv)) || error("lags must be positive integers")
+        allunique(lv) || error("lags must be distinct")
+        (origin_every isa Integer && origin_every >= 1) || error("explicit lags need origin_every, a positive integer")
+        E = Int(origin_every); nslots = cld(maximum(lv), E)
+        nslots <= 64 || error("ceil(max lag / origin_every) = $nslots origin slots; at most 64")
+    end
+    edges = nbins > 0 ? Float64.(0:nbins) .* (rm / nbins) : [0.0]
+    nl = length(lv)
+    return SelfDynamics(qv, rm, nbins, lv, E, nslots, zeros(Int64, nl), zeros(2 + length(qv), nl), zeros(Int64, nbins, nl),
+                        edges, (edges[1:end-1] .+ edges[2:end]) ./ 2, 0, 3, 1.0)
+end
+reset!(dyn::SelfDynamics) = (dyn.nsamples .= 0; dyn.sums .= 0; dyn.hist .= 0; dyn)
+
+"stops, events: the sampler's steps in a run of T steps; events[s] = (samples [(slot, row)] 0-based, origin slot or -1)"
+function dyn_schedule(dyn::SelfDynamics, T::Int)
+    events = Dict{Int,Tuple{Vector{Tuple{Int,Int}},Int}}()
+    if dyn.origin_every == 0
+        row = Dict(l => k - 1 for (k, l) in enumerate(dyn.lags))
+        for s in vcat(0, [t for t in _log_stops() if t < T])
+            smp = Tuple{Int,Int}[]
+            if s > 0
+                j = (s - 1) ÷ DYN_MAXLOG
+                haskey(row, s - j * DYN_MAXLOG) && push!(smp, (0, row[s - j * DYN_MAXLOG]))
+            end
+            events[s] = (smp, mod(s, DYN_MAXLOG) == 0 ? 0 : -1)
+        end
+    else
+        E = dyn.origin_every; nsl = dyn.nslots
+        for m in 0:cld(T, E)-1
+            s = m * E
+            events[s] = (get(events, s, (Tuple{Int,Int}[], -1))[1], mod(m, nsl))
+        end
+        for m in 0:cld(T, E)-1, (k, l) in enumerate(dyn.lags)      # origin order, then lag order: as analysis.py
+            s = m * E + l
+            s < T || continue
+            ev = get!(events, s, (Tuple{Int,Int}[], -1))
+            push!(ev[1], (mod(m, nsl), k - 1))
+        end
+    end
+    return sort(collect(keys(events))), events
+end
+
+function dyn_setup!(dev::Device, dyn::SelfDynamics)
+    check(dev, ccall((:md_dyn_setup, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{Float64}, Cint, Float64, Cint),
+                     dev.h, dyn.nslots, length(dyn.lags), dyn.q, length(dyn.q), dyn.r_max, dyn.nbins))
+end
+dyn_origin!(dev::Device, slot::Integer) = check(dev, ccall((:md_dyn_origin, LIB), Cint, (Ptr{Cvoid}, Cint), dev.h, slot))
+function dyn_sample!(dev::Device, slots::Vector{Int32}, rows::Vector{Int32})
+    check(dev, ccall((:md_dyn_sample, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Cint), dev.h, slots, rows,
+                     length(slots)))
+end
+dyn_reset!(dev::Device) = check(dev, ccall((:md_dyn_reset, LIB), Cint, (Ptr{Cvoid},), dev.h))
+function dyn_act!(dev::Device, ev)
+    smp, org = ev
+    isempty(smp) || dyn_sample!(dev, Int32[a for (a, _) in smp], Int32[b for (_, b) in smp])
+    org >= 0 && dyn_origin!(dev, org)
+end
+function dyn_collect!(dev::Device, dyn::SelfDynamics, dimension, dt)
+    nl = length(dyn.lags)
+    ns = zeros(Int64, nl); sums = zeros(2 + length(dyn.q), nl); hist = zeros(Int64, max(dyn.nbins, 1), nl)
+    check(dev, ccall((:md_dyn_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}), dev.h, ns, sums, hist))
+    dyn.nsamples .+= ns; dyn.sums .+= sums
+    dyn.nbins > 0 && (dyn.hist .+= hist)
+    dyn.n_particles = dev.n; dyn.dimension = dimension; dyn.dt = dt
+    return dyn
+end
+
+_per(dyn::SelfDynamics, v) = [dyn.nsamples[k] > 0 ? v[k] / (dyn.n_particles * dyn.nsamples[k]) : NaN for k in eachindex(v)]
+"<d^2> per lag"
+msd(dyn::SelfDynamics) = _per(dyn, dyn.sums[1, :])
+"d <d^4> / ((d + 2) <d^2>^2) - 1 per lag"
+alpha2(dyn::SelfDynamics) = (d = dyn.dimension; d .* _per(dyn, dyn.sums[2, :]) ./ ((d + 2) .* msd(dyn) .^ 2) .- 1.0)
+"F_s(q, t): nlags x nq, sum s / (d N ns)"
+fs(dyn::SelfDynamics) = [dyn.nsamples[k] > 0 ? dyn.sums[2 + j, k] / (dyn.dimension * dyn.n_particles * dyn.nsamples[k]) : NaN
+                         for k in eachindex(dyn.lags), j in eachindex(dyn.q)]
+"G_s(r_k, t): nlags x nbins, count_k / (ns N V_k)"
+function van_hove(dyn::SelfDynamics)
+    e = dyn.edges
+    Vk = dyn.dimension == 3 ? (4π / 3) .* (e[2:end] .^ 3 .- e[1:end-1] .^ 3) : π .* (e[2:end] .^ 2 .- e[1:end-1] .^ 2)
+    return [dyn.nsamples[k] > 0 ? dyn.hist[b, k] / (dyn.nsamples[k] * dyn.n_particles * Vk[b]) : NaN
+            for k in eachindex(dyn.lags), b in 1:dyn.nbins]
+end
+
+function write_dynamics(path, dyn::SelfDynamics; dt=dyn.dt)
+    m = msd(dyn); a = alpha2(dyn); f = fs(dyn)
+    open(path, "w") do io
+        print(io, "# lag time msd alpha2")
+        for q in dyn.q; print(io, " Fs(q=", @sprintf("%.6g", q), ")"); end
+        println(io, " nsamples")
+        for (k, l) in enumerate(dyn.lags)
+            dyn.nsamples[k] > 0 || continue
+            @printf(io, "%d %.6e %.6e %.6e", l, l * dt, m[k], a[k])
+            for j in eachindex(dyn.q); @printf(io, " %.6e", f[k, j]); end
+            @printf(io, " %d\n", dyn.nsamples[k])
+        end
+    end
+end
+
+function write_van_hove(path, dyn::SelfDynamics)
+    g = van_hove(dyn)
+    open(path, "w") do io
+        println(io, "# lag r G_s count")
+        first = true
+        for (k, l) in enumerate(dyn.lags)
+            dyn.nsamples[k] > 0 || continue
+            first || println(io)
+            first = false
+            for b in 1:dyn.nbins
+                @printf(io, "%d %.6f %.6e %d\n", l, dyn.r[b], g[k, b], dyn.hist[b, k])
+            end
+        end
+    end
+end
+
 # ---- output: src/io.jl ---------------------------------------------------------------------------------------------
-function generate_log_times(; max_iter::Int=10000, logn::Int=40, logbase::Float64=1.35)   # src/io.jl:17-36
+function generate_log_times(; max_iter::Int=10000, logn::Int=40, logbase::Float64=1.35, save::Bool=true)   # src/io.jl:17-36
     dtime = Int[]
     maxlog = floor(Int, logbase^logn)
     for j in 0:max_iter, i in 0:logn
         push!(dtime, floor(Int, j * maxlog + logbase^i))
     end
     logs = sort(unique(dtime))
+    save || return logs
     open("new-log-times.txt", "w") do file                                          # src/io.jl:1-15 (in the CWD, as the reference)
         write(file, "#maxsnap=$logn,base=$logbase\n")
         for l in logs; write(file, "$l\n"); end
@@ -425,12 +581,17 @@ RadialDistribution, g(r) is sampled on the device at every rdf.every-th output s
 function run_simulation!(state::SimulationState, params::Parameters, ensemble::Ensemble, total_steps::Int,
                          frequency::Int, pathname::String; traj_name::String="trajectory.xyz",
                          thermo_name::String="thermo.txt", compress::Bool=false, log_times::Bool=false,
-                         rdf::Union{Nothing,RadialDistribution}=nothing)
+                         rdf::Union{Nothing,RadialDistribution}=nothing,
+                         dynamics::Union{Nothing,SelfDynamics}=nothing)
     dev = state.system.device; d = state.dimension; n = params.n_particles
     brownian = ensemble isa Brownian
     configure!(dev, params.potential)
     upload!(dev, state; velocities=!brownian)
     rdf === nothing || rdf_setup!(dev, rdf)
+    # the dynamics schedule restarts at step 0 in every call; its stops are added to the output steps
+    dyn_stops, dyn_events = dynamics === nothing ? (Int[], nothing) : dyn_schedule(dynamics, total_steps)
+    dynamics === nothing || dyn_setup!(dev, dynamics)
+    dyn_i = 1
     trajectory_file, thermo_file = open_files(pathname, traj_name, thermo_name)
     open(io -> println(io, "# Step Energy Temperature Pressure"), thermo_file, "a")
     volume = abs(det(state.unitcell))                                                # src/simulation.jl:7-9
@@ -460,6 +621,8 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
             while snap_i <= length(snapshot_times) && snapshot_times[snap_i] < step; snap_i += 1; end
             snap_i <= length(snapshot_times) && (next_out = min(next_out, snapshot_times[snap_i]))
         end
+        while dyn_i <= length(dyn_stops) && dyn_stops[dyn_i] < step; dyn_i += 1; end
+        dyn_i <= length(dyn_stops) && (next_out = min(next_out, dyn_stops[dyn_i]))
         last = min(next_out, total_steps - 1)
         ns = last - step + 1
         if brownian
@@ -503,6 +666,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         if rdf !== nothing && mod(last, frequency) == 0 && mod(last ÷ frequency, rdf.every) == 0
             rdf_sample!(dev)                         # only where the loop stops anyway: no extra segment cut
         end
+        if dyn_i <= length(dyn_stops) && dyn_stops[dyn_i] == last
+            dyn_act!(dev, dyn_events[last])          # the samples, then the new origin
+            dyn_i += 1
+        end
         if log_times && snap_i <= length(snapshot_times) && snapshot_times[snap_i] == last   # :153-171
             push!(pending, (joinpath(pathname, "snapshot.$(last)"), last, "w"))
             snap_i += 1
@@ -519,6 +686,11 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
     if rdf !== nothing
         rdf_collect!(dev, rdf, state.unitcell)
         write_rdf(joinpath(pathname, "rdf.txt"), rdf)
+    end
+    if dynamics !== nothing
+        dyn_collect!(dev, dynamics, d, params.dt)
+        write_dynamics(joinpath(pathname, "dynamics.txt"), dynamics)
+        dynamics.nbins > 0 && write_van_hove(joinpath(pathname, "vanhove.txt"), dynamics)
     end
     compress && isfile(trajectory_file) && compress_zstd(trajectory_file)
     return nothing

@@ -25,6 +25,7 @@ EXPORTS = [
     "md_dom_async_end", "md_dom_comm_unique_id", "md_dom_comm_init", "md_dom_run_window", "md_dom_rebuild",
     "md_dom_enable_pruning", "md_dom_max_disp0", "md_dom_invalidate_inner",
     "md_rdf_setup", "md_rdf_sample", "md_rdf_read", "md_rdf_reset",
+    "md_dyn_setup", "md_dyn_origin", "md_dyn_sample", "md_dyn_read", "md_dyn_reset",
 ]
 
 
@@ -140,6 +141,16 @@ def load():
     L.md_rdf_read.restype = C.c_int
     L.md_rdf_reset.argtypes = [vp]
     L.md_rdf_reset.restype = C.c_int
+    L.md_dyn_setup.argtypes = [vp, C.c_int, C.c_int, dp, C.c_int, C.c_double, C.c_int]
+    L.md_dyn_setup.restype = C.c_int
+    L.md_dyn_origin.argtypes = [vp, C.c_int]
+    L.md_dyn_origin.restype = C.c_int
+    L.md_dyn_sample.argtypes = [vp, ip, ip, C.c_int]
+    L.md_dyn_sample.restype = C.c_int
+    L.md_dyn_read.argtypes = [vp, i64p, dp, i64p]
+    L.md_dyn_read.restype = C.c_int
+    L.md_dyn_reset.argtypes = [vp]
+    L.md_dyn_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

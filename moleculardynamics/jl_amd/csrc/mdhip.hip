@@ -11,6 +11,7 @@
 #include "md_kernels.hpp"
 #include "md_domain.hpp"
 #include "md_rdf.hpp"
+#include "md_dyn.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -283,6 +284,29 @@ struct md_ctx {
         DBuf<int32_t> cell_start, cell_end, work;
         DBuf<char> sort_tmp;
     } rdf;
+
+    // self dynamics (md_dyn_*): origin frames in slots, the current frame, block partials, per-row sums and histograms
+    struct Dyn {
+        bool on = false;
+        int nslots = 0, nrows = 0, nq = 0, nbins = 0;
+        double r_max = 0.0;
+        std::vector<double> q;
+        std::vector<char> filled;         // nslots: the slot holds an origin
+        std::vector<int64_t> nsamples;    // nrows
+        double *ox = nullptr;             // nslots frames of n x dim wrapped coordinates, in particle-id order
+        int32_t *oi = nullptr;            // nslots frames of n x dim image counts
+        DBuf<double> cx, part, sums, e2;  // current frame; block partials of one batch; nrows x (2 + nq); nbins + 1
+        DBuf<int32_t> ci;
+        DBuf<unsigned long long> hist;    // nrows x nbins
+        void release_slots()
+        {
+            if (ox) (void)hipFree(ox);
+            if (oi) (void)hipFree(oi);
+            ox = nullptr;
+            oi = nullptr;
+        }
+        ~Dyn() { release_slots(); }
+    } dyn;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1942,6 +1966,221 @@ int md_rdf_reset(md_ctx *ctx)
     HIPCHK(hipMemsetAsync(R.hist.p, 0, sizeof(unsigned long long) * R.nbins, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     R.nsamples = 0;
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Self dynamics (md_dyn.hpp): an origin store and a sample each launch k_export -- the gather md_download makes -- into the
+// sampler's own buffers and read nothing else of the state, so the step loop, the list and the cell order are exactly
+// what they would have been without them.
+static md_ctx::Dyn &dyn_of(md_ctx *ctx, const char *who)
+{
+    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
+    if (!ctx->dyn.on) throw HipError(std::string(who) + ": no setup (call md_dyn_setup first)");
+    return ctx->dyn;
+}
+
+static void dyn_export(md_ctx *ctx, double *x, int32_t *im)
+{
+    DevState s = ctx->dev(ctx->cur);
+    if (ctx->dim == 3)
+        k_export<3><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
+    else
+        k_export<2><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
+    HIPCHK(hipGetLastError());
+}
+
+int md_dyn_setup(md_ctx *ctx, int nslots, int nrows, const double *q, int nq, double r_max, int nbins)
+{
+#pragma clang fp contract(off)
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_dyn_setup: not available on a slab-decomposition handle");
+    char b[320];
+    if (nslots < 1 || nslots > MD_DYN_MAX_SLOTS) {
+        snprintf(b, sizeof b, "md_dyn_setup: nslots must be in 1..%d, got %d", MD_DYN_MAX_SLOTS, nslots);
+        throw HipError(b);
+    }
+    if (nrows < 1) {
+        snprintf(b, sizeof b, "md_dyn_setup: nrows must be >= 1, got %d", nrows);
+        throw HipError(b);
+    }
+    if (nq < 0 || nq > MD_DYN_MAX_Q) {
+        snprintf(b, sizeof b, "md_dyn_setup: nq must be in 0..%d, got %d", MD_DYN_MAX_Q, nq);
+        throw HipError(b);
+    }
+    if (nq > 0 && !q) throw HipError("md_dyn_setup: q is null");
+    for (int j = 0; j < nq; ++j)
+        if (!std::isfinite(q[j])) {
+            snprintf(b, sizeof b, "md_dyn_setup: q[%d] must be finite", j);
+            throw HipError(b);
+        }
+    if (nbins < 0 || nbins > MD_DYN_MAX_BINS) {
+        snprintf(b, sizeof b, "md_dyn_setup: nbins must be in 0..%d, got %d", MD_DYN_MAX_BINS, nbins);
+        throw HipError(b);
+    }
+    if (nbins > 0 && (!(r_max > 0.0) || !std::isfinite(r_max)))
+        throw HipError("md_dyn_setup: r_max must be finite and > 0 when nbins > 0");
+    md_ctx::Dyn &Y = ctx->dyn;
+    Y.on = false;
+    Y.release_slots();
+    const int64_t n = ctx->n;
+    const size_t frame = (size_t)n * ctx->dim;
+    const size_t bytes = (size_t)nslots * frame * 12;
+    // MDHIP_DYN_ALLOC_LIMIT=bytes: origin slots above this size are refused as if the device had run out of memory (a
+    // debug switch: the message can be checked at a test size)
+    const char *lim = getenv("MDHIP_DYN_ALLOC_LIMIT");
+    hipError_t ea = hipSuccess, eb = hipSuccess;
+    if (lim && bytes > (size_t)strtoull(lim, nullptr, 10))
+        ea = hipErrorOutOfMemory;
+    else {
+        ea = hipMalloc((void **)&Y.ox, (size_t)nslots * frame * sizeof(double));
+        if (ea == hipSuccess) eb = hipMalloc((void **)&Y.oi, (size_t)nslots * frame * sizeof(int32_t));
+    }
+    if (ea != hipSuccess || eb != hipSuccess) {
+        (void)hipGetLastError();
+        Y.release_slots();
+        snprintf(b, sizeof b,
+                 "md_dyn_setup: cannot allocate %zu bytes for %d origin slots (nslots*N*d*12 = %d*%lld*%d*12): %s", bytes,
+                 nslots, nslots, (long long)n, ctx->dim, hipGetErrorString(ea != hipSuccess ? ea : eb));
+        throw HipError(b);
+    }
+    const int nquant = 2 + nq;
+    const int nblk = (int)((n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
+    Y.cx.alloc(frame);
+    Y.ci.alloc(frame);
+    Y.part.alloc((size_t)MD_DYN_MAX_BATCH * nquant * nblk);
+    Y.sums.alloc((size_t)nrows * nquant);
+    Y.hist.alloc((size_t)nrows * std::max(nbins, 1));
+    Y.e2.alloc((size_t)nbins + 1);
+    // squared bin edges exactly as md_rdf_setup builds them: e2[k] = (k delta)^2, delta = r_max / nbins
+    std::vector<double> e2(nbins + 1, 0.0);
+    if (nbins > 0) {
+        const double delta = r_max / nbins;
+        for (int k = 0; k <= nbins; ++k) {
+            double rk = (double)k * delta;
+            e2[k] = rk * rk;
+        }
+    }
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemcpyAsync(Y.e2.p, e2.data(), sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(Y.sums.p, 0, sizeof(double) * nrows * nquant, st));
+    HIPCHK(hipMemsetAsync(Y.hist.p, 0, sizeof(unsigned long long) * nrows * std::max(nbins, 1), st));
+    HIPCHK(hipStreamSynchronize(st)); // (the edge table is a host vector)
+    Y.nslots = nslots;
+    Y.nrows = nrows;
+    Y.nq = nq;
+    Y.nbins = nbins;
+    Y.r_max = nbins > 0 ? r_max : 0.0;
+    Y.q.assign(q, q + nq);
+    Y.filled.assign(nslots, 0);
+    Y.nsamples.assign(nrows, 0);
+    Y.on = true;
+    API_END
+}
+
+int md_dyn_origin(md_ctx *ctx, int slot)
+{
+    API_BEGIN
+    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_origin");
+    require_state(ctx, "md_dyn_origin");
+    if (slot < 0 || slot >= Y.nslots) {
+        char b[160];
+        snprintf(b, sizeof b, "md_dyn_origin: slot %d is out of range 0..%d", slot, Y.nslots - 1);
+        throw HipError(b);
+    }
+    const size_t frame = (size_t)ctx->n * ctx->dim;
+    dyn_export(ctx, Y.ox + (size_t)slot * frame, Y.oi + (size_t)slot * frame);
+    Y.filled[slot] = 1;
+    API_END
+}
+
+int md_dyn_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int count)
+{
+#pragma clang fp contract(off)
+    API_BEGIN
+    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_sample");
+    require_state(ctx, "md_dyn_sample");
+    char b[200];
+    if (count < 0) {
+        snprintf(b, sizeof b, "md_dyn_sample: count must be >= 0, got %d", count);
+        throw HipError(b);
+    }
+    if (count > 0 && (!slots || !rows)) throw HipError("md_dyn_sample: slots / rows is null");
+    for (int i = 0; i < count; ++i) {
+        if (slots[i] < 0 || slots[i] >= Y.nslots) {
+            snprintf(b, sizeof b, "md_dyn_sample: slot %d is out of range 0..%d", (int)slots[i], Y.nslots - 1);
+            throw HipError(b);
+        }
+        if (rows[i] < 0 || rows[i] >= Y.nrows) {
+            snprintf(b, sizeof b, "md_dyn_sample: row %d is out of range 0..%d", (int)rows[i], Y.nrows - 1);
+            throw HipError(b);
+        }
+        if (!Y.filled[slots[i]]) {
+            snprintf(b, sizeof b, "md_dyn_sample: slot %d is empty (store an origin with md_dyn_origin first)",
+                     (int)slots[i]);
+            throw HipError(b);
+        }
+    }
+    if (count == 0) return 0;
+    hipStream_t st = ctx->stream;
+    dyn_export(ctx, Y.cx.p, Y.ci.p);
+    DynParams P{};
+    P.n = (int)ctx->n;
+    P.dim = ctx->dim;
+    P.nq = Y.nq;
+    P.nbins = Y.nbins;
+    P.nblk = (int)((ctx->n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
+    P.nquant = 2 + Y.nq;
+    P.inv_delta = Y.nbins > 0 ? (float)(Y.nbins / Y.r_max) : 0.0f;
+    for (int c = 0; c < 9; ++c) P.U[c] = ctx->A[c];
+    for (int j = 0; j < Y.nq; ++j) P.q[j] = Y.q[j];
+    const size_t lds = sizeof(uint32_t) * Y.nbins;
+    for (int i0 = 0; i0 < count; i0 += MD_DYN_MAX_BATCH) {
+        DynBatch B{};
+        B.count = std::min(count - i0, MD_DYN_MAX_BATCH);
+        for (int i = 0; i < B.count; ++i) {
+            B.slot[i] = slots[i0 + i];
+            B.row[i] = rows[i0 + i];
+        }
+        dim3 grid(P.nblk, B.count);
+        if (ctx->dim == 3)
+            k_dyn_sample<3><<<grid, MD_DYN_BLOCK, lds, st>>>(P, B, Y.cx.p, Y.ci.p, Y.ox, Y.oi, Y.e2.p, Y.part.p, Y.hist.p);
+        else
+            k_dyn_sample<2><<<grid, MD_DYN_BLOCK, lds, st>>>(P, B, Y.cx.p, Y.ci.p, Y.ox, Y.oi, Y.e2.p, Y.part.p, Y.hist.p);
+        HIPCHK(hipGetLastError());
+        k_dyn_reduce<<<1, MD_DYN_REDUCE_BLOCK, 0, st>>>(P, B, Y.part.p, Y.sums.p);
+        HIPCHK(hipGetLastError());
+        for (int i = 0; i < B.count; ++i) ++Y.nsamples[B.row[i]];
+    }
+    API_END
+}
+
+int md_dyn_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *hist)
+{
+    API_BEGIN
+    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_read");
+    const size_t ns = (size_t)Y.nrows * (2 + Y.nq), nh = (size_t)Y.nrows * Y.nbins;
+    hipStream_t st = ctx->stream;
+    std::vector<unsigned long long> h(nh);
+    if (sums) HIPCHK(hipMemcpyAsync(sums, Y.sums.p, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
+    if (hist && nh) HIPCHK(hipMemcpyAsync(h.data(), Y.hist.p, sizeof(unsigned long long) * nh, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (hist)
+        for (size_t k = 0; k < nh; ++k) hist[k] = (int64_t)h[k];
+    if (nsamples)
+        for (int r = 0; r < Y.nrows; ++r) nsamples[r] = Y.nsamples[r];
+    API_END
+}
+
+int md_dyn_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_reset");
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemsetAsync(Y.sums.p, 0, sizeof(double) * Y.nrows * (2 + Y.nq), st));
+    HIPCHK(hipMemsetAsync(Y.hist.p, 0, sizeof(unsigned long long) * Y.nrows * std::max(Y.nbins, 1), st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::fill(Y.nsamples.begin(), Y.nsamples.end(), (int64_t)0);
     API_END
 }
 

@@ -189,6 +189,41 @@ class MDDevice:
     def rdf_reset(self):
         self._chk(self._L.md_rdf_reset(self._h))
 
+    # -- self dynamics (MSD, F_s(q, t), van Hove) -----------------------------------------
+    def dyn_setup(self, nslots, nrows, q=(), r_max=0.0, nbins=0):
+        """Allocate the device self-dynamics sampler (md_dyn_setup): nslots origin slots, nrows zeroed rows of
+        {sum d2, sum d4, sum s(q) per q} and, when nbins > 0, a van Hove histogram of nbins bins of width r_max / nbins."""
+        qa = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+        self._chk(self._L.md_dyn_setup(self._h, int(nslots), int(nrows), _dp(qa) if qa.size else None, int(qa.size),
+                                       float(r_max), int(nbins)))
+        self._dyn_shape = (int(nrows), int(qa.size), int(nbins))
+
+    def dyn_origin(self, slot):
+        """Store the current frame (what download() returns: wrapped x and images) in `slot` (does not wait)."""
+        self._chk(self._L.md_dyn_origin(self._h, int(slot)))
+
+    def dyn_sample(self, slots, rows):
+        """Export the current frame once and add one sample per (slots[i], rows[i]): this frame against the origin in
+        slots[i], accumulated into rows[i] (does not wait, changes no state)."""
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        if s.shape != r.shape:
+            raise ValueError("slots and rows must have the same length")
+        self._chk(self._L.md_dyn_sample(self._h, _ip(s), _ip(r), int(s.size)))
+
+    def dyn_read(self):
+        """(nsamples int64[nrows], sums float64[nrows, 2 + nq], hist int64[nrows, nbins]), summed since setup / reset."""
+        nrows, nq, nbins = getattr(self, "_dyn_shape", (0, 0, 0))
+        ns = np.zeros(max(nrows, 1), dtype=np.int64)
+        sums = np.zeros((max(nrows, 1), 2 + nq))
+        hist = np.zeros((max(nrows, 1), max(nbins, 1)), dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.md_dyn_read(self._h, ns.ctypes.data_as(i64), _dp(sums), hist.ctypes.data_as(i64)))
+        return ns[:nrows], sums[:nrows], hist[:nrows, :nbins]
+
+    def dyn_reset(self):
+        self._chk(self._L.md_dyn_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

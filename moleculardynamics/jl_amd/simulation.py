@@ -34,12 +34,19 @@ def _configure_device(state, params):
 
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
-                   thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None):
+                   thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
+                   dynamics=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
     (step % frequency == 0); the counts are added to it at the end and written to pathname/rdf.txt.  Sampling happens
-    only where the loop stops anyway and changes nothing else the run produces."""
+    only where the loop stops anyway and changes nothing else the run produces.
+
+    dynamics: a SelfDynamics (analysis.py) to sample MSD, alpha2, F_s(q, t) and the van Hove function into, on the device,
+    at the steps of its schedule (by default the log-time steps `log_times=True` writes snapshots at); the schedule
+    restarts at step 0 in every call and the samples accumulate in the object.  At the end it is written to
+    pathname/dynamics.txt (and pathname/vanhove.txt when it has bins).  Its stops are added to the loop's output steps;
+    nothing else the run produces changes."""
     brownian = isinstance(ensemble, Brownian)
     os.makedirs(pathname, exist_ok=True)
     trajectory_file, thermo_file = _io.open_files(pathname, traj_name, thermo_name)
@@ -61,6 +68,10 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
     if rdf is not None:
         _analysis._start(dev, rdf)
+    dyn_stops, dyn_events, dyn_i = [], {}, 0
+    if dynamics is not None:
+        dyn_stops, dyn_events = dynamics.schedule(total_steps)
+        _analysis._dyn_start(dev, dynamics)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -106,6 +117,10 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
                 snap_i += 1
             if snap_i < len(snapshot_times):
                 next_out = min(next_out, snapshot_times[snap_i])
+        while dyn_i < len(dyn_stops) and dyn_stops[dyn_i] < step:
+            dyn_i += 1
+        if dyn_i < len(dyn_stops):
+            next_out = min(next_out, dyn_stops[dyn_i])
         last = min(next_out, total_steps - 1)
         U, W, K = segment(step, last - step + 1)
         collect()                       # the frame exported before this segment: its copy had the whole segment to finish
@@ -131,6 +146,9 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
                 want_frame = True
         if rdf is not None and last % frequency == 0 and (last // frequency) % rdf.every == 0:
             dev.rdf_sample()
+        if dyn_i < len(dyn_stops) and dyn_stops[dyn_i] == last:
+            _analysis._dyn_act(dev, dyn_events[last])
+            dyn_i += 1
         if snapshot_times is not None and snap_i < len(snapshot_times) and snapshot_times[snap_i] == last:
             pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w"))
             want_frame = True
@@ -153,6 +171,11 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     if rdf is not None:
         _analysis._collect(dev, rdf, n, state.unitcell)
         rdf.write(os.path.join(pathname, "rdf.txt"))
+    if dynamics is not None:
+        _analysis._dyn_collect(dev, dynamics, n, dim, params.dt)
+        dynamics.write(os.path.join(pathname, "dynamics.txt"))
+        if dynamics.nbins > 0:
+            dynamics.write_van_hove(os.path.join(pathname, "vanhove.txt"))
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
