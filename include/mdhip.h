@@ -194,6 +194,36 @@ int md_dyn_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int co
 int md_dyn_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *hist);
 int md_dyn_reset(md_ctx *ctx);
 
+/* Density modes, the static structure factor S(q) and the coherent intermediate scattering function F(q, t), sampled on
+ * the device (new relative to the reference, whose users compute them on the host from dumped frames).  A wave vector is
+ * an integer tuple n (d components), q_n = 2*pi*U^-T n, so q_n.x = 2*pi*n.f with f = U^-1 x the fractional coordinate:
+ * the phase does not depend on the image counts, and the sampler reads only the wrapped coordinates of a frame -- what
+ * md_download returns at that moment, in particle-id order, written by the same gather into a buffer the sampler owns.
+ * Sign convention: rho(q) = sum over particles of exp(+i q.x).  Per particle and vector
+ *   f_c = x_c / L_c (diagonal cell)   or   f_c = (Uinv_c0*x_0 + Uinv_c1*x_1) + Uinv_c2*x_2 (general cell)
+ *   t   = (n_0*f_0 + n_1*f_1) + n_2*f_2,  r = t - rint(t) (exact)                  (2-D: no third term)
+ * and the particle adds (cos 2*pi*r, sin 2*pi*r) to (Re rho, Im rho); everything in fp64, every operation of t rounded on
+ * its own.  The sum over particles is a tree fixed by N alone, without floating-point atomics, so rho is a function of
+ * the frame only (the same bits on any handle, whatever its skin, list history or cell order), and per component
+ *   |rho - rho_true| <= N * (32*kappa*|n|_1 + 128) * 2^-53,   kappa = || |U^-1| |U| ||_inf  (1 for a diagonal cell).
+ * Accumulators, fp64, no fma, added in stream order: s2[v] += Re*Re + Im*Im (static), and for a sample of the current
+ * frame against origin slot s into row k, corr[k][v] += Re_now*Re_s + Im_now*Im_s.
+ *
+ * md_sq_setup takes nvec vectors (n[v*d + c], 1 <= nvec <= 16384, |n_c| <= 32767, n != 0), 0 <= nslots <= 64 origin
+ * slots of 2*nvec doubles and nrows >= 0 correlation rows, all zeroed; calling it again starts over.  md_sq_sample
+ * evaluates rho of the current frame once, then, in this order: adds it to the static accumulator if add_static != 0,
+ * adds the `count` correlations (frame vs slots[i] into rows[i]), and stores rho in origin_slot unless that is -1.  It
+ * does not wait and changes nothing the handle computes afterwards.  md_sq_rho waits and returns rho of the last sampled
+ * frame as rho[2*v] = Re, rho[2*v + 1] = Im.  md_sq_read waits and returns the number of static samples, s2[nvec],
+ * nsamples[nrows] and corr[nrows*nvec] (any pointer may be NULL); md_sq_reset zeroes the accumulators and the counts and
+ * keeps the setup and the stored origins.  A slab-decomposition handle, a vector out of range, a slot or row out of
+ * range, an empty origin slot and any call before md_sq_setup are refused.                                      */
+int md_sq_setup(md_ctx *ctx, const int32_t *n, int nvec, int nslots, int nrows);
+int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_t *rows, int count, int origin_slot);
+int md_sq_rho(md_ctx *ctx, double *rho);
+int md_sq_read(md_ctx *ctx, int64_t *nstatic, double *s2, int64_t *nsamples, double *corr);
+int md_sq_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

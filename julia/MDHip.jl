@@ -16,7 +16,8 @@ import CodecZstd                                    # compress=true: src/io.jl:2
 export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, PseudoHS, Polydisperse,
        initialize_state, initialize_velocities, run_simulation!, LinearRamp, ExponentialRamp, fire_minimize!, minimize!,
        LennardJonesShifted, LennardJonesForceShifted, LennardJonesXPLOR, device_spec, RadialDistribution, compute_rdf,
-       gofr, write_rdf, SelfDynamics, msd, alpha2, fs, van_hove, write_dynamics, write_van_hove
+       gofr, write_rdf, SelfDynamics, msd, alpha2, fs, van_hove, write_dynamics, write_van_hove,
+       StructureFactor, select_wave_vectors, compute_sq, sofq, fqt, fqt_normalised, write_sq, write_fqt
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -488,6 +489,191 @@ function write_van_hove(path, dyn::SelfDynamics)
     end
 end
 
+# ---- density modes, S(q) and coherent F(q,t), sampled on the device (md_sq_*; normalisation and file formats as analysis.py)
+"""
+select_wave_vectors(unitcell, q_max; dq=nothing, max_per_bin=16, seed=0) -> (n, q, bin): every integer vector n of the half
+space (first non-zero component positive) with |q_n| <= q_max, q_n = 2pi U^-T n, thinned to at most max_per_bin per |q| bin
+of width dq (default 2pi / the smallest face distance) by a permutation seeded with `seed`.  n is d x nvec (Int32), sorted
+by bin, then by n.  Deterministic for given arguments (the permutation is Julia's, not numpy's).
+"""
+function select_wave_vectors(unitcell::AbstractMatrix, q_max::Real; dq=nothing, max_per_bin::Int=16, seed::Integer=0)
+    d = size(unitcell, 1)
+    (d in (2, 3) && size(unitcell, 2) == d) || error("unitcell must be a 2 x 2 or 3 x 3 matrix")
+    (q_max > 0 && isfinite(q_max)) || error("q_max must be finite and > 0")
+    max_per_bin >= 1 || error("max_per_bin must be >= 1")
+    Ui = inv(Float64.(unitcell))
+    w = dq === nothing ? 2π * maximum(norm(Ui[c, :]) for c in 1:d) : Float64(dq)
+    (w > 0 && isfinite(w)) || error("dq must be finite and > 0")
+    m = [floor(Int, norm(unitcell[:, c]) * q_max / 2π * (1 + 1e-12)) for c in 1:d]
+    maximum(m) <= 32767 || error("q_max needs integer components beyond 32767")
+    bins = Dict{Int,Vector{Tuple{Vector{Int},Float64}}}()
+    r3 = d == 3 ? (-m[3]:m[3]) : (0:0)
+    for n1 in 0:m[1], n2 in -m[2]:m[2], n3 in r3
+        nv = d == 3 ? [n1, n2, n3] : [n1, n2]
+        k = findfirst(!=(0), nv)
+        (k === nothing || nv[k] < 0) && continue
+        q = 2π * norm(Ui' * nv)
+        q <= q_max || continue
+        push!(get!(bins, floor(Int, q / w), Tuple{Vector{Int},Float64}[]), (nv, q))
+    end
+    isempty(bins) && error("no wave vector with |q| <= q_max: the smallest one of this cell is longer")
+    rng = Random.Xoshiro(seed)
+    ns = Vector{Int}[]; qs = Float64[]; bs = Int[]
+    for b in sort(collect(keys(bins)))
+        members = bins[b]
+        keep = sort(randperm(rng, length(members))[1:min(max_per_bin, length(members))])
+        for (nv, q) in sort(members[keep]; by=first)
+            push!(ns, nv); push!(qs, q); push!(bs, b)
+        end
+    end
+    length(ns) <= 16384 || error("$(length(ns)) wave vectors selected; at most 16384 (lower q_max or max_per_bin, or widen dq)")
+    return Int32.(reduce(hcat, ns)), qs, bs
+end
+
+"""
+StructureFactor(q_max; dq, max_per_bin=16, seed=0, every=1, lags, origin_every, dynamic=false): S(q) sampled at every
+`every`-th output step of run_simulation!(...; sq) and, with dynamic=true, the coherent F(q,t) on SelfDynamics' schedule
+(default: the log-time schedule; explicit lags need origin_every, at most 64 slots; samples before the new origin).
+"""
+mutable struct StructureFactor
+    q_max::Float64
+    dq::Union{Nothing,Float64}
+    max_per_bin::Int
+    seed::Int
+    every::Int
+    dynamic::Bool
+    sched::Union{Nothing,SelfDynamics}   # the schedule (lags, origin_every, nslots) is SelfDynamics' own
+    lags::Vector{Int}
+    nslots::Int
+    unitcell::Union{Nothing,Matrix{Float64}}
+    n::Matrix{Int32}                     # d x nvec
+    qvec::Vector{Float64}
+    bin::Vector{Int}                     # per vector: index into q
+    q::Vector{Float64}                   # mean |q| of a bin
+    nvectors::Vector{Int}
+    nstatic::Int64
+    s2::Vector{Float64}
+    nsamples::Vector{Int64}
+    corr::Matrix{Float64}                # nvec x nlags
+    n_particles::Int
+    dt::Float64
+end
+function StructureFactor(q_max; dq=nothing, max_per_bin::Int=16, seed::Int=0, every::Int=1, lags=nothing,
+                         origin_every=nothing, dynamic::Bool=false)
+    (q_max > 0 && isfinite(q_max)) || error("q_max must be finite and > 0")
+    (dq === nothing || (dq > 0 && isfinite(dq))) || error("dq must be finite and > 0")
+    max_per_bin >= 1 || error("max_per_bin must be >= 1")
+    every >= 1 || error("every must be >= 1")
+    (dynamic || (lags === nothing && origin_every === nothing)) || error("lags and origin_every need dynamic=true")
+    sched = dynamic ? SelfDynamics(; q=Float64[], lags=lags, origin_every=origin_every) : nothing
+    lv = dynamic ? copy(sched.lags) : Int[]
+    return StructureFactor(Float64(q_max), dq === nothing ? nothing : Float64(dq), max_per_bin, seed, every, dynamic, sched,
+                           lv, dynamic ? sched.nslots : 0, nothing, zeros(Int32, 0, 0), Float64[], Int[], Float64[], Int[],
+                           0, Float64[], zeros(Int64, length(lv)), zeros(0, length(lv)), 0, 1.0)
+end
+function reset!(sq::StructureFactor)
+    sq.unitcell = nothing; sq.nstatic = 0; sq.nsamples .= 0
+    sq.n = zeros(Int32, 0, 0); sq.s2 = Float64[]; sq.corr = zeros(0, length(sq.lags))
+    return sq
+end
+sq_schedule(sq::StructureFactor, T::Int) = sq.dynamic ? dyn_schedule(sq.sched, T) : (Int[], nothing)
+
+function sq_setup!(dev::Device, sq::StructureFactor, unitcell)
+    U = Matrix{Float64}(unitcell)
+    if sq.unitcell === nothing
+        n, q, b = select_wave_vectors(U, sq.q_max; dq=sq.dq, max_per_bin=sq.max_per_bin, seed=sq.seed)
+        ub = sort(unique(b))
+        sq.unitcell = U; sq.n = n; sq.qvec = q; sq.bin = [searchsortedfirst(ub, x) for x in b]
+        sq.nvectors = [count(==(k), sq.bin) for k in eachindex(ub)]
+        sq.q = [sum(q[sq.bin .== k]) / sq.nvectors[k] for k in eachindex(ub)]
+        sq.s2 = zeros(length(q)); sq.corr = zeros(length(q), length(sq.lags))
+    else
+        sq.unitcell == U || error("the unit cell differs from the one the wave vectors were selected for; reset! first")
+    end
+    check(dev, ccall((:md_sq_setup, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Cint, Cint, Cint),
+                     dev.h, sq.n, size(sq.n, 2), sq.nslots, length(sq.lags)))
+end
+"rho of the current frame once; then the static sample, the correlations (slot, row), the origin store (-1: none)"
+function sq_sample!(dev::Device, static::Bool, slots::Vector{Int32}, rows::Vector{Int32}, origin::Integer)
+    check(dev, ccall((:md_sq_sample, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Int32}, Cint, Cint),
+                     dev.h, static ? 1 : 0, slots, rows, length(slots), origin))
+end
+function sq_act!(dev::Device, static::Bool, ev)
+    smp, org = ev === nothing ? (Tuple{Int,Int}[], -1) : ev
+    sq_sample!(dev, static, Int32[a for (a, _) in smp], Int32[b for (_, b) in smp], org)
+end
+"rho(q) of the last sampled frame (rho = sum exp(+i q.x)); waits"
+function sq_rho(dev::Device, nvec::Int)
+    out = zeros(2, nvec)
+    check(dev, ccall((:md_sq_rho, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), dev.h, out))
+    return [complex(out[1, v], out[2, v]) for v in 1:nvec]
+end
+sq_reset!(dev::Device) = check(dev, ccall((:md_sq_reset, LIB), Cint, (Ptr{Cvoid},), dev.h))
+function sq_collect!(dev::Device, sq::StructureFactor, dt)
+    nvec = length(sq.qvec); nl = length(sq.lags)
+    nst = Ref{Int64}(0); s2 = zeros(nvec); ns = zeros(Int64, max(nl, 1)); corr = zeros(nvec, max(nl, 1))
+    check(dev, ccall((:md_sq_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+                     dev.h, nst, s2, ns, corr))
+    sq.nstatic += nst[]; sq.s2 .+= s2
+    if nl > 0
+        sq.nsamples .+= ns[1:nl]; sq.corr .+= corr[:, 1:nl]
+    end
+    sq.n_particles = dev.n; sq.dt = dt
+    return sq
+end
+
+_sq_binned(sq::StructureFactor, v) = [sum(v[sq.bin .== k]) / sq.nvectors[k] for k in eachindex(sq.q)]
+"S(q) per |q| bin: sum over the bin's vectors of s2_v / (nstatic N M_bin)"
+sofq(sq::StructureFactor) = sq.nstatic == 0 ? fill(NaN, length(sq.q)) : _sq_binned(sq, sq.s2 ./ (sq.nstatic * sq.n_particles))
+"F(q,t): nlags x nbins, sum over the bin's vectors of corr_kv / (ns_k N M_bin); NaN where a lag has no sample"
+function fqt(sq::StructureFactor)
+    out = fill(NaN, length(sq.lags), length(sq.q))
+    for k in eachindex(sq.lags)
+        sq.nsamples[k] > 0 && (out[k, :] = _sq_binned(sq, sq.corr[:, k] ./ (sq.nsamples[k] * sq.n_particles)))
+    end
+    return out
+end
+"F(q,t) / S(q)"
+fqt_normalised(sq::StructureFactor) = fqt(sq) ./ sofq(sq)'
+
+function write_sq(path, sq::StructureFactor)
+    s = sofq(sq)
+    open(path, "w") do io
+        println(io, "# q S(q) nvectors nsamples")
+        for b in eachindex(sq.q)
+            @printf(io, "%.6f %.6e %d %d\n", sq.q[b], s[b], sq.nvectors[b], sq.nstatic)
+        end
+    end
+end
+
+function write_fqt(path, sq::StructureFactor; dt=sq.dt)
+    f = fqt(sq); fn = fqt_normalised(sq)
+    open(path, "w") do io
+        println(io, "# lag time q F F/S nsamples")
+        first = true
+        for (k, l) in enumerate(sq.lags)
+            sq.nsamples[k] > 0 || continue
+            first || println(io)
+            first = false
+            for b in eachindex(sq.q)
+                @printf(io, "%d %.6e %.6f %.6e %.6e %d\n", l, l * dt, sq.q[b], f[k, b], fn[k, b], sq.nsamples[k])
+            end
+        end
+    end
+end
+
+"compute_sq(state, params, q_max; dq, max_per_bin, seed): one device sample of S(q) of state's positions"
+function compute_sq(state::SimulationState, params::Parameters, q_max; dq=nothing, max_per_bin::Int=16, seed::Int=0)
+    sq = StructureFactor(q_max; dq=dq, max_per_bin=max_per_bin, seed=seed)
+    dev = state.system.device
+    X = pack(state.system.positions, state.dimension)
+    check(dev, ccall((:md_upload, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                     dev.h, X, C_NULL, C_NULL, state.images, C_NULL))
+    sq_setup!(dev, sq, state.unitcell)
+    sq_sample!(dev, true, Int32[], Int32[], -1)
+    return sq_collect!(dev, sq, params.dt)
+end
+
 # ---- output: src/io.jl ---------------------------------------------------------------------------------------------
 function generate_log_times(; max_iter::Int=10000, logn::Int=40, logbase::Float64=1.35, save::Bool=true)   # src/io.jl:17-36
     dtime = Int[]
@@ -577,12 +763,15 @@ runs device-resident inside libmdhip; this driver cuts the run into segments tha
 steps (step % frequency == 0, 0-based), draws the thermostat's random numbers on the host in the reference's
 order, and writes the thermo line, the LAMMPS frames, the log-spaced snapshots and final.xyz.  With rdf a
 RadialDistribution, g(r) is sampled on the device at every rdf.every-th output step and written to pathname/rdf.txt.
+With sq a StructureFactor, S(q) is sampled the same way (pathname/sq.txt) and, if it is dynamic, the coherent F(q,t) on its
+schedule (pathname/fqt.txt).
 """
 function run_simulation!(state::SimulationState, params::Parameters, ensemble::Ensemble, total_steps::Int,
                          frequency::Int, pathname::String; traj_name::String="trajectory.xyz",
                          thermo_name::String="thermo.txt", compress::Bool=false, log_times::Bool=false,
                          rdf::Union{Nothing,RadialDistribution}=nothing,
-                         dynamics::Union{Nothing,SelfDynamics}=nothing)
+                         dynamics::Union{Nothing,SelfDynamics}=nothing,
+                         sq::Union{Nothing,StructureFactor}=nothing)
     dev = state.system.device; d = state.dimension; n = params.n_particles
     brownian = ensemble isa Brownian
     configure!(dev, params.potential)
@@ -592,6 +781,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
     dyn_stops, dyn_events = dynamics === nothing ? (Int[], nothing) : dyn_schedule(dynamics, total_steps)
     dynamics === nothing || dyn_setup!(dev, dynamics)
     dyn_i = 1
+    # the structure factor: static samples at every sq.every-th output step, the dynamic stops as SelfDynamics' are
+    sq_stops, sq_events = sq === nothing ? (Int[], nothing) : sq_schedule(sq, total_steps)
+    sq === nothing || sq_setup!(dev, sq, state.unitcell)
+    sq_i = 1
     trajectory_file, thermo_file = open_files(pathname, traj_name, thermo_name)
     open(io -> println(io, "# Step Energy Temperature Pressure"), thermo_file, "a")
     volume = abs(det(state.unitcell))                                                # src/simulation.jl:7-9
@@ -623,6 +816,8 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         end
         while dyn_i <= length(dyn_stops) && dyn_stops[dyn_i] < step; dyn_i += 1; end
         dyn_i <= length(dyn_stops) && (next_out = min(next_out, dyn_stops[dyn_i]))
+        while sq_i <= length(sq_stops) && sq_stops[sq_i] < step; sq_i += 1; end
+        sq_i <= length(sq_stops) && (next_out = min(next_out, sq_stops[sq_i]))
         last = min(next_out, total_steps - 1)
         ns = last - step + 1
         if brownian
@@ -670,6 +865,14 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
             dyn_act!(dev, dyn_events[last])          # the samples, then the new origin
             dyn_i += 1
         end
+        if sq !== nothing
+            sq_static = mod(last, frequency) == 0 && mod(last ÷ frequency, sq.every) == 0
+            sq_ev = nothing
+            if sq_i <= length(sq_stops) && sq_stops[sq_i] == last
+                sq_ev = sq_events[last]; sq_i += 1
+            end
+            (sq_static || sq_ev !== nothing) && sq_act!(dev, sq_static, sq_ev)   # rho once: static, samples, origin
+        end
         if log_times && snap_i <= length(snapshot_times) && snapshot_times[snap_i] == last   # :153-171
             push!(pending, (joinpath(pathname, "snapshot.$(last)"), last, "w"))
             snap_i += 1
@@ -691,6 +894,11 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         dyn_collect!(dev, dynamics, d, params.dt)
         write_dynamics(joinpath(pathname, "dynamics.txt"), dynamics)
         dynamics.nbins > 0 && write_van_hove(joinpath(pathname, "vanhove.txt"), dynamics)
+    end
+    if sq !== nothing
+        sq_collect!(dev, sq, params.dt)
+        write_sq(joinpath(pathname, "sq.txt"), sq)
+        sq.dynamic && write_fqt(joinpath(pathname, "fqt.txt"), sq)
     end
     compress && isfile(trajectory_file) && compress_zstd(trajectory_file)
     return nothing

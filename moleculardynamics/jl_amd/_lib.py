@@ -26,6 +26,7 @@ EXPORTS = [
     "md_dom_enable_pruning", "md_dom_max_disp0", "md_dom_invalidate_inner",
     "md_rdf_setup", "md_rdf_sample", "md_rdf_read", "md_rdf_reset",
     "md_dyn_setup", "md_dyn_origin", "md_dyn_sample", "md_dyn_read", "md_dyn_reset",
+    "md_sq_setup", "md_sq_sample", "md_sq_rho", "md_sq_read", "md_sq_reset",
 ]
 
 
@@ -151,6 +152,16 @@ def load():
     L.md_dyn_read.restype = C.c_int
     L.md_dyn_reset.argtypes = [vp]
     L.md_dyn_reset.restype = C.c_int
+    L.md_sq_setup.argtypes = [vp, ip, C.c_int, C.c_int, C.c_int]
+    L.md_sq_setup.restype = C.c_int
+    L.md_sq_sample.argtypes = [vp, C.c_int, ip, ip, C.c_int, C.c_int]
+    L.md_sq_sample.restype = C.c_int
+    L.md_sq_rho.argtypes = [vp, dp]
+    L.md_sq_rho.restype = C.c_int
+    L.md_sq_read.argtypes = [vp, i64p, dp, i64p, dp]
+    L.md_sq_read.restype = C.c_int
+    L.md_sq_reset.argtypes = [vp]
+    L.md_sq_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -1,4 +1,5 @@
-"""Structure of a simulated configuration: the radial distribution function g(r), sampled on the device.
+"""Structure and dynamics of a simulated configuration, sampled on the device: the radial distribution function g(r),
+the self dynamics (MSD, F_s(q, t), van Hove) and the collective side (density modes, S(q), coherent F(q, t)).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -105,6 +106,66 @@ def _log_schedule():
     return maxlog, lags, stops
 
 
+def _parse_schedule(lags, origin_every):
+    """(maxlog, lag_list, origin_every, nslots) of a sampling schedule: lags=None is the log-time schedule (one slot),
+    explicit positive distinct `lags` need `origin_every` and use ceil(max lag / origin_every) <= 64 slots."""
+    if lags is None:
+        if origin_every is not None:
+            raise ValueError("origin_every needs explicit lags (the default is the log-time schedule)")
+        maxlog, lag_list, _ = _log_schedule()
+        return maxlog, lag_list, None, 1
+    lag_list = [int(v) for v in np.atleast_1d(lags)]
+    if not lag_list or any(v < 1 for v in lag_list) or any(int(v) != v for v in np.atleast_1d(lags)):
+        raise ValueError("lags must be positive integers")
+    if len(set(lag_list)) != len(lag_list):
+        raise ValueError("lags must be distinct")
+    if origin_every is None or int(origin_every) != origin_every or int(origin_every) < 1:
+        raise ValueError("explicit lags need origin_every, a positive integer")
+    nslots = -(-max(lag_list) // int(origin_every))
+    if nslots > 64:
+        raise ValueError(f"ceil(max lag / origin_every) = {nslots} origin slots; at most 64")
+    return None, lag_list, int(origin_every), nslots
+
+
+def _schedule(maxlog, lags, origin_every, nslots, total_steps):
+    """(stops, events) of one run of `total_steps` steps (SelfDynamics.schedule, shared with StructureFactor)."""
+    T = int(total_steps)
+    events = {}
+
+    def ev(s):
+        return events.setdefault(s, ([], None))
+
+    if maxlog is not None:
+        maxlog, _, stops = _log_schedule()
+        row = {int(l): k for k, l in enumerate(lags)}
+        for s in [0] + [s for s in stops if s < T]:
+            smp, org = ev(s)
+            if s > 0:
+                j = (s - 1) // maxlog
+                k = row.get(s - j * maxlog)
+                if k is not None:
+                    smp.append((0, k))
+            if s % maxlog == 0:
+                org = 0
+            events[s] = (smp, org)
+    else:
+        E, ns = origin_every, nslots
+        for m in range(0, (T + E - 1) // E):
+            o = m * E
+            smp, _ = ev(o)
+            events[o] = (smp, m % ns)
+        for m in range(0, (T + E - 1) // E):
+            for k, l in enumerate(lags):
+                s = m * E + int(l)
+                if s < T:
+                    ev(s)[0].append((m % ns, k, m))
+        for s, (smp, org) in events.items():
+            smp.sort(key=lambda t: (t[2], t[1]))
+            events[s] = ([(a, b) for a, b, _ in smp], org)
+    stops = sorted(events)
+    return stops, events
+
+
 class SelfDynamics:
     """Self dynamics of the particles, accumulated on the device over the samples of a schedule until reset().
 
@@ -132,25 +193,7 @@ class SelfDynamics:
             r_max = float(r_max)
         else:
             r_max = None if r_max is None else float(r_max)
-        if lags is None:
-            if origin_every is not None:
-                raise ValueError("origin_every needs explicit lags (the default is the log-time schedule)")
-            self.maxlog, lag_list, _ = _log_schedule()
-            self.origin_every = None
-            self.nslots = 1
-        else:
-            lag_list = [int(v) for v in np.atleast_1d(lags)]
-            if not lag_list or any(v < 1 for v in lag_list) or any(int(v) != v for v in np.atleast_1d(lags)):
-                raise ValueError("lags must be positive integers")
-            if len(set(lag_list)) != len(lag_list):
-                raise ValueError("lags must be distinct")
-            if origin_every is None or int(origin_every) != origin_every or int(origin_every) < 1:
-                raise ValueError("explicit lags need origin_every, a positive integer")
-            self.maxlog = None
-            self.origin_every = int(origin_every)
-            self.nslots = -(-max(lag_list) // self.origin_every)
-            if self.nslots > 64:
-                raise ValueError(f"ceil(max lag / origin_every) = {self.nslots} origin slots; at most 64")
+        self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
         self.q, self.r_max, self.nbins = q, r_max, nbins
         self.lags = np.array(lag_list, dtype=np.int64)
         nl = len(lag_list)
@@ -173,41 +216,7 @@ class SelfDynamics:
         """(stops, events) for one run of `total_steps` steps: the sorted steps where the sampler acts, and per stop a
         pair (samples, origin): samples = [(slot, row), ...] in origin order, origin = the slot the frame is stored in
         after them, or None."""
-        T = int(total_steps)
-        events = {}
-
-        def ev(s):
-            return events.setdefault(s, ([], None))
-
-        if self.maxlog is not None:
-            maxlog, _, stops = _log_schedule()
-            row = {int(l): k for k, l in enumerate(self.lags)}
-            for s in [0] + [s for s in stops if s < T]:
-                smp, org = ev(s)
-                if s > 0:
-                    j = (s - 1) // maxlog
-                    k = row.get(s - j * maxlog)
-                    if k is not None:
-                        smp.append((0, k))
-                if s % maxlog == 0:
-                    org = 0
-                events[s] = (smp, org)
-        else:
-            E, ns = self.origin_every, self.nslots
-            for m in range(0, (T + E - 1) // E):
-                o = m * E
-                smp, _ = ev(o)
-                events[o] = (smp, m % ns)
-            for m in range(0, (T + E - 1) // E):
-                for k, l in enumerate(self.lags):
-                    s = m * E + int(l)
-                    if s < T:
-                        ev(s)[0].append((m % ns, k, m))
-            for s, (smp, org) in events.items():
-                smp.sort(key=lambda t: (t[2], t[1]))
-                events[s] = ([(a, b) for a, b, _ in smp], org)
-        stops = sorted(events)
-        return stops, events
+        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
 
     # -- results ----------------------------------------------------------------------------------------------------
     def _accumulate(self, nsamples, sums, hist, n_particles, dimension, dt):
@@ -294,3 +303,268 @@ def _dyn_act(dev, event):
 def _dyn_collect(dev, dyn, n_particles, dimension, dt):
     ns, sums, hist = dev.dyn_read()
     dyn._accumulate(ns, sums, hist, n_particles, dimension, dt)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Collective structure: the density modes rho(q) = sum_j exp(i q.x_j), the static structure factor S(q) = <|rho|^2> / N
+# and the coherent intermediate scattering function F(q, t) = <rho(q, t0 + t) rho*(q, t0)> / N, sampled on the device
+# (md_sq_*) on wave vectors commensurate with the cell.
+
+MAX_WAVE_VECTORS = 16384
+
+
+def select_wave_vectors(unitcell, q_max, dq=None, max_per_bin=16, seed=0):
+    """Wave vectors commensurate with `unitcell` (d x d, columns = lattice vectors): returns (n, q, bin).
+
+    n: int32 (nvec, d), every integer vector of the half space (first non-zero component positive, so -q never duplicates
+    q) with |q_n| <= q_max, q_n = 2 pi U^-T n, thinned to at most `max_per_bin` per |q| bin of width dq (default 2 pi / the
+    smallest face distance) by a permutation seeded with `seed`; q: |q_n|; bin: floor(|q_n| / dq).  Sorted by bin, then by
+    n.  The same arguments give the same selection."""
+    u = np.asarray(unitcell, dtype=np.float64)
+    if u.ndim == 1:
+        u = np.diag(u)
+    d = u.shape[0]
+    if u.shape != (d, d) or d not in (2, 3):
+        raise ValueError("unitcell must be a 2 x 2 or 3 x 3 matrix (or its diagonal)")
+    q_max, max_per_bin = float(q_max), int(max_per_bin)
+    if not (q_max > 0.0 and math.isfinite(q_max)):
+        raise ValueError("q_max must be finite and > 0")
+    if max_per_bin < 1:
+        raise ValueError("max_per_bin must be >= 1")
+    uinv = np.linalg.inv(u)
+    if dq is None:
+        dq = 2.0 * math.pi * float(np.max(np.linalg.norm(uinv, axis=1)))   # face distance c = 1 / |row c of U^-1|
+    dq = float(dq)
+    if not (dq > 0.0 and math.isfinite(dq)):
+        raise ValueError("dq must be finite and > 0")
+    # n_c = (column c of U) . q / 2 pi, so |n_c| <= |column c| q_max / 2 pi
+    m = [int(math.floor(np.linalg.norm(u[:, c]) * q_max / (2.0 * math.pi) * (1.0 + 1e-12))) for c in range(d)]
+    if max(m) > 32767:
+        raise ValueError("q_max needs integer components beyond 32767")
+    rng = np.random.default_rng(seed)
+    g2 = 4.0 * math.pi * math.pi * (uinv @ uinv.T)      # |q_n|^2 = n^T g2 n
+    rest = np.meshgrid(*[np.arange(-m[c], m[c] + 1, dtype=np.int64) for c in range(1, d)], indexing="ij")
+    rest = [r.reshape(-1) for r in rest]
+    if d == 3:
+        positive0 = (rest[0] > 0) | ((rest[0] == 0) & (rest[1] > 0))
+    else:
+        positive0 = rest[0] > 0
+    restf = [r.astype(np.float64) for r in rest]
+    # the part of n^T g2 n that does not involve n_0
+    base = sum(g2[a + 1, b + 1] * restf[a] * restf[b] for a in range(d - 1) for b in range(d - 1))
+    cross = 2.0 * sum(g2[0, a + 1] * restf[a] for a in range(d - 1))
+    q2max = q_max * q_max
+    nbins_max = int(q_max / dq) + 2
+    thr = np.full(nbins_max, np.inf)                    # per bin: the largest key still in the selection once it is full
+    pool_n = np.zeros((0, d), dtype=np.int64)
+    pool_q = np.zeros(0)
+    pool_b = np.zeros(0, dtype=np.int64)
+    pool_k = np.zeros(0)
+    for n0 in range(0, m[0] + 1):
+        q2 = (g2[0, 0] * n0 * n0 + n0 * cross) + base
+        ok = q2 <= q2max
+        if n0 == 0:
+            ok &= positive0
+        idx = np.nonzero(ok)[0]
+        if idx.size == 0:
+            continue
+        key = rng.random(idx.size)                      # a random key per candidate: the smallest keys of a bin are kept
+        qn = np.sqrt(q2[idx])
+        b = np.floor(qn / dq).astype(np.int64)
+        keep = key <= thr[b]
+        idx, key, qn, b = idx[keep], key[keep], qn[keep], b[keep]
+        nn = np.empty((idx.size, d), dtype=np.int64)
+        nn[:, 0] = n0
+        for c in range(1, d):
+            nn[:, c] = rest[c - 1][idx]
+        pool_n = np.concatenate([pool_n, nn])
+        pool_q = np.concatenate([pool_q, qn])
+        pool_b = np.concatenate([pool_b, b])
+        pool_k = np.concatenate([pool_k, key])
+        order = np.lexsort((pool_k, pool_b))
+        sb = pool_b[order]
+        first = np.searchsorted(sb, sb, side="left")    # rank of an entry within its bin = position - first of the bin
+        rank = np.arange(sb.size) - first
+        sel = order[rank < max_per_bin]
+        pool_n, pool_q, pool_b, pool_k = pool_n[sel], pool_q[sel], pool_b[sel], pool_k[sel]
+        full = np.nonzero(np.bincount(pool_b, minlength=nbins_max) >= max_per_bin)[0]
+        if full.size:
+            worst = np.zeros(nbins_max)
+            np.maximum.at(worst, pool_b, pool_k)
+            thr[full] = worst[full]
+    if pool_n.shape[0] == 0:
+        raise ValueError("no wave vector with |q| <= q_max: the smallest one of this cell is longer")
+    if pool_n.shape[0] > MAX_WAVE_VECTORS:
+        raise ValueError(f"{pool_n.shape[0]} wave vectors selected; at most {MAX_WAVE_VECTORS} (lower q_max or max_per_bin, "
+                         "or widen dq)")
+    order = np.lexsort(tuple(pool_n[:, c] for c in range(d - 1, -1, -1)) + (pool_b,))
+    return pool_n[order].astype(np.int32), pool_q[order], pool_b[order]
+
+
+def wave_vector_lengths(unitcell, n):
+    """|q_n| = 2 pi |U^-T n| of integer vectors n (nvec, d)."""
+    u = np.asarray(unitcell, dtype=np.float64)
+    if u.ndim == 1:
+        u = np.diag(u)
+    return 2.0 * math.pi * np.linalg.norm(np.asarray(n, dtype=np.float64) @ np.linalg.inv(u), axis=1)
+
+
+class StructureFactor:
+    """S(q) and, with dynamic=True, the coherent F(q, t), accumulated on the device until reset().
+
+    The wave vectors are select_wave_vectors(unitcell, q_max, dq, max_per_bin, seed) of the cell the sampler is first used
+    on.  Static samples are taken at every `every`-th output step of run_simulation(..., sq=...).  dynamic=True adds the
+    correlations on SelfDynamics' schedule: lags=None is the reference's log-time schedule, explicit positive `lags` need
+    `origin_every` (at most 64 origin slots); at a step that has both, the samples are taken before the new origin is
+    stored.  An origin costs 2 nvec doubles.
+
+    Fields: n (nvec, d), qvec (|q| per vector), bin (per vector: index into q), q (mean |q| of a bin), nvectors (per bin),
+    nstatic, s2 (per vector: sum |rho|^2), lags, nsamples (per lag), corr (nlags, nvec: sum Re rho(t0 + t) rho*(t0))."""
+
+    def __init__(self, q_max, dq=None, max_per_bin=16, seed=0, every=1, lags=None, origin_every=None, dynamic=False):
+        q_max, max_per_bin, every = float(q_max), int(max_per_bin), int(every)
+        if not (q_max > 0.0 and math.isfinite(q_max)):
+            raise ValueError("q_max must be finite and > 0")
+        if dq is not None and not (float(dq) > 0.0 and math.isfinite(float(dq))):
+            raise ValueError("dq must be finite and > 0")
+        if max_per_bin < 1:
+            raise ValueError("max_per_bin must be >= 1")
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        self.q_max, self.dq, self.max_per_bin, self.seed, self.every = q_max, dq, max_per_bin, seed, every
+        self.dynamic = bool(dynamic)
+        if self.dynamic:
+            self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+        else:
+            if lags is not None or origin_every is not None:
+                raise ValueError("lags and origin_every need dynamic=True")
+            self.maxlog, lag_list, self.origin_every, self.nslots = None, [], None, 0
+        self.lags = np.array(lag_list, dtype=np.int64)
+        self.nsamples = np.zeros(len(lag_list), dtype=np.int64)
+        self.nstatic = 0
+        self.unitcell = None
+        self.n = self.qvec = self.bin = self.q = self.nvectors = self.s2 = self.corr = None
+        self.n_particles = 0
+        self.dt = 1.0
+
+    def _select(self, unitcell):
+        u = np.array(unitcell, dtype=np.float64)
+        if self.unitcell is not None:
+            if u.shape != self.unitcell.shape or not np.array_equal(u, self.unitcell):
+                raise ValueError("the unit cell differs from the one the wave vectors were selected for; reset() first")
+            return
+        n, q, b = select_wave_vectors(u, self.q_max, self.dq, self.max_per_bin, self.seed)
+        self._set_vectors(u, n, q, b)
+
+    def _set_vectors(self, unitcell, n, q, b):
+        self.unitcell = unitcell
+        self.n, self.qvec = np.ascontiguousarray(n, dtype=np.int32), np.asarray(q, dtype=np.float64)
+        bins, self.bin = np.unique(np.asarray(b), return_inverse=True)
+        self.bin = self.bin.reshape(-1)
+        self.nvectors = np.bincount(self.bin, minlength=bins.size).astype(np.int64)
+        self.q = np.bincount(self.bin, weights=self.qvec, minlength=bins.size) / self.nvectors
+        self.s2 = np.zeros(self.n.shape[0])
+        self.corr = np.zeros((len(self.lags), self.n.shape[0]))
+
+    def reset(self):
+        """Forget the samples and the wave vectors (the next use selects them again, for the cell it meets)."""
+        self.nsamples[:] = 0
+        self.nstatic = 0
+        self.unitcell = None
+        self.n = self.qvec = self.bin = self.q = self.nvectors = self.s2 = self.corr = None
+
+    def schedule(self, total_steps):
+        """(stops, events) of the dynamic part, as SelfDynamics.schedule; empty without dynamic=True."""
+        if not self.dynamic:
+            return [], {}
+        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
+
+    def _accumulate(self, nstatic, s2, nsamples, corr, n_particles, dt):
+        self.nstatic += int(nstatic)
+        self.s2 += np.asarray(s2, dtype=np.float64)
+        if self.dynamic:
+            self.nsamples += np.asarray(nsamples, dtype=np.int64)
+            self.corr += np.asarray(corr, dtype=np.float64)
+        self.n_particles, self.dt = int(n_particles), float(dt)
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    def _binned(self, per_vector):
+        return np.bincount(self.bin, weights=per_vector, minlength=self.q.size) / self.nvectors
+
+    def s_vectors(self):
+        """S(q_v) per wave vector: s2_v / (nstatic N); nan before the first static sample."""
+        if self.nstatic == 0:
+            return np.full(self.s2.shape, np.nan)
+        return self.s2 / (self.nstatic * self.n_particles)
+
+    def s(self):
+        """S(q) per |q| bin: sum over the bin's vectors of s2_v / (nstatic N M_bin)."""
+        return self._binned(self.s_vectors())
+
+    def f_vectors(self):
+        """F(q_v, t), (nlags, nvec): corr_kv / (ns_k N); nan where a lag has no sample."""
+        ns = self.nsamples.astype(np.float64)[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ns > 0, self.corr / (ns * self.n_particles), np.nan)
+
+    def f(self):
+        """F(q, t), (nlags, nbins): sum over the bin's vectors of corr_kv / (ns_k N M_bin)."""
+        fv = self.f_vectors()
+        return np.array([self._binned(fv[k]) for k in range(fv.shape[0])]).reshape(fv.shape[0], self.q.size)
+
+    def f_normalised(self):
+        """F(q, t) / S(q), (nlags, nbins)."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.f() / self.s()[None, :]
+
+    def write(self, path):
+        """# q S(q) nvectors nsamples, one row per |q| bin."""
+        sq = self.s()
+        with open(path, "w") as io:
+            io.write("# q S(q) nvectors nsamples\n")
+            for b in range(self.q.size):
+                io.write("%.6f %.6e %d %d\n" % (self.q[b], sq[b], self.nvectors[b], self.nstatic))
+
+    def write_fqt(self, path, dt=None):
+        """One block per lag that has a sample, lines `lag time q F F/S nsamples`, a blank line between blocks."""
+        dt = self.dt if dt is None else float(dt)
+        f, fn = self.f(), self.f_normalised()
+        with open(path, "w") as io:
+            io.write("# lag time q F F/S nsamples\n")
+            first = True
+            for k, l in enumerate(self.lags):
+                if self.nsamples[k] == 0:
+                    continue
+                if not first:
+                    io.write("\n")
+                first = False
+                for b in range(self.q.size):
+                    io.write("%d %.6e %.6f %.6e %.6e %d\n" % (int(l), l * dt, self.q[b], f[k, b], fn[k, b],
+                                                            int(self.nsamples[k])))
+
+
+def _sq_start(dev, sq, unitcell):
+    sq._select(unitcell)
+    dev.sq_setup(sq.n, sq.nslots, len(sq.lags))
+
+
+def _sq_act(dev, static, event):
+    """The sampler's work at one stop: rho of the frame once, then the static sample, the correlations, the origin."""
+    smp, org = event if event is not None else ([], None)
+    dev.sq_sample(static, [a for a, _ in smp], [b for _, b in smp], org)
+
+
+def _sq_collect(dev, sq, n_particles, dt):
+    nst, s2, ns, corr = dev.sq_read()
+    sq._accumulate(nst, s2, ns, corr, n_particles, dt)
+
+
+def compute_sq(state, params, q_max, dq=None, max_per_bin=16, seed=0):
+    """One static sample of S(q) of `state`'s positions, taken on its device handle; returns a StructureFactor."""
+    sq = StructureFactor(q_max, dq=dq, max_per_bin=max_per_bin, seed=seed)
+    dev = state.system.device
+    dev.upload(x=state.system.positions, images=state.images)
+    _sq_start(dev, sq, state.unitcell)
+    dev.sq_sample(True)
+    _sq_collect(dev, sq, dev.n, params.dt)
+    return sq

@@ -12,6 +12,7 @@
 #include "md_domain.hpp"
 #include "md_rdf.hpp"
 #include "md_dyn.hpp"
+#include "md_sq.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -307,6 +308,20 @@ struct md_ctx {
         }
         ~Dyn() { release_slots(); }
     } dyn;
+
+    // density modes (md_sq_*): the wave vectors, the current frame and its fractional coordinates, block partials, rho of
+    // the last sampled frame, the static and the correlation accumulators, rho of the stored origins
+    struct Sq {
+        bool on = false;
+        int nvec = 0, nvec_pad = 0, nslots = 0, nrows = 0, nblk = 0;
+        bool sampled = false;             // rho holds a frame
+        int64_t nstatic = 0;
+        std::vector<char> filled;         // nslots: the slot holds an origin
+        std::vector<int64_t> nsamples;    // nrows
+        DBuf<double> nd;                  // nvec_pad x 3 wave vectors as doubles
+        DBuf<double> cx, fr, part, rho, s2, corr, org; // frame; f per axis; (vector, comp, block); 2 nvec; nvec; nrows x nvec; nslots x nvec x 2
+        DBuf<int32_t> ci;
+    } sq;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -2181,6 +2196,192 @@ int md_dyn_reset(md_ctx *ctx)
     HIPCHK(hipMemsetAsync(Y.hist.p, 0, sizeof(unsigned long long) * Y.nrows * std::max(Y.nbins, 1), st));
     HIPCHK(hipStreamSynchronize(st));
     std::fill(Y.nsamples.begin(), Y.nsamples.end(), (int64_t)0);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Density modes, S(q) and coherent F(q, t) (md_sq.hpp): a sample launches k_export into the sampler's own frame buffer and
+// reads nothing else of the state, so the step loop, the list and the cell order are what they would have been without it.
+static md_ctx::Sq &sq_of(md_ctx *ctx, const char *who)
+{
+    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
+    if (!ctx->sq.on) throw HipError(std::string(who) + ": no setup (call md_sq_setup first)");
+    return ctx->sq;
+}
+
+int md_sq_setup(md_ctx *ctx, const int32_t *nvecs, int nvec, int nslots, int nrows)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_sq_setup: not available on a slab-decomposition handle");
+    char b[240];
+    if (nvec < 1 || nvec > MD_SQ_MAX_VEC) {
+        snprintf(b, sizeof b, "md_sq_setup: nvec must be in 1..%d, got %d", MD_SQ_MAX_VEC, nvec);
+        throw HipError(b);
+    }
+    if (!nvecs) throw HipError("md_sq_setup: n is null");
+    if (nslots < 0 || nslots > MD_SQ_MAX_SLOTS) {
+        snprintf(b, sizeof b, "md_sq_setup: nslots must be in 0..%d, got %d", MD_SQ_MAX_SLOTS, nslots);
+        throw HipError(b);
+    }
+    if (nrows < 0) {
+        snprintf(b, sizeof b, "md_sq_setup: nrows must be >= 0, got %d", nrows);
+        throw HipError(b);
+    }
+    const int dim = ctx->dim;
+    for (int v = 0; v < nvec; ++v) {
+        bool zero = true;
+        for (int c = 0; c < dim; ++c) {
+            const int32_t k = nvecs[(size_t)v * dim + c];
+            if (k < -MD_SQ_MAX_N || k > MD_SQ_MAX_N) {
+                snprintf(b, sizeof b, "md_sq_setup: component %d of vector %d is %d, outside -%d..%d", c, v, (int)k,
+                         MD_SQ_MAX_N, MD_SQ_MAX_N);
+                throw HipError(b);
+            }
+            zero = zero && k == 0;
+        }
+        if (zero) {
+            snprintf(b, sizeof b, "md_sq_setup: vector %d is n = 0 (rho(0) = N carries no information)", v);
+            throw HipError(b);
+        }
+    }
+    md_ctx::Sq &S = ctx->sq;
+    S.on = false;
+    const int64_t n = ctx->n;
+    const size_t frame = (size_t)n * dim;
+    const int nblk = (int)((n + MD_SQ_BLOCK * MD_SQ_PPT - 1) / (MD_SQ_BLOCK * MD_SQ_PPT));
+    const int nvec_pad = (nvec + MD_SQ_TILE - 1) / MD_SQ_TILE * MD_SQ_TILE;
+    std::vector<double> nd((size_t)nvec_pad * 3, 0.0);
+    for (int v = 0; v < nvec; ++v)
+        for (int c = 0; c < dim; ++c) nd[(size_t)v * 3 + c] = (double)nvecs[(size_t)v * dim + c];
+    S.nd.alloc(nd.size());
+    S.cx.alloc(frame);
+    S.ci.alloc(frame);
+    S.fr.alloc(frame);
+    S.part.alloc((size_t)nvec_pad * 2 * nblk);
+    S.rho.alloc((size_t)nvec * 2);
+    S.s2.alloc(nvec);
+    S.corr.alloc((size_t)nrows * nvec);
+    S.org.alloc((size_t)nslots * nvec * 2);
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemcpyAsync(S.nd.p, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(S.rho.p, 0, sizeof(double) * nvec * 2, st));
+    HIPCHK(hipMemsetAsync(S.s2.p, 0, sizeof(double) * nvec, st));
+    if (nrows) HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * nrows * nvec, st));
+    if (nslots) HIPCHK(hipMemsetAsync(S.org.p, 0, sizeof(double) * nslots * nvec * 2, st));
+    HIPCHK(hipStreamSynchronize(st)); // (the vector table is a host vector)
+    S.nvec = nvec;
+    S.nvec_pad = nvec_pad;
+    S.nslots = nslots;
+    S.nrows = nrows;
+    S.nblk = nblk;
+    S.sampled = false;
+    S.nstatic = 0;
+    S.filled.assign(nslots, 0);
+    S.nsamples.assign(nrows, 0);
+    S.on = true;
+    API_END
+}
+
+int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_t *rows, int count, int origin_slot)
+{
+    API_BEGIN
+    md_ctx::Sq &S = sq_of(ctx, "md_sq_sample");
+    require_state(ctx, "md_sq_sample");
+    char b[200];
+    if (count < 0) {
+        snprintf(b, sizeof b, "md_sq_sample: count must be >= 0, got %d", count);
+        throw HipError(b);
+    }
+    if (count > 0 && (!slots || !rows)) throw HipError("md_sq_sample: slots / rows is null");
+    for (int i = 0; i < count; ++i) {
+        if (slots[i] < 0 || slots[i] >= S.nslots) {
+            snprintf(b, sizeof b, "md_sq_sample: slot %d is out of range 0..%d", (int)slots[i], S.nslots - 1);
+            throw HipError(b);
+        }
+        if (rows[i] < 0 || rows[i] >= S.nrows) {
+            snprintf(b, sizeof b, "md_sq_sample: row %d is out of range 0..%d", (int)rows[i], S.nrows - 1);
+            throw HipError(b);
+        }
+        if (!S.filled[slots[i]]) {
+            snprintf(b, sizeof b, "md_sq_sample: slot %d is empty (store an origin with origin_slot first)", (int)slots[i]);
+            throw HipError(b);
+        }
+    }
+    if (origin_slot < -1 || origin_slot >= S.nslots) {
+        snprintf(b, sizeof b, "md_sq_sample: origin slot %d is out of range -1..%d", origin_slot, S.nslots - 1);
+        throw HipError(b);
+    }
+    hipStream_t st = ctx->stream;
+    const int n = (int)ctx->n;
+    DevState s = ctx->dev(ctx->cur);
+    if (ctx->dim == 3) {
+        k_export<3><<<ctx->nblk, MD_BLOCK, 0, st>>>(n, s, ctx->grid, S.cx.p, nullptr, nullptr, S.ci.p);
+        k_sq_frac<3><<<nblocks(n), MD_BLOCK, 0, st>>>(n, ctx->grid, S.cx.p, S.fr.p);
+        k_sq_rho<3><<<dim3(S.nblk, S.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(n, S.nblk, S.fr.p, S.nd.p, S.part.p);
+    } else {
+        k_export<2><<<ctx->nblk, MD_BLOCK, 0, st>>>(n, s, ctx->grid, S.cx.p, nullptr, nullptr, S.ci.p);
+        k_sq_frac<2><<<nblocks(n), MD_BLOCK, 0, st>>>(n, ctx->grid, S.cx.p, S.fr.p);
+        k_sq_rho<2><<<dim3(S.nblk, S.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(n, S.nblk, S.fr.p, S.nd.p, S.part.p);
+    }
+    HIPCHK(hipGetLastError());
+    const int rblk = (S.nvec + MD_SQ_REDUCE_BLOCK / 64 - 1) / (MD_SQ_REDUCE_BLOCK / 64);
+    int i0 = 0;
+    do {
+        SqBatch B{};
+        B.count = std::min(count - i0, MD_SQ_MAX_BATCH);
+        for (int i = 0; i < B.count; ++i) {
+            B.slot[i] = slots[i0 + i];
+            B.row[i] = rows[i0 + i];
+        }
+        const bool last = i0 + B.count >= count;
+        k_sq_reduce<<<rblk, MD_SQ_REDUCE_BLOCK, 0, st>>>(S.nvec, S.nblk, i0 == 0, add_static != 0, B, last ? origin_slot : -1,
+                                                        S.part.p, S.rho.p, S.s2.p, S.corr.p, S.org.p);
+        HIPCHK(hipGetLastError());
+        i0 += B.count;
+    } while (i0 < count);
+    S.sampled = true;
+    if (add_static) ++S.nstatic;
+    for (int i = 0; i < count; ++i) ++S.nsamples[rows[i]];
+    if (origin_slot >= 0) S.filled[origin_slot] = 1;
+    API_END
+}
+
+int md_sq_rho(md_ctx *ctx, double *rho)
+{
+    API_BEGIN
+    md_ctx::Sq &S = sq_of(ctx, "md_sq_rho");
+    if (!S.sampled) throw HipError("md_sq_rho: no frame has been sampled since md_sq_setup");
+    if (!rho) throw HipError("md_sq_rho: rho is null");
+    HIPCHK(hipMemcpyAsync(rho, S.rho.p, sizeof(double) * S.nvec * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    API_END
+}
+
+int md_sq_read(md_ctx *ctx, int64_t *nstatic, double *s2, int64_t *nsamples, double *corr)
+{
+    API_BEGIN
+    md_ctx::Sq &S = sq_of(ctx, "md_sq_read");
+    hipStream_t st = ctx->stream;
+    if (s2) HIPCHK(hipMemcpyAsync(s2, S.s2.p, sizeof(double) * S.nvec, hipMemcpyDeviceToHost, st));
+    if (corr && S.nrows)
+        HIPCHK(hipMemcpyAsync(corr, S.corr.p, sizeof(double) * S.nrows * S.nvec, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nstatic) *nstatic = S.nstatic;
+    if (nsamples)
+        for (int r = 0; r < S.nrows; ++r) nsamples[r] = S.nsamples[r];
+    API_END
+}
+
+int md_sq_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    md_ctx::Sq &S = sq_of(ctx, "md_sq_reset");
+    hipStream_t st = ctx->stream;
+    HIPCHK(hipMemsetAsync(S.s2.p, 0, sizeof(double) * S.nvec, st));
+    if (S.nrows) HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * S.nrows * S.nvec, st));
+    HIPCHK(hipStreamSynchronize(st));
+    S.nstatic = 0;
+    std::fill(S.nsamples.begin(), S.nsamples.end(), (int64_t)0);
     API_END
 }
 

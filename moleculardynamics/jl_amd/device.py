@@ -224,6 +224,47 @@ class MDDevice:
     def dyn_reset(self):
         self._chk(self._L.md_dyn_reset(self._h))
 
+    # -- density modes, S(q), coherent F(q, t) --------------------------------------------
+    def sq_setup(self, n, nslots=0, nrows=0):
+        """Allocate the device density-mode sampler (md_sq_setup): the integer wave vectors n (nvec, d), q_n = 2 pi U^-T n,
+        nslots origin slots and nrows correlation rows, all zeroed."""
+        na = np.ascontiguousarray(n, dtype=np.int32)
+        if na.ndim != 2 or na.shape[1] != self.dim:
+            raise ValueError(f"n must have shape (nvec, {self.dim})")
+        self._chk(self._L.md_sq_setup(self._h, _ip(na) if na.size else None, int(na.shape[0]), int(nslots), int(nrows)))
+        self._sq_shape = (int(na.shape[0]), int(nrows))
+
+    def sq_sample(self, static=True, slots=(), rows=(), origin=None):
+        """Evaluate rho(q) of the current frame once; then add |rho|^2 to the static accumulator if `static`, one
+        correlation per (slots[i], rows[i]) -- this frame against the origin in slots[i], into rows[i] -- and store rho in
+        slot `origin` unless it is None, in that order (does not wait, changes no state)."""
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        if s.shape != r.shape:
+            raise ValueError("slots and rows must have the same length")
+        self._chk(self._L.md_sq_sample(self._h, 1 if static else 0, _ip(s) if s.size else None, _ip(r) if r.size else None,
+                                       int(s.size), -1 if origin is None else int(origin)))
+
+    def sq_rho(self):
+        """rho(q) of the last sampled frame, complex128[nvec] (rho = sum exp(+i q.x)); waits."""
+        nvec, _ = getattr(self, "_sq_shape", (0, 0))
+        out = np.zeros((max(nvec, 1), 2))
+        self._chk(self._L.md_sq_rho(self._h, _dp(out)))
+        return out[:nvec].copy().view(np.complex128).reshape(nvec)
+
+    def sq_read(self):
+        """(nstatic, s2 float64[nvec], nsamples int64[nrows], corr float64[nrows, nvec]), summed since setup / reset."""
+        nvec, nrows = getattr(self, "_sq_shape", (0, 0))
+        nst = C.c_int64()
+        s2 = np.zeros(max(nvec, 1))
+        ns = np.zeros(max(nrows, 1), dtype=np.int64)
+        corr = np.zeros((max(nrows, 1), max(nvec, 1)))
+        self._chk(self._L.md_sq_read(self._h, C.byref(nst), _dp(s2), ns.ctypes.data_as(C.POINTER(C.c_int64)), _dp(corr)))
+        return nst.value, s2[:nvec], ns[:nrows], corr[:nrows, :nvec]
+
+    def sq_reset(self):
+        self._chk(self._L.md_sq_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

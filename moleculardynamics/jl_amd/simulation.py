@@ -35,7 +35,7 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None):
+                   dynamics=None, sq=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -46,7 +46,12 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     at the steps of its schedule (by default the log-time steps `log_times=True` writes snapshots at); the schedule
     restarts at step 0 in every call and the samples accumulate in the object.  At the end it is written to
     pathname/dynamics.txt (and pathname/vanhove.txt when it has bins).  Its stops are added to the loop's output steps;
-    nothing else the run produces changes."""
+    nothing else the run produces changes.
+
+    sq: a StructureFactor (analysis.py) to sample S(q) into, on the device, at every sq.every-th output step and, with
+    dynamic=True, the coherent F(q, t) at the steps of its schedule (SelfDynamics' rules: the stops are added to the
+    loop's output steps, the schedule restarts at step 0 in every call).  Written to pathname/sq.txt and, if dynamic,
+    pathname/fqt.txt.  Nothing else the run produces changes."""
     brownian = isinstance(ensemble, Brownian)
     os.makedirs(pathname, exist_ok=True)
     trajectory_file, thermo_file = _io.open_files(pathname, traj_name, thermo_name)
@@ -72,6 +77,10 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     if dynamics is not None:
         dyn_stops, dyn_events = dynamics.schedule(total_steps)
         _analysis._dyn_start(dev, dynamics)
+    sq_stops, sq_events, sq_i = [], {}, 0
+    if sq is not None:
+        sq_stops, sq_events = sq.schedule(total_steps)
+        _analysis._sq_start(dev, sq, state.unitcell)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -121,6 +130,10 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             dyn_i += 1
         if dyn_i < len(dyn_stops):
             next_out = min(next_out, dyn_stops[dyn_i])
+        while sq_i < len(sq_stops) and sq_stops[sq_i] < step:
+            sq_i += 1
+        if sq_i < len(sq_stops):
+            next_out = min(next_out, sq_stops[sq_i])
         last = min(next_out, total_steps - 1)
         U, W, K = segment(step, last - step + 1)
         collect()                       # the frame exported before this segment: its copy had the whole segment to finish
@@ -149,6 +162,14 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         if dyn_i < len(dyn_stops) and dyn_stops[dyn_i] == last:
             _analysis._dyn_act(dev, dyn_events[last])
             dyn_i += 1
+        if sq is not None:
+            sq_static = last % frequency == 0 and (last // frequency) % sq.every == 0
+            sq_event = None
+            if sq_i < len(sq_stops) and sq_stops[sq_i] == last:
+                sq_event = sq_events[last]
+                sq_i += 1
+            if sq_static or sq_event is not None:
+                _analysis._sq_act(dev, sq_static, sq_event)
         if snapshot_times is not None and snap_i < len(snapshot_times) and snapshot_times[snap_i] == last:
             pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w"))
             want_frame = True
@@ -176,6 +197,11 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         dynamics.write(os.path.join(pathname, "dynamics.txt"))
         if dynamics.nbins > 0:
             dynamics.write_van_hove(os.path.join(pathname, "vanhove.txt"))
+    if sq is not None:
+        _analysis._sq_collect(dev, sq, n, params.dt)
+        sq.write(os.path.join(pathname, "sq.txt"))
+        if sq.dynamic:
+            sq.write_fqt(os.path.join(pathname, "fqt.txt"))
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
