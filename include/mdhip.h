@@ -256,6 +256,8 @@ typedef struct {
     int64_t rebuilds_timed; /* list builds timed since md_profile(ctx, k): every one, whatever the stride */
     double rebuild_ms;      /* their summed duration, from the end of the last step before the build to the point where
                                the next step can start (state conversion, sort, gather, rows, host waits included) */
+    int64_t fused_build;    /* 1: the rows of the last build came from the fused per-tile kernel (k_build_tile), 0: from the
+                               two-kernel fallback (a tile or a cell did not fit it) */
 } md_stats;
 /* enable = 0: off; 1: HIP events around every force and kick-drift launch; k > 1: around every k-th launch of each
  * (an event record costs a few microseconds of device time: sampling keeps a timed run honest) */

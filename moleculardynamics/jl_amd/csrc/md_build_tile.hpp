@@ -28,28 +28,66 @@
 // Sweep of a thread's share of the 27 (9) neighbour cells over the LDS image.  The cell loop is
 // fully unrolled (MD_HALF_CELLS iterations, cells beyond the thread's share are skipped) so
 // that the per-cell hit masks live in registers:
-//   tile_sweep_mark : tests d^2 <= rl^2 for every staged particle of each cell, eight at a
-//                     time, marks the particles the tile keeps (branch-free byte store; misses
-//                     write a trash slot), records one 64-bit hit mask per cell;
-//   tile_sweep_emit : walks the set bits only and writes the row entries -- no distance is
-//                     computed twice.
+//   tile_sweep_mark     : tests d^2 <= rl^2 for every staged particle of each cell, four at a
+//                         time, and records the hits of a cell as two 32-bit words (candidates
+//                         0-31 / 32-63 of the cell's staged range);
+//   tile_sweep_emit_lds : walks the set bits only and writes the row entries -- no distance is
+//                         computed twice.
 // A cell holding more than 64 particles does not fit a mask: the tile reports overflow and the
 // host falls back to the two-kernel build.
 #define MD_HALF_CELLS 14
 
 typedef float md_f2 __attribute__((ext_vector_type(2)));
 
+// Hit word of the staged candidates [qa, qb) (at most 32, a multiple of 4): bit c is set iff candidate qa + c lies
+// within rl.  d^2 <= rl2f holds exactly when the sign bit of rl2f - d^2 is clear (equality gives +0, a pad entry
+// d^2 = inf), so every candidate costs one v_alignbit_b32 that shifts its sign bit into the word -- no compare, no
+// select, no shift by a loop-carried amount.  (Non-finite coordinates never get here: the staging turns them into
+// pad entries and the thread's own into -1e30, so that no NaN can reach a sign bit.)
+template <int D>
+__device__ __forceinline__ unsigned tile_sweep_word(md_f2 xi2, md_f2 yi2, md_f2 zi2, md_f2 rl2, int qa, int qb,
+                                                    const float *px, const float *py, const float *pz)
+{
+    unsigned w = ~0u; // sign bits: 1 = miss
+    // four candidates per iteration, two per packed fp32 instruction (v_pk_add/mul/fma_f32)
+    for (int q0 = qa; q0 < qb; q0 += 4) {
+        float4 x4 = *(const float4 *)(px + q0);
+        float4 y4 = *(const float4 *)(py + q0);
+        md_f2 dxa = md_f2{x4.x, x4.y} - xi2, dxb = md_f2{x4.z, x4.w} - xi2;
+        md_f2 dya = md_f2{y4.x, y4.y} - yi2, dyb = md_f2{y4.z, y4.w} - yi2;
+        md_f2 da = dxa * dxa, db = dxb * dxb;
+        da = __builtin_elementwise_fma(dya, dya, da);
+        db = __builtin_elementwise_fma(dyb, dyb, db);
+        if constexpr (D == 3) {
+            float4 z4 = *(const float4 *)(pz + q0);
+            md_f2 dza = md_f2{z4.x, z4.y} - zi2, dzb = md_f2{z4.z, z4.w} - zi2;
+            da = __builtin_elementwise_fma(dza, dza, da);
+            db = __builtin_elementwise_fma(dzb, dzb, db);
+        }
+        // (pad entries are 1e30 away: d^2 = inf, they never hit)
+        const md_f2 ta = rl2 - da, tb = rl2 - db;
+        w = __builtin_amdgcn_alignbit(w, __float_as_uint(ta.x), 31); // (w << 1) | sign
+        w = __builtin_amdgcn_alignbit(w, __float_as_uint(ta.y), 31);
+        w = __builtin_amdgcn_alignbit(w, __float_as_uint(tb.x), 31);
+        w = __builtin_amdgcn_alignbit(w, __float_as_uint(tb.y), 31);
+    }
+    // candidate c sits at bit count-1-c of w, ones above: reverse the complement and drop the 32 - count low bits
+    // (count = 32: no shift; count <= 0: ~w is 0 whatever the shift)
+    return __brev(~w) >> ((32 - (qb - qa)) & 31);
+}
+
 template <int D>
 __device__ __forceinline__ int tile_sweep_mark(float xi, float yi, float zi, const uint16_t *ctab_row, float rl2f,
                                                int self_q, int n0, int n1, const float *px, const float *py,
-                                               const float *pz, const int *coff, unsigned long long *refmask,
-                                               unsigned long long *mask, int *qstart, bool *too_big)
+                                               const float *pz, const int *coff, unsigned *refmask, unsigned *mask0,
+                                               unsigned *mask1, int *qstart, bool *too_big)
 {
     int cnt = 0;
-    const md_f2 xi2 = {xi, xi}, yi2 = {yi, yi}, zi2 = {zi, zi};
+    const md_f2 xi2 = {xi, xi}, yi2 = {yi, yi}, zi2 = {zi, zi}, rl2 = {rl2f, rl2f};
 #pragma unroll
     for (int ci = 0; ci < MD_HALF_CELLS; ++ci) {
-        mask[ci] = 0ull;
+        mask0[ci] = 0u;
+        mask1[ci] = 0u;
         qstart[ci] = 0;
         int nbi = n0 + ci;
         if (nbi >= n1) continue;
@@ -61,56 +99,22 @@ __device__ __forceinline__ int tile_sweep_mark(float xi, float yi, float zi, con
             continue;
         }
         qstart[ci] = qs;
-        unsigned long long mk = 0ull;
-        // four candidates per iteration, two per packed fp32 instruction (v_pk_add/mul/fma_f32); their four hit
-        // bits are assembled as a nibble and shifted into the cell's mask once
-        for (int q0 = qs; q0 < qe; q0 += 4) {
-            float4 x4 = *(const float4 *)(px + q0);
-            float4 y4 = *(const float4 *)(py + q0);
-            md_f2 dxa = md_f2{x4.x, x4.y} - xi2, dxb = md_f2{x4.z, x4.w} - xi2;
-            md_f2 dya = md_f2{y4.x, y4.y} - yi2, dyb = md_f2{y4.z, y4.w} - yi2;
-            md_f2 da = dxa * dxa, db = dxb * dxb;
-            da = __builtin_elementwise_fma(dya, dya, da);
-            db = __builtin_elementwise_fma(dyb, dyb, db);
-            if constexpr (D == 3) {
-                float4 z4 = *(const float4 *)(pz + q0);
-                md_f2 dza = md_f2{z4.x, z4.y} - zi2, dzb = md_f2{z4.z, z4.w} - zi2;
-                da = __builtin_elementwise_fma(dza, dza, da);
-                db = __builtin_elementwise_fma(dzb, dzb, db);
-            }
-            // (pad entries are 1e30 away: they never hit)
-            unsigned nib = (da.x <= rl2f ? 1u : 0u) | (da.y <= rl2f ? 2u : 0u) | (db.x <= rl2f ? 4u : 0u) |
-                           (db.y <= rl2f ? 8u : 0u);
-            mk |= (unsigned long long)nib << (q0 - qs);
-        }
+        unsigned m0 = tile_sweep_word<D>(xi2, yi2, zi2, rl2, qs, min(qs + 32, qe), px, py, pz);
+        unsigned m1 = tile_sweep_word<D>(xi2, yi2, zi2, rl2, qs + 32, qe, px, py, pz);
         // the particle itself sits in its own cell's range
-        if (self_q >= qs && self_q < qe) mk &= ~(1ull << (self_q - qs));
-        // which staged particles the tile references at all: one 64-bit OR per (particle, cell)
-        if (mk) atomicOr(&refmask[lo], mk);
-        mask[ci] = mk;
-        cnt += __popcll(mk);
-    }
-    return cnt;
-}
-
-__device__ __forceinline__ int tile_sweep_emit(const unsigned long long *mask, const int *qstart,
-                                               const uint16_t *newidx, uint16_t *rowbase, int lane, int maxn,
-                                               int cnt0, int rs)
-{
-    int cnt = cnt0;
-#pragma unroll
-    for (int ci = 0; ci < MD_HALF_CELLS; ++ci) {
-        unsigned long long mk = mask[ci];
-        int qs = qstart[ci];
-        while (mk) {
-            int b = __ffsll((long long)mk) - 1;
-            mk &= mk - 1ull;
-            unsigned v = (unsigned)newidx[qs + b] * (unsigned)rs;
-            // (entry-by-entry 2-byte stores: collecting four entries into one 8-byte store made this sweep 50 %
-            // slower -- the bookkeeping in the divergent bit walk costs more than the stores)
-            if (cnt < maxn) rowbase[row_off(cnt, lane)] = (uint16_t)v;
-            ++cnt;
+        const unsigned so = (unsigned)(self_q - qs);
+        if (so < (unsigned)(qe - qs)) {
+            if (so < 32u)
+                m0 &= ~(1u << so);
+            else
+                m1 &= ~(1u << (so - 32u));
         }
+        // which staged particles the tile references at all: one 32-bit OR per (particle, cell, word)
+        if (m0) atomicOr(&refmask[2 * lo], m0);
+        if (m1) atomicOr(&refmask[2 * lo + 1], m1);
+        mask0[ci] = m0;
+        mask1[ci] = m1;
+        cnt += __popc(m0) + __popc(m1);
     }
     return cnt;
 }
@@ -119,40 +123,72 @@ __device__ __forceinline__ int tile_sweep_emit(const unsigned long long *mask, c
 #define MD_ROWPITCH 132  // LDS row buffer of the emit phase: 256 rows x 132 entries x 2 bytes, over the dead phase-1 arrays
 #define MD_BT_POOL 68864
 
-// Walks the set bits of the per-cell hit masks and appends the hits to an LDS row as STAGED indices (the copy-out
+// Walks the set bits of the per-cell hit words and appends the hits to an LDS row as STAGED indices (the copy-out
 // translates them to halo offsets with independent, pipelined lookups -- a lookup inside this walk would put one
-// dependent LDS round trip on every trip of a divergent loop).  Two bits per trip.  Entries beyond the row buffer's
-// pitch (rows of more than MD_ROWPITCH entries: rare) go straight to global memory, translated here.
-__device__ __forceinline__ int tile_sweep_emit_lds(const unsigned long long *mask, const int *qstart,
+// dependent LDS round trip on every trip of a divergent loop).  Two bits per trip, all in 32-bit arithmetic.
+// GUARD = false: the caller knows that the row ends within the row buffer's pitch, the walk tests nothing.
+// GUARD = true: entries beyond the pitch (rows of more than MD_ROWPITCH entries: rare) go straight to global
+// memory, translated here.
+template <bool GUARD>
+__device__ __forceinline__ int tile_emit_word(unsigned m, int qb, const uint16_t *newidx, uint16_t *row,
+                                              uint16_t *grow, int lane, int maxn, int cnt, int rs)
+{
+    while (m) {
+        const int b1 = __ffs((int)m) - 1;
+        const unsigned m1 = m & (m - 1u);
+        const int b2 = __ffs((int)m1) - 1; // (-1 when m1 == 0: not stored)
+        m = m1 & (m1 - 1u);
+        if (!GUARD || cnt + 1 < MD_ROWPITCH) {
+            row[cnt] = (uint16_t)(qb + b1);
+            if (m1) row[cnt + 1] = (uint16_t)(qb + b2);
+        } else {
+            if (cnt < MD_ROWPITCH)
+                row[cnt] = (uint16_t)(qb + b1);
+            else if (cnt < maxn)
+                grow[row_off(cnt, lane)] = (uint16_t)((unsigned)newidx[qb + b1] * (unsigned)rs);
+            if (m1 && cnt + 1 < maxn) grow[row_off(cnt + 1, lane)] = (uint16_t)((unsigned)newidx[qb + b2] * (unsigned)rs);
+        }
+        cnt += m1 ? 2 : 1;
+    }
+    return cnt;
+}
+
+template <bool GUARD>
+__device__ __forceinline__ int tile_sweep_emit_lds(const unsigned *mask0, const unsigned *mask1, const int *qstart,
                                                    const uint16_t *newidx, uint16_t *row, uint16_t *grow, int lane,
                                                    int maxn, int cnt0, int rs)
 {
     int cnt = cnt0;
 #pragma unroll
     for (int ci = 0; ci < MD_HALF_CELLS; ++ci) {
-        unsigned long long mk = mask[ci];
         const int qs = qstart[ci];
-        while (mk) {
-            int b1 = __ffsll((long long)mk) - 1;
-            unsigned long long m1 = mk & (mk - 1ull);
-            int b2 = __ffsll((long long)m1) - 1; // (-1 when m1 == 0: not stored)
-            mk = m1 & (m1 - 1ull);
-            if (cnt + 1 < MD_ROWPITCH) {
-                row[cnt] = (uint16_t)(qs + b1);
-                if (m1) row[cnt + 1] = (uint16_t)(qs + b2);
-            } else {
-                if (cnt < MD_ROWPITCH)
-                    row[cnt] = (uint16_t)(qs + b1);
-                else if (cnt < maxn)
-                    grow[row_off(cnt, lane)] = (uint16_t)((unsigned)newidx[qs + b1] * (unsigned)rs);
-                if (m1 && cnt + 1 < maxn) grow[row_off(cnt + 1, lane)] = (uint16_t)((unsigned)newidx[qs + b2] * (unsigned)rs);
-            }
-            cnt += m1 ? 2 : 1;
-        }
+        cnt = tile_emit_word<GUARD>(mask0[ci], qs, newidx, row, grow, lane, maxn, cnt, rs);
+        cnt = tile_emit_word<GUARD>(mask1[ci], qs + 32, newidx, row, grow, lane, maxn, cnt, rs);
     }
     return cnt;
 }
 
+
+// One word of a unique cell's reference mask: its set bits, in ascending order, get consecutive halo slots.
+template <bool GUARD>
+__device__ __forceinline__ int tile_compact_word(unsigned m, int base, int src0, uint16_t *newidx, uint32_t *hrow,
+                                                 int hcap, int run)
+{
+    while (m) {
+        const int bit = __ffs((int)m) - 1;
+        m &= m - 1u;
+        newidx[base + bit] = (uint16_t)run;
+        if (!GUARD || run < hcap) hrow[run] = (uint32_t)(src0 + bit);
+        ++run;
+    }
+    return run;
+}
+
+// Tile-relative fp32 coordinates are a few cell edges at most.  Anything else (NaN, inf, a particle that has left for
+// 1e29) is replaced so that its distance to everything is +inf: a staged candidate becomes a pad entry, the sweeping
+// thread's own particle goes to the opposite end.
+__device__ __forceinline__ float tile_staged_coord(float v) { return fabsf(v) < 1.0e29f ? v : 1.0e30f; }
+__device__ __forceinline__ float tile_own_coord(float v) { return fabsf(v) < 1.0e29f ? v : -1.0e30f; }
 
 template <int D>
 __global__ void __launch_bounds__(MD_BT_THREADS)
@@ -169,7 +205,7 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
     // phase-1 arrays carved out of one pool; phase 2 (emit) reuses the whole pool as the row buffer
     __shared__ __attribute__((aligned(16))) unsigned char pool[MD_BT_POOL];
     float *px = (float *)pool, *py = px + MD_SCAP, *pz = py + MD_SCAP;                    // 43008 bytes
-    unsigned long long *refmask = (unsigned long long *)(pool + 43008);                   // per unique cell: which of its (<= 64) staged particles some row references
+    unsigned *refmask = (unsigned *)(pool + 43008);                                       // per unique cell, two words: which of its (<= 64) staged particles some row references
     int *ucell = (int *)(pool + 51200);                                                   // MD_NCMAX
     int *coff = (int *)(pool + 55296);                                                    // MD_NCMAX + 2
     int *lcell = (int *)(pool + 59408);                                                   // bounding-box cell (local numbering) -> global cell id, -1: not needed / empty
@@ -196,7 +232,10 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
 
     const double4 org = P[tile * MD_TILE]; // tile-local frame: keeps fp32 coordinates small
     double4 pd = P[active ? k : n - 1];
-    const float xi = (float)(pd.x - org.x), yi = (float)(pd.y - org.y), zi = (D == 3) ? (float)(pd.z - org.z) : 0.f;
+    // (a coordinate that is not finite -- a system that has blown up -- is moved out of everybody's reach: it misses
+    // every candidate, as a NaN distance does, and no NaN reaches the sign-bit test of the sweep)
+    const float xi = tile_own_coord((float)(pd.x - org.x)), yi = tile_own_coord((float)(pd.y - org.y)),
+                zi = (D == 3) ? tile_own_coord((float)(pd.z - org.z)) : 0.f;
     int ec[3];
     cell_coords<D>(pd, g, ec);
 #pragma unroll
@@ -210,7 +249,7 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
         sh_misc[4] = sh_misc[5] = sh_misc[6] = 0x7fffffff; // bounding box of the owned cells (extended coordinates)
         sh_misc[7] = sh_misc[8] = sh_misc[9] = -1;
     }
-    for (int i = tid; i < MD_NCMAX; i += MD_BT_THREADS) refmask[i] = 0ull;
+    for (int i = tid; i < 2 * MD_NCMAX; i += MD_BT_THREADS) refmask[i] = 0u;
     for (int i = tid; i < MD_BBMAX; i += MD_BT_THREADS) lcell[i] = -1;
     __syncthreads();
     const int c_first = sh_misc[0], c_last = sh_misc[1];
@@ -330,9 +369,9 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
         int off = i - coff[u];
         if (off < (int)ccnt[u]) {
             double4 p = P[cell_start[ucell[u]] + off];
-            px[i] = (float)(p.x - org.x);
-            py[i] = (float)(p.y - org.y);
-            if constexpr (D == 3) pz[i] = (float)(p.z - org.z);
+            px[i] = tile_staged_coord((float)(p.x - org.x));
+            py[i] = tile_staged_coord((float)(p.y - org.y));
+            if constexpr (D == 3) pz[i] = tile_staged_coord((float)(p.z - org.z));
         } else {
             px[i] = 1.0e30f; // pad entry
             py[i] = 1.0e30f;
@@ -350,17 +389,17 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
     // 3. sweep: mark + per-cell hit masks
     const int wt = tile * (MD_TILE / 64) + (pt >> 6);
     const int n0 = half ? nA : 0, n1 = half ? NNB : nA;
-    unsigned long long hmask[MD_HALF_CELLS];
+    unsigned hmask0[MD_HALF_CELLS], hmask1[MD_HALF_CELLS];
     int qstart[MD_HALF_CELLS];
     int cnt = 0;
     bool too_big = false;
     if (active)
-        cnt = tile_sweep_mark<D>(xi, yi, zi, ctab + myci * NNB, rl2f, self_q, n0, n1, px, py, pz, coff, refmask, hmask,
-                                 qstart, &too_big);
+        cnt = tile_sweep_mark<D>(xi, yi, zi, ctab + myci * NNB, rl2f, self_q, n0, n1, px, py, pz, coff, refmask, hmask0,
+                                 hmask1, qstart, &too_big);
     else {
 #pragma unroll
         for (int ci = 0; ci < MD_HALF_CELLS; ++ci) {
-            hmask[ci] = 0ull;
+            hmask0[ci] = hmask1[ci] = 0u;
             qstart[ci] = 0;
         }
     }
@@ -379,20 +418,22 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
         int c = 0;
         for (int q = 0; q < per; ++q) {
             int u = tid * per + q;
-            if (u < nu) c += __popcll(refmask[u]);
+            if (u < nu) c += __popc(refmask[2 * u]) + __popc(refmask[2 * u + 1]);
         }
         int run = block_excl_scan(c, sh_scan, &H);
+        uint32_t *hrow = halo + (size_t)tile * hcap;
         for (int q = 0; q < per; ++q) {
             int u = tid * per + q;
             if (u >= nu) continue;
-            unsigned long long mk = refmask[u];
             const int base = coff[u], src0 = cell_start[ucell[u]];
-            while (mk) {
-                int bit = __ffsll((long long)mk) - 1;
-                mk &= mk - 1ull;
-                newidx[base + bit] = (uint16_t)run;
-                if (run < hcap) halo[(size_t)tile * hcap + run] = (uint32_t)(src0 + bit);
-                ++run;
+            const unsigned r0 = refmask[2 * u], r1 = refmask[2 * u + 1];
+            if (run + __popc(r0) + __popc(r1) <= hcap) {
+                // (the common case: the tile's halo fits, nothing to test per entry)
+                run = tile_compact_word<false>(r0, base, src0, newidx, hrow, hcap, run);
+                run = tile_compact_word<false>(r1, base + 32, src0 + 32, newidx, hrow, hcap, run);
+            } else {
+                run = tile_compact_word<true>(r0, base, src0, newidx, hrow, hcap, run);
+                run = tile_compact_word<true>(r1, base + 32, src0 + 32, newidx, hrow, hcap, run);
             }
         }
         if (tid == 0) {
@@ -430,7 +471,12 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
     uint16_t *grow = nlist16 + ((size_t)wt * maxn) * 64;
     if (active) {
         const int start = half ? cntA[pt] : 0;
-        tile_sweep_emit_lds(hmask, qstart, newidx, rowbuf + (size_t)pt * MD_ROWPITCH, grow, lane, maxn, start, rs);
+        uint16_t *row = rowbuf + (size_t)pt * MD_ROWPITCH;
+        // decided once per thread: a row that ends within the buffer's pitch (nearly all) is walked without tests
+        if (start + cnt <= MD_ROWPITCH)
+            tile_sweep_emit_lds<false>(hmask0, hmask1, qstart, newidx, row, grow, lane, maxn, start, rs);
+        else
+            tile_sweep_emit_lds<true>(hmask0, hmask1, qstart, newidx, row, grow, lane, maxn, start, rs);
     }
     __syncthreads();
     {

@@ -560,6 +560,7 @@ __global__ void __launch_bounds__(MD_BLOCK)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_src) return;
+    if (i == 0) nimg[n_src] = 0; // the extra item of the exclusive scan that follows: its output is the total
     if (alive && !alive[i]) {
         nimg[i] = 0;
         return;
@@ -605,9 +606,15 @@ __global__ void __launch_bounds__(MD_BLOCK)
 template <int D>
 __global__ void __launch_bounds__(MD_BLOCK)
     k_emit(int n_src, int n_own_src, DevState s, BoxGrid g, const int32_t *__restrict__ alive,
-           const int32_t *__restrict__ img_off, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals)
+           const int32_t *__restrict__ img_off, uint64_t *__restrict__ keys, uint32_t *__restrict__ vals,
+           int32_t *__restrict__ cell_start, int32_t *__restrict__ cell_end, int ncell1)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
+    // the cell ranges of the coming build start out empty (k_gather writes the non-empty ones after the sort)
+    for (int j = i; j < ncell1; j += gridDim.x * blockDim.x) {
+        cell_start[j] = 0;
+        cell_end[j] = 0;
+    }
     if (i >= n_src) return;
     if (alive && !alive[i]) return;
     bool is_xh = i >= n_own_src;
@@ -644,16 +651,31 @@ __device__ __forceinline__ double4 shifted(double4 p, uint32_t code, const BoxGr
     return p;
 }
 
+// what a list build starts from: no violation, no displacement, no overflow recorded
+__device__ __forceinline__ void reset_flags(Scalars *sc)
+{
+    sc->first_viol = MD_NO_VIOLATION;
+    sc->max_disp2_bits = 0ull;
+    sc->overflow = 0;
+    sc->hmax = 0;
+    sc->halo_overflow = 0;
+    sc->dbg_rmax = 0;
+    sc->dbg_smax = 0;
+    sc->d1max2_bits = 0ull;
+}
+
 // stage 3 (after the radix sort): move every array into the new order, create the ghost
 // copies' translated coordinates, find the cell ranges.
 template <int D>
 __global__ void __launch_bounds__(MD_BLOCK)
     k_gather(int n, int next, DevState so, DevState sn, BoxGrid g, const uint64_t *__restrict__ keys,
              const uint32_t *__restrict__ vals, int32_t *__restrict__ newslot, int32_t *__restrict__ gsrc,
-             uint32_t *__restrict__ gcode, int32_t *__restrict__ cell_start, int32_t *__restrict__ cell_end)
+             uint32_t *__restrict__ gcode, int32_t *__restrict__ cell_start, int32_t *__restrict__ cell_end,
+             Scalars *sc)
 {
     int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= next) return;
+    if (k == 0) reset_flags(sc); // for the row build that follows
     uint64_t key = keys[k];
     uint32_t val = vals[k];
     int src = (int)(val & MD_VAL_SRC_MASK);

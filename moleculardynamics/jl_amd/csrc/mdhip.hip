@@ -370,17 +370,7 @@ __global__ void k_init_state(int n, int64_t cap, DevState s, int dim)
         }
 }
 
-__global__ void k_reset_flags(Scalars *sc)
-{
-    sc->first_viol = MD_NO_VIOLATION;
-    sc->max_disp2_bits = 0ull;
-    sc->overflow = 0;
-    sc->hmax = 0;
-    sc->halo_overflow = 0;
-    sc->dbg_rmax = 0;
-    sc->dbg_smax = 0;
-    sc->d1max2_bits = 0ull;
-}
+__global__ void k_reset_flags(Scalars *sc) { reset_flags(sc); }
 
 __global__ void k_reset_disp0(Scalars *sc) { sc->max_disp2_bits = 0ull; }
 __global__ void k_clear_halo_overflow(Scalars *sc) { sc->halo_overflow = 0; }
@@ -651,8 +641,8 @@ void rebuild_t(md_ctx *c)
     DevState so = c->dev(c->cur);
     BoxGrid g = c->grid;
 
+    // (k_wrap_count also writes the scan's extra item, nimg[n_src] = 0)
     k_wrap_count<D><<<nbs, MD_BLOCK, 0, st>>>(n_src, n_own_src, so, g, alive, c->nimg.p);
-    HIPCHK(hipMemsetAsync(c->nimg.p + n_src, 0, sizeof(int32_t), st));
     // exclusive scan over n_src+1 items -> img_off[n_src] = total number of sort entries
     size_t tmp_bytes = 0;
     HIPCHK(rocprim::exclusive_scan(nullptr, tmp_bytes, c->nimg.p, c->img_off.p, (int32_t)0, (size_t)n_src + 1,
@@ -671,7 +661,9 @@ void rebuild_t(md_ctx *c)
     so = c->dev(c->cur);
     DevState sn = c->dev(c->cur ^ 1);
 
-    k_emit<D><<<nbs, MD_BLOCK, 0, st>>>(n_src, n_own_src, so, g, alive, c->img_off.p, c->keys_in.p, c->vals_in.p);
+    // (k_emit also zeroes the cell ranges that k_gather fills in after the sort: nothing reads them in between)
+    k_emit<D><<<nbs, MD_BLOCK, 0, st>>>(n_src, n_own_src, so, g, alive, c->img_off.p, c->keys_in.p, c->vals_in.p,
+                                        c->cell_start.p, c->cell_end.p, c->ncell_ext + 1);
     // Only the (ghost bit, cell) digits are sorted -- three radix passes instead of five.  The sort is stable, so the
     // particles of a cell keep the order they were emitted in (source-slot order), which is as deterministic as the
     // id order the low digits would give.
@@ -682,11 +674,10 @@ void rebuild_t(md_ctx *c)
     c->sort_tmp.ensure(tmp_bytes);
     HIPCHK(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, c->keys_in.p, c->keys_out.p, c->vals_in.p,
                                      c->vals_out.p, (size_t)next, begin_bit, end_bit, st));
-    HIPCHK(hipMemsetAsync(c->cell_start.p, 0, sizeof(int32_t) * (c->ncell_ext + 1), st));
-    HIPCHK(hipMemsetAsync(c->cell_end.p, 0, sizeof(int32_t) * (c->ncell_ext + 1), st));
+    // (k_gather also resets the build's flags for the first attempt below)
     k_gather<D><<<nblocks(next), MD_BLOCK, 0, st>>>(n, (int)next, so, sn, g, c->keys_out.p, c->vals_out.p,
                                                      c->newslot.p, c->gsrc.p, c->gcode.p, c->cell_start.p,
-                                                     c->cell_end.p);
+                                                     c->cell_end.p, c->scal.p);
     if (nghost > 0)
         k_ghost_owner<<<nblocks(nghost), MD_BLOCK, 0, st>>>(nghost, c->gsrc.p, c->newslot.p, c->gowner.p);
     c->cur ^= 1;
@@ -725,7 +716,7 @@ void rebuild_t(md_ctx *c)
         // fp32 sweep radius with a safety margin over fp32 rounding of tile-relative coordinates
         float rl2f = (float)(rl2 * (1.0 + 1.0e-4));
         for (int attempt = 0; attempt < 8; ++attempt) {
-            k_reset_flags<<<1, 1, 0, st>>>(c->scal.p);
+            if (attempt > 0 || next == 0) k_reset_flags<<<1, 1, 0, st>>>(c->scal.p);
             k_build_tile<D><<<c->nblk, MD_BT_THREADS, 0, st>>>(n, sn, g, rl2f, c->cell_start.p, c->cell_end.p,
                                                                c->nlist16.p, c->maxn, c->nneigh.p, c->nmax_tile.p,
                                                                c->halo.p, c->hcap, c->halo_count.p, c->scal.p,
@@ -2976,6 +2967,7 @@ int md_get_stats(md_ctx *ctx, md_stats *out)
     out->prune_ms = ctx->prof_prune_ms_acc;
     out->rebuilds_timed = ctx->prof_rebuild_acc;
     out->rebuild_ms = ctx->prof_rebuild_ms_acc;
+    out->fused_build = (ctx->list_valid && ctx->use_tiles && !ctx->have_nlist32) ? 1 : 0;
     API_END
 }
 
