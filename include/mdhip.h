@@ -224,6 +224,48 @@ int md_sq_rho(md_ctx *ctx, double *rho);
 int md_sq_read(md_ctx *ctx, int64_t *nstatic, double *s2, int64_t *nsamples, double *corr);
 int md_sq_reset(md_ctx *ctx);
 
+/* Pressure tensor and its Green-Kubo correlations, sampled on the device (new relative to the reference, whose users
+ * dump frames and recompute every pair force on the host).  One sample evaluates, for the state md_download would return
+ * at that moment (unit mass),
+ *   K_ab = sum over particles of v_a*v_b                                   (the product rounded, then added)
+ *   W_ab = sum over accepted pairs of (f/r)*del_a*del_b,   del = x_j(+periodic translation) - x_i
+ * where the accepted pairs are the force kernels': d2 = (del0*del0 + del1*del1) + del2*del2 (no fma) must satisfy
+ * d2 <= list_cutoff^2, the potential's own cutoff applies inside the pair evaluation, and f/r is the value the force
+ * kernels' generic path uses.  Components, in this order: xx, yy, zz, xy, xz, yz in 3-D (nc = 6); xx, yy, xy in 2-D
+ * (nc = 3).  The trace of W_ab is the virial W of md_compute_forces; the pressure tensor is (K_ab + W_ab)/V.
+ * Summation: each particle walks its outer neighbour row in row order with t = (f/r)*del_a rounded and
+ * W_ab = fma(t, del_b, W_ab) in fp64; then the 64 lanes of a wave (shuffle tree), the 4 waves of a 256-particle block in
+ * order, and the blocks in block order (one block, 1024 threads: thread t adds blocks t, t+1024, ..., then the same
+ * wave/block tree) -- no floating-point atomics.  Every pair is seen from both ends; the total is multiplied by 0.5
+ * (exact).  The tensor therefore depends on the handle's row order: it is reproducible for the same handle history but,
+ * unlike the md_dyn_ and md_sq_ samplers' sums, it is not a function of the frame alone (two handles holding the same
+ * frame agree to rounding, ~1e-15 of sum |f/r| d2).  Across a periodic face the two ends of a pair see different
+ * roundings of the same separation; that residual applies here exactly as it does to the forces.
+ *
+ * Correlations: md_stress_setup allocates a ring of nlags channel vectors.  Sample number m (0-based since setup or
+ * the last reset) forms sig_c = kin_c + vir_c (one rounded add per component) and the channels
+ *   3-D: ch0 = sig_xy, ch1 = sig_xz, ch2 = sig_yz, ch3 = (sig_xx - sig_yy)*0.5, ch4 = (sig_yy - sig_zz)*0.5,
+ *        ch5 = ((sig_xx + sig_yy) + sig_zz)/3
+ *   2-D: ch0 = sig_xy, ch1 = (sig_xx - sig_yy)*0.5, ch2 = (sig_xx + sig_yy)/2
+ * stores them in ring[m % nlags], and for k = 0 .. min(m, nlags-1) adds corr[k][ch] += ch(m)*ch(m-k) (the product
+ * rounded, then added; no fma; samples in stream order) -- ncorr[k] counts these.  The running sums sum_kin[c] += kin_c,
+ * sum_vir[c] += vir_c and nsamples += 1 go with every sample.  The lag unit is the caller's sampling interval.
+ *
+ * md_stress_setup: 0 <= nlags <= 65536 (0 = tensor and means only); everything zeroed; calling it again starts over.
+ * md_stress_sample does not wait and changes nothing the handle computes afterwards: it writes only the sampler's own
+ * buffers; if the neighbour list is not valid (first call after md_upload) it builds it exactly as md_compute_forces
+ * would, which is the list the next md_run or md_compute_forces would have built itself.  It dispatches on the potential
+ * in force at that moment (md_set_potential after the setup is allowed).  md_stress_tensor waits and returns the last
+ * sampled frame, kin[nc] and vir[nc].  md_stress_read waits and returns nsamples, sum_kin[nc], sum_vir[nc], ncorr[nlags]
+ * and corr[k*nc + ch] (any pointer may be NULL).  md_stress_reset zeroes the sums, corr and the counts and empties the
+ * ring; it keeps the setup.  Refused: a slab-decomposition handle, a user potential (MD_POT_CUSTOM), nlags out of range,
+ * any call before md_stress_setup, md_stress_tensor before the first sample.                                       */
+int md_stress_setup(md_ctx *ctx, int nlags);
+int md_stress_sample(md_ctx *ctx);
+int md_stress_tensor(md_ctx *ctx, double *kin, double *vir);
+int md_stress_read(md_ctx *ctx, int64_t *nsamples, double *sum_kin, double *sum_vir, int64_t *ncorr, double *corr);
+int md_stress_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

@@ -8,7 +8,8 @@ from .temperature_ramps import LinearRamp, ExponentialRamp, initial_temperature_
 from .initialization import (initialize_state, initialize_velocities, lattice_positions, to_unitcell,
                              SimulationState, EnergyAndForces)
 from .simulation import run_simulation
-from .analysis import RadialDistribution, compute_rdf, SelfDynamics, StructureFactor, compute_sq, select_wave_vectors
+from .analysis import (RadialDistribution, compute_rdf, SelfDynamics, StructureFactor, compute_sq, select_wave_vectors,
+                       StressTensor, compute_stress)
 from .minimize import fire_minimize, minimize
 from .device import MDDevice
 from ._lib import MdhipError
@@ -19,4 +20,5 @@ __all__ = [
     "initialize_velocities", "Potential", "evaluate", "MDDevice", "MdhipError", "lattice_positions",
     "fire_minimize", "minimize", "LennardJonesShifted", "LennardJonesForceShifted", "LennardJonesXPLOR",
     "RadialDistribution", "compute_rdf", "SelfDynamics", "StructureFactor", "compute_sq", "select_wave_vectors",
+    "StressTensor", "compute_stress",
 ]

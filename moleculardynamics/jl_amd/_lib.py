@@ -27,6 +27,7 @@ EXPORTS = [
     "md_rdf_setup", "md_rdf_sample", "md_rdf_read", "md_rdf_reset",
     "md_dyn_setup", "md_dyn_origin", "md_dyn_sample", "md_dyn_read", "md_dyn_reset",
     "md_sq_setup", "md_sq_sample", "md_sq_rho", "md_sq_read", "md_sq_reset",
+    "md_stress_setup", "md_stress_sample", "md_stress_tensor", "md_stress_read", "md_stress_reset",
 ]
 
 
@@ -163,6 +164,16 @@ def load():
     L.md_sq_read.restype = C.c_int
     L.md_sq_reset.argtypes = [vp]
     L.md_sq_reset.restype = C.c_int
+    L.md_stress_setup.argtypes = [vp, C.c_int]
+    L.md_stress_setup.restype = C.c_int
+    L.md_stress_sample.argtypes = [vp]
+    L.md_stress_sample.restype = C.c_int
+    L.md_stress_tensor.argtypes = [vp, dp, dp]
+    L.md_stress_tensor.restype = C.c_int
+    L.md_stress_read.argtypes = [vp, i64p, dp, dp, i64p, dp]
+    L.md_stress_read.restype = C.c_int
+    L.md_stress_reset.argtypes = [vp]
+    L.md_stress_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -1,5 +1,6 @@
 """Structure and dynamics of a simulated configuration, sampled on the device: the radial distribution function g(r),
-the self dynamics (MSD, F_s(q, t), van Hove) and the collective side (density modes, S(q), coherent F(q, t)).
+the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes, S(q), coherent F(q, t)) and the stress
+(pressure tensor, stress autocorrelations, Green-Kubo viscosity).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -568,3 +569,188 @@ def compute_sq(state, params, q_max, dq=None, max_per_bin=16, seed=0):
     dev.sq_sample(True)
     _sq_collect(dev, sq, dev.n, params.dt)
     return sq
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Stress: the pressure tensor P_ab = (K_ab + W_ab) / V, K_ab = sum v_a v_b (unit mass), W_ab = sum over pairs of
+# (f/r) del_a del_b, and the Green-Kubo correlations of its shear components, sampled on the device (md_stress_*) from the
+# positions, velocities and neighbour rows the handle already holds.
+
+def _tensor(comp, d):
+    """d x d symmetric matrix of a component vector (xx, yy, zz, xy, xz, yz in 3-D; xx, yy, xy in 2-D)."""
+    c = np.asarray(comp, dtype=np.float64)
+    t = np.zeros((d, d))
+    if d == 3:
+        t[0, 0], t[1, 1], t[2, 2] = c[0], c[1], c[2]
+        t[0, 1] = t[1, 0] = c[3]
+        t[0, 2] = t[2, 0] = c[4]
+        t[1, 2] = t[2, 1] = c[5]
+    else:
+        t[0, 0], t[1, 1] = c[0], c[1]
+        t[0, 1] = t[1, 0] = c[2]
+    return t
+
+
+class StressTensor:
+    """The pressure tensor and, with nlags > 0, the stress autocorrelation functions and the running Green-Kubo viscosity,
+    accumulated on the device until reset().
+
+    Passed to run_simulation(..., stress=...), it takes a sample at every step that is a multiple of `every` (0 included);
+    lag k of the correlations is the time k * every * dt.  Each run_simulation call restarts the step counter and the
+    ring of past samples; the sums accumulate here across calls.
+
+    Channels: 3-D  sig_xy, sig_xz, sig_yz, (sig_xx - sig_yy)/2, (sig_yy - sig_zz)/2, tr sig / 3;
+    2-D  sig_xy, (sig_xx - sig_yy)/2, tr sig / 2, with sig = K + W (extensive: the pressure tensor times V).
+
+    Fields: nsamples, sum_kin, sum_vir (component vectors summed over the samples), corr (nlags, nc: sum of ch(m) ch(m - k)),
+    ncorr (products per lag)."""
+
+    def __init__(self, every, nlags=0):
+        if int(every) != every or int(every) < 1:
+            raise ValueError("every must be a positive integer")
+        if int(nlags) != nlags or not 0 <= int(nlags) <= 65536:
+            raise ValueError("nlags must be in 0..65536")
+        self.every, self.nlags = int(every), int(nlags)
+        self.dimension = 3
+        self.n_particles = 0
+        self.volume = 0.0
+        self.dt = 1.0
+        self.nsamples = 0
+        self.sum_kin = self.sum_vir = self.corr = None
+        self.ncorr = np.zeros(self.nlags, dtype=np.int64)
+
+    def reset(self):
+        self.nsamples = 0
+        self.sum_kin = self.sum_vir = self.corr = None
+        self.ncorr = np.zeros(self.nlags, dtype=np.int64)
+
+    def schedule(self, total_steps):
+        """The steps of one run of `total_steps` steps at which a sample is taken: 0, every, 2 every, ... < total_steps."""
+        return list(range(0, int(total_steps), self.every))
+
+    def _accumulate(self, nsamples, sum_kin, sum_vir, ncorr, corr, n_particles, unitcell, dt):
+        u = np.asarray(unitcell, dtype=np.float64)
+        d = u.shape[0]
+        nc = 6 if d == 3 else 3
+        sum_kin, sum_vir = np.asarray(sum_kin, dtype=np.float64), np.asarray(sum_vir, dtype=np.float64)
+        corr = np.asarray(corr, dtype=np.float64).reshape(self.nlags, nc)
+        if sum_kin.shape != (nc,) or sum_vir.shape != (nc,):
+            raise ValueError(f"expected {nc} tensor components")
+        if self.sum_kin is None:
+            self.sum_kin, self.sum_vir, self.corr = np.zeros(nc), np.zeros(nc), np.zeros((self.nlags, nc))
+        elif self.sum_kin.shape != (nc,):
+            raise ValueError("the dimension differs from the one already accumulated; reset() first")
+        self.nsamples += int(nsamples)
+        self.sum_kin += sum_kin
+        self.sum_vir += sum_vir
+        self.corr += corr
+        self.ncorr += np.asarray(ncorr, dtype=np.int64).reshape(self.nlags)
+        self.dimension, self.n_particles = d, int(n_particles)
+        self.volume = abs(float(np.linalg.det(u)))
+        self.dt = float(dt)
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    def _need(self):
+        if self.nsamples == 0 or self.sum_kin is None:
+            raise ValueError("no sample yet")
+
+    def kinetic(self):
+        """Mean kinetic tensor <sum v_a v_b>, d x d."""
+        self._need()
+        return _tensor(self.sum_kin / self.nsamples, self.dimension)
+
+    def virial(self):
+        """Mean virial tensor <sum (f/r) del_a del_b>, d x d."""
+        self._need()
+        return _tensor(self.sum_vir / self.nsamples, self.dimension)
+
+    def pressure_tensor(self):
+        """(K + W) / V, d x d."""
+        return (self.kinetic() + self.virial()) / self.volume
+
+    def pressure(self):
+        """tr P / d.  The isotropic tail correction of a truncated potential (pot.pressure_lrc(N, V)) is NOT included: it
+        is the caller's to add, as the thermo line of run_simulation does."""
+        return float(np.trace(self.pressure_tensor())) / self.dimension
+
+    def temperature(self):
+        """tr K / nf with nf = d (N - 1), the thermo line's temperature."""
+        return float(np.trace(self.kinetic())) / (self.dimension * (self.n_particles - 1.0))
+
+    def shear_channels(self):
+        """Indices of the channels averaged into C_shear: the off-diagonal components and the normal-stress differences."""
+        return [0, 1, 2, 3, 4] if self.dimension == 3 else [0, 1]
+
+    def acf(self):
+        """(t, C, C_shear): lag times k every dt, the per-channel correlations corr / ncorr (nlags, nc) with <p-channel>^2
+        subtracted from the last (pressure) channel, and the average of the shear channels.  nan where a lag has no
+        product.  Units of sig = P V."""
+        self._need()
+        if self.nlags == 0:
+            raise ValueError("no correlations were requested (nlags = 0)")
+        t = np.arange(self.nlags, dtype=np.float64) * (self.every * self.dt)
+        nn = self.ncorr.astype(np.float64)[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c = np.where(nn > 0, self.corr / nn, np.nan)
+        d = self.dimension
+        pbar = (np.sum(self.sum_kin[:d]) + np.sum(self.sum_vir[:d])) / (d * self.nsamples)
+        c[:, -1] = c[:, -1] - pbar * pbar
+        return t, c, c[:, self.shear_channels()].mean(axis=1)
+
+    def viscosity(self, kT=None):
+        """(t, eta): the running Green-Kubo integral eta(t) = 1 / (V kT) int_0^t C_shear, trapezoid rule on the lag grid;
+        kT defaults to temperature()."""
+        t, _, cs = self.acf()
+        kT = self.temperature() if kT is None else float(kT)
+        eta = np.zeros(self.nlags)
+        if self.nlags > 1:
+            eta[1:] = np.cumsum(0.5 * (cs[1:] + cs[:-1]) * np.diff(t))
+        return t, eta / (self.volume * kT)
+
+    def write(self, path):
+        """# component kinetic virial pressure, one row per tensor component (means over the samples), then nsamples."""
+        d = self.dimension
+        names = ["xx", "yy", "zz", "xy", "xz", "yz"] if d == 3 else ["xx", "yy", "xy"]
+        k, w = self.sum_kin / self.nsamples, self.sum_vir / self.nsamples
+        with open(path, "w") as io:
+            io.write("# component kinetic virial pressure\n")
+            for c, name in enumerate(names):
+                io.write("%s %.10e %.10e %.10e\n" % (name, k[c], w[c], (k[c] + w[c]) / self.volume))
+            io.write("# nsamples %d\n" % self.nsamples)
+
+    def write_acf(self, path, kT=None):
+        """# lag time C_shear C_ch... C_pp eta_running ncorr, one row per lag that has a product."""
+        t, c, cs = self.acf()
+        _, eta = self.viscosity(kT)
+        nch = c.shape[1]
+        with open(path, "w") as io:
+            io.write("# lag time C_shear" + "".join(" C_ch%d" % i for i in range(nch - 1)) + " C_pp eta_running ncorr\n")
+            for k in range(self.nlags):
+                if self.ncorr[k] > 0:
+                    io.write(("%d %.6e %.6e" + " %.6e" * nch + " %.6e %d\n")
+                             % ((k, t[k], cs[k]) + tuple(c[k]) + (eta[k], int(self.ncorr[k]))))
+
+
+def _stress_start(dev, stress):
+    dev.stress_setup(stress.nlags)
+
+
+def _stress_collect(dev, stress, n_particles, unitcell, dt):
+    ns, sk, sv, ncorr, corr = dev.stress_read()
+    stress._accumulate(ns, sk, sv, ncorr, corr, n_particles, unitcell, dt)
+
+
+def compute_stress(state, params):
+    """One sample of the stress of `state` (positions and velocities), taken on its device handle with params.potential;
+    returns (K, W) as d x d arrays: K_ab = sum v_a v_b, W_ab = sum over pairs of (f/r) del_a del_b.  The pressure tensor is
+    (K + W) / V."""
+    dev = state.system.device
+    spec = params.potential.device_spec()
+    if spec[0] != "builtin":
+        raise ValueError("compute_stress needs a built-in potential (user potentials are not supported by the sampler)")
+    dev.set_potential(spec[1], spec[2])
+    dev.upload(x=state.system.positions, v=state.velocities, images=state.images, diameters=state.diameters)
+    dev.stress_setup(0)
+    dev.stress_sample()
+    kin, vir = dev.stress_tensor()
+    return _tensor(kin, dev.dim), _tensor(vir, dev.dim)

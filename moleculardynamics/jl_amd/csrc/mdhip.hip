@@ -13,6 +13,7 @@
 #include "md_rdf.hpp"
 #include "md_dyn.hpp"
 #include "md_sq.hpp"
+#include "md_stress.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -322,6 +323,16 @@ struct md_ctx {
         DBuf<double> cx, fr, part, rho, s2, corr, org; // frame; f per axis; (vector, comp, block); 2 nvec; nvec; nrows x nvec; nslots x nvec x 2
         DBuf<int32_t> ci;
     } sq;
+
+    // pressure tensor (md_stress_*): block partials, the last frame's tensor, the running sums, the channel ring and the
+    // lag products
+    struct Stress {
+        bool on = false;
+        bool sampled = false;             // last holds a frame
+        int nlags = 0;
+        int64_t nsamples = 0;             // since setup / reset: the next sample's number m
+        DBuf<double> part, last, sums, ring, corr; // 2 nc x nblk; 2 nc; 2 nc; nlags x nc; nlags x nc
+    } stress;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1326,6 +1337,76 @@ int fail(md_ctx *c, const char *what)
     else
         g_create_error = what;
     return 1;
+}
+
+} // namespace
+
+// ---- pressure tensor sampler (md_stress.hpp): launches ----------------------------------------------------------
+namespace {
+
+template <int D, int POT, bool UNIFORM>
+void launch_stress_tpu(md_ctx *c)
+{
+    int n = (int)c->n;
+    int nb = c->nblk;
+    DevState s = c->dev(c->cur);
+    double *part = c->stress.part.p;
+    if (c->use_tiles) {
+        static int attr_dev_mask = 0; // the attribute is per device: one bit per device id
+        auto kfn = k_stress_tile<D, POT, UNIFORM>;
+        if (!(attr_dev_mask & (1 << (c->device & 31)))) {
+            HIPCHK(hipFuncSetAttribute((const void *)kfn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)(160 * 1024 - 2048)));
+            attr_dev_mask |= 1 << (c->device & 31);
+        }
+        if (c->tile_rs != (UNIFORM ? 24 : 32)) throw HipError("internal: stress sampler and tile rows disagree on the record stride");
+        kfn<<<nb, MD_TILE, c->tile_lds, c->stream>>>(n, s, c->pp, c->nlist16.p, c->maxn, c->nmax_tile.p, c->halo.p, c->hcap,
+                                                     c->halo_count.p, part, nb);
+    } else {
+        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
+        k_stress<D, POT, UNIFORM><<<nb, MD_BLOCK, 0, c->stream>>>(n, s, c->pp, c->nlist.p, c->maxn, c->nmax_tile.p, part, nb);
+    }
+}
+
+template <int D>
+void launch_stress_d(md_ctx *c)
+{
+    bool u = c->uniform_sigma;
+    switch (c->pot_kind) {
+    case POT_LJ:
+        if (u)
+            launch_stress_tpu<D, POT_LJ, true>(c);
+        else
+            launch_stress_tpu<D, POT_LJ, false>(c);
+        break;
+    case POT_PSEUDOHS:
+        if (u)
+            launch_stress_tpu<D, POT_PSEUDOHS, true>(c);
+        else
+            launch_stress_tpu<D, POT_PSEUDOHS, false>(c);
+        break;
+    case POT_POLYDISPERSE:
+        launch_stress_tpu<D, POT_POLYDISPERSE, false>(c);
+        break;
+    case POT_LJ_MOD:
+        launch_stress_tpu<D, POT_LJ_MOD, false>(c);
+        break;
+    default:
+        throw HipError("md_stress_sample: not available with a user potential (MD_POT_CUSTOM)");
+    }
+}
+
+inline int stress_nc(const md_ctx *c) { return c->dim == 3 ? 6 : 3; }
+
+void stress_zero(md_ctx *c)
+{
+    md_ctx::Stress &S = c->stress;
+    const int nc = stress_nc(c);
+    HIPCHK(hipMemsetAsync(S.sums.p, 0, sizeof(double) * 2 * nc, c->stream));
+    HIPCHK(hipMemsetAsync(S.ring.p, 0, sizeof(double) * std::max(S.nlags, 1) * nc, c->stream));
+    HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * std::max(S.nlags, 1) * nc, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    S.nsamples = 0;
 }
 
 } // namespace
@@ -2373,6 +2454,112 @@ int md_sq_reset(md_ctx *ctx)
     HIPCHK(hipStreamSynchronize(st));
     S.nstatic = 0;
     std::fill(S.nsamples.begin(), S.nsamples.end(), (int64_t)0);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pressure tensor and its lag correlations (md_stress.hpp): a sample walks the OUTER rows -- valid for the current
+// positions whenever the list is, as md_compute_forces relies on -- reads positions and velocities and writes only the
+// sampler's own buffers, so the step loop, the list and the cell order are exactly what they would have been without it.
+static md_ctx::Stress &stress_of(md_ctx *ctx, const char *who)
+{
+    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
+    if (!ctx->stress.on) throw HipError(std::string(who) + ": no setup (call md_stress_setup first)");
+    return ctx->stress;
+}
+
+int md_stress_setup(md_ctx *ctx, int nlags)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_stress_setup: not available on a slab-decomposition handle");
+    if (ctx->pot_kind == POT_CUSTOM) throw HipError("md_stress_setup: not available with a user potential (MD_POT_CUSTOM)");
+    if (nlags < 0 || nlags > MD_STRESS_MAX_LAGS) {
+        char b[160];
+        snprintf(b, sizeof b, "md_stress_setup: nlags must be in 0..%d, got %d", MD_STRESS_MAX_LAGS, nlags);
+        throw HipError(b);
+    }
+    md_ctx::Stress &S = ctx->stress;
+    S.on = false;
+    const int nc = stress_nc(ctx);
+    S.part.alloc((size_t)2 * nc * std::max(nblocks(ctx->n), 1));
+    S.last.alloc(2 * nc);
+    S.sums.alloc(2 * nc);
+    S.ring.alloc((size_t)std::max(nlags, 1) * nc);
+    S.corr.alloc((size_t)std::max(nlags, 1) * nc);
+    S.nlags = nlags;
+    S.sampled = false;
+    HIPCHK(hipMemsetAsync(S.last.p, 0, sizeof(double) * 2 * nc, ctx->stream));
+    stress_zero(ctx);
+    S.on = true;
+    API_END
+}
+
+int md_stress_sample(md_ctx *ctx)
+{
+    API_BEGIN
+    require_state(ctx, "md_stress_sample");
+    md_ctx::Stress &S = stress_of(ctx, "md_stress_sample");
+    if (ctx->pot_kind == POT_CUSTOM) throw HipError("md_stress_sample: not available with a user potential (MD_POT_CUSTOM)");
+    if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
+    const int nc = stress_nc(ctx);
+    S.part.ensure((size_t)2 * nc * std::max(ctx->nblk, 1));
+    if (ctx->dim == 3) {
+        launch_stress_d<3>(ctx);
+        k_stress_finish<3><<<1, 1024, 0, ctx->stream>>>(ctx->nblk, S.part.p, (long long)S.nsamples, S.nlags, S.last.p,
+                                                        S.sums.p, S.ring.p, S.corr.p);
+    } else {
+        launch_stress_d<2>(ctx);
+        k_stress_finish<2><<<1, 1024, 0, ctx->stream>>>(ctx->nblk, S.part.p, (long long)S.nsamples, S.nlags, S.last.p,
+                                                        S.sums.p, S.ring.p, S.corr.p);
+    }
+    HIPCHK(hipGetLastError());
+    ++S.nsamples;
+    S.sampled = true;
+    API_END
+}
+
+int md_stress_tensor(md_ctx *ctx, double *kin, double *vir)
+{
+    API_BEGIN
+    md_ctx::Stress &S = stress_of(ctx, "md_stress_tensor");
+    if (!S.sampled) throw HipError("md_stress_tensor: no frame sampled yet (call md_stress_sample first)");
+    const int nc = stress_nc(ctx);
+    double h[12];
+    HIPCHK(hipMemcpyAsync(h, S.last.p, sizeof(double) * 2 * nc, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    for (int c = 0; c < nc; ++c) {
+        if (kin) kin[c] = h[c];
+        if (vir) vir[c] = h[nc + c];
+    }
+    API_END
+}
+
+int md_stress_read(md_ctx *ctx, int64_t *nsamples, double *sum_kin, double *sum_vir, int64_t *ncorr, double *corr)
+{
+    API_BEGIN
+    md_ctx::Stress &S = stress_of(ctx, "md_stress_read");
+    const int nc = stress_nc(ctx);
+    double h[12];
+    HIPCHK(hipMemcpyAsync(h, S.sums.p, sizeof(double) * 2 * nc, hipMemcpyDeviceToHost, ctx->stream));
+    if (corr && S.nlags > 0)
+        HIPCHK(hipMemcpyAsync(corr, S.corr.p, sizeof(double) * (size_t)S.nlags * nc, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (nsamples) *nsamples = S.nsamples;
+    for (int c = 0; c < nc; ++c) {
+        if (sum_kin) sum_kin[c] = h[c];
+        if (sum_vir) sum_vir[c] = h[nc + c];
+    }
+    // lag k has one product per sample m >= k
+    if (ncorr)
+        for (int k = 0; k < S.nlags; ++k) ncorr[k] = std::max<int64_t>(S.nsamples - k, 0);
+    API_END
+}
+
+int md_stress_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    stress_of(ctx, "md_stress_reset");
+    stress_zero(ctx);
     API_END
 }
 

@@ -265,6 +265,41 @@ class MDDevice:
     def sq_reset(self):
         self._chk(self._L.md_sq_reset(self._h))
 
+    # -- pressure tensor and its lag correlations -----------------------------------------
+    def stress_setup(self, nlags=0):
+        """Allocate the device pressure-tensor sampler (md_stress_setup): running sums of the kinetic and virial tensors
+        and, with nlags > 0, a ring of nlags channel vectors and the lag products corr[k][ch], all zeroed."""
+        self._chk(self._L.md_stress_setup(self._h, int(nlags)))
+        self._stress_nlags = int(nlags)
+
+    def stress_sample(self):
+        """Add one sample of the current state (does not wait, changes nothing the handle computes afterwards)."""
+        self._chk(self._L.md_stress_sample(self._h))
+
+    def stress_tensor(self):
+        """(kin, vir) of the last sampled frame, float64[nc] each: K_ab = sum v_a v_b and W_ab = sum (f/r) del_a del_b, in the
+        order xx, yy, zz, xy, xz, yz (3-D) or xx, yy, xy (2-D); waits."""
+        nc = 6 if self.dim == 3 else 3
+        kin, vir = np.zeros(nc), np.zeros(nc)
+        self._chk(self._L.md_stress_tensor(self._h, _dp(kin), _dp(vir)))
+        return kin, vir
+
+    def stress_read(self):
+        """(nsamples, sum_kin float64[nc], sum_vir float64[nc], ncorr int64[nlags], corr float64[nlags, nc]), summed since
+        setup / reset; waits."""
+        nc = 6 if self.dim == 3 else 3
+        nl = getattr(self, "_stress_nlags", 0)
+        ns = C.c_int64()
+        sk, sv = np.zeros(nc), np.zeros(nc)
+        ncorr = np.zeros(max(nl, 1), dtype=np.int64)
+        corr = np.zeros((max(nl, 1), nc))
+        self._chk(self._L.md_stress_read(self._h, C.byref(ns), _dp(sk), _dp(sv),
+                                         ncorr.ctypes.data_as(C.POINTER(C.c_int64)), _dp(corr)))
+        return ns.value, sk, sv, ncorr[:nl], corr[:nl]
+
+    def stress_reset(self):
+        self._chk(self._L.md_stress_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

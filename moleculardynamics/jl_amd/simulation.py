@@ -35,7 +35,7 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, sq=None):
+                   dynamics=None, sq=None, stress=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -51,7 +51,13 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     sq: a StructureFactor (analysis.py) to sample S(q) into, on the device, at every sq.every-th output step and, with
     dynamic=True, the coherent F(q, t) at the steps of its schedule (SelfDynamics' rules: the stops are added to the
     loop's output steps, the schedule restarts at step 0 in every call).  Written to pathname/sq.txt and, if dynamic,
-    pathname/fqt.txt.  Nothing else the run produces changes."""
+    pathname/fqt.txt.  Nothing else the run produces changes.
+
+    stress: a StressTensor (analysis.py) to sample the pressure tensor and, with nlags > 0, its lag correlations into, on
+    the device, at every step that is a multiple of stress.every (the stops are added to the loop's output steps; the step
+    counter and the ring of past samples restart in every call, the sums accumulate in the object).  Written to
+    pathname/stress.txt and, with nlags > 0, pathname/stress_acf.txt.  Not available with Brownian dynamics (no velocities)
+    or a user potential.  Nothing else the run produces changes."""
     brownian = isinstance(ensemble, Brownian)
     os.makedirs(pathname, exist_ok=True)
     trajectory_file, thermo_file = _io.open_files(pathname, traj_name, thermo_name)
@@ -81,6 +87,12 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     if sq is not None:
         sq_stops, sq_events = sq.schedule(total_steps)
         _analysis._sq_start(dev, sq, state.unitcell)
+    st_stops, st_i = [], 0
+    if stress is not None:
+        if brownian:
+            raise ValueError("stress= needs velocities: not available with the Brownian ensemble")
+        st_stops = stress.schedule(total_steps)
+        _analysis._stress_start(dev, stress)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -134,6 +146,10 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             sq_i += 1
         if sq_i < len(sq_stops):
             next_out = min(next_out, sq_stops[sq_i])
+        while st_i < len(st_stops) and st_stops[st_i] < step:
+            st_i += 1
+        if st_i < len(st_stops):
+            next_out = min(next_out, st_stops[st_i])
         last = min(next_out, total_steps - 1)
         U, W, K = segment(step, last - step + 1)
         collect()                       # the frame exported before this segment: its copy had the whole segment to finish
@@ -170,6 +186,9 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
                 sq_i += 1
             if sq_static or sq_event is not None:
                 _analysis._sq_act(dev, sq_static, sq_event)
+        if st_i < len(st_stops) and st_stops[st_i] == last:
+            dev.stress_sample()
+            st_i += 1
         if snapshot_times is not None and snap_i < len(snapshot_times) and snapshot_times[snap_i] == last:
             pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w"))
             want_frame = True
@@ -202,6 +221,12 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         sq.write(os.path.join(pathname, "sq.txt"))
         if sq.dynamic:
             sq.write_fqt(os.path.join(pathname, "fqt.txt"))
+    if stress is not None:
+        _analysis._stress_collect(dev, stress, n, state.unitcell, params.dt)
+        if stress.nsamples > 0:
+            stress.write(os.path.join(pathname, "stress.txt"))
+        if stress.nsamples > 0 and stress.nlags > 0:
+            stress.write_acf(os.path.join(pathname, "stress_acf.txt"))
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
