@@ -5,9 +5,39 @@ the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
 """
+import bisect
 import math
+import os
 
 import numpy as np
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The sampler protocol.  run_simulation drives every sampler class of this module through four private methods:
+#   _begin(dev, run)            set the sampler up on the device and derive what it needs for this run; `run` carries
+#                               total_steps, frequency, n, dim, dt, unitcell and brownian
+#   _next(step)                 the first step >= `step` at which the sampler acts in this run, or None
+#   _act(dev, step)             the device calls of that step
+#   _finish(dev, run, pathname) read back, accumulate into the object, write the files
+
+def _next_multiple(step, period, total_steps):
+    """The first multiple of `period` that is >= step, or None when the run ends before it."""
+    s = -(-step // period) * period
+    return s if s < total_steps else None
+
+
+def _next_stop(stops, step):
+    """The first entry >= step of the sorted list `stops`, or None."""
+    i = bisect.bisect_left(stops, step)
+    return stops[i] if i < len(stops) else None
+
+
+def shell_volumes(edges, dimension):
+    """Volumes (3-D) or areas (2-D) of the shells between consecutive radii of `edges`."""
+    e = edges
+    if dimension == 3:
+        return 4.0 * math.pi / 3.0 * (e[1:] ** 3 - e[:-1] ** 3)
+    return math.pi * (e[1:] ** 2 - e[:-1] ** 2)
 
 
 class RadialDistribution:
@@ -48,11 +78,7 @@ class RadialDistribution:
         self.dimension = u.shape[0]
 
     def shell_volumes(self, dimension=None):
-        d = self.dimension if dimension is None else dimension
-        e = self.edges
-        if d == 3:
-            return 4.0 * math.pi / 3.0 * (e[1:] ** 3 - e[:-1] ** 3)
-        return math.pi * (e[1:] ** 2 - e[:-1] ** 2)
+        return shell_volumes(self.edges, self.dimension if dimension is None else dimension)
 
     def g(self):
         """g_k = counts_k / (nsamples * N (N - 1) / (2 V) * V_k): 1 for an ideal gas."""
@@ -70,13 +96,21 @@ class RadialDistribution:
                 io.write("%.6f %.6f %d\n" % (self.r[k], gr[k], self.counts[k]))
 
 
-def _start(dev, rdf):
-    dev.rdf_setup(rdf.r_max, rdf.nbins)
+    # -- run_simulation's sampler protocol: a sample at every `every`-th output step ---------------------------------
+    def _begin(self, dev, run):
+        self._period, self._total_steps = run.frequency * self.every, run.total_steps
+        dev.rdf_setup(self.r_max, self.nbins)
 
+    def _next(self, step):
+        return _next_multiple(step, self._period, self._total_steps)
 
-def _collect(dev, rdf, n_particles, unitcell):
-    counts, ns = dev.rdf_read()
-    rdf._accumulate(counts, ns, n_particles, unitcell)
+    def _act(self, dev, step):
+        dev.rdf_sample()
+
+    def _finish(self, dev, run, pathname):
+        counts, ns = dev.rdf_read()
+        self._accumulate(counts, ns, run.n, run.unitcell)
+        self.write(os.path.join(pathname, "rdf.txt"))
 
 
 def compute_rdf(state, params, r_max, nbins):
@@ -84,9 +118,10 @@ def compute_rdf(state, params, r_max, nbins):
     rdf = RadialDistribution(r_max, nbins)
     dev = state.system.device
     dev.upload(x=state.system.positions, images=state.images)
-    _start(dev, rdf)
+    dev.rdf_setup(rdf.r_max, rdf.nbins)
     dev.rdf_sample()
-    _collect(dev, rdf, dev.n, state.unitcell)
+    counts, ns = dev.rdf_read()
+    rdf._accumulate(counts, ns, dev.n, state.unitcell)
     return rdf
 
 
@@ -249,11 +284,7 @@ class SelfDynamics:
             return np.where(ns > 0, self.sums[:, 2:] / (self.dimension * self.n_particles * ns), np.nan)
 
     def shell_volumes(self, dimension=None):
-        d = self.dimension if dimension is None else dimension
-        e = self.edges
-        if d == 3:
-            return 4.0 * math.pi / 3.0 * (e[1:] ** 3 - e[:-1] ** 3)
-        return math.pi * (e[1:] ** 2 - e[:-1] ** 2)
+        return shell_volumes(self.edges, self.dimension if dimension is None else dimension)
 
     def van_hove(self):
         """G_s(r_k, t), (nlags, nbins): count_k / (ns N V_k)."""
@@ -288,22 +319,28 @@ class SelfDynamics:
                     io.write("%d %.6f %.6e %d\n" % (int(l), self.r[b], g[k, b], self.hist[k, b]))
 
 
-def _dyn_start(dev, dyn):
-    dev.dyn_setup(dyn.nslots, len(dyn.lags), dyn.q, dyn.r_max or 0.0, dyn.nbins)
+    # -- run_simulation's sampler protocol: the stops of schedule() ---------------------------------------------------
+    def _begin(self, dev, run):
+        self._stops, self._events = self.schedule(run.total_steps)
+        dev.dyn_setup(self.nslots, len(self.lags), self.q, self.r_max or 0.0, self.nbins)
 
+    def _next(self, step):
+        return _next_stop(self._stops, step)
 
-def _dyn_act(dev, event):
-    """The sampler's work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
-    smp, org = event
-    if smp:
-        dev.dyn_sample([a for a, _ in smp], [b for _, b in smp])
-    if org is not None:
-        dev.dyn_origin(org)
+    def _act(self, dev, step):
+        """The work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
+        smp, org = self._events[step]
+        if smp:
+            dev.dyn_sample([a for a, _ in smp], [b for _, b in smp])
+        if org is not None:
+            dev.dyn_origin(org)
 
-
-def _dyn_collect(dev, dyn, n_particles, dimension, dt):
-    ns, sums, hist = dev.dyn_read()
-    dyn._accumulate(ns, sums, hist, n_particles, dimension, dt)
+    def _finish(self, dev, run, pathname):
+        ns, sums, hist = dev.dyn_read()
+        self._accumulate(ns, sums, hist, run.n, run.dim, run.dt)
+        self.write(os.path.join(pathname, "dynamics.txt"))
+        if self.nbins > 0:
+            self.write_van_hove(os.path.join(pathname, "vanhove.txt"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -544,20 +581,31 @@ class StructureFactor:
                                                             int(self.nsamples[k])))
 
 
-def _sq_start(dev, sq, unitcell):
-    sq._select(unitcell)
-    dev.sq_setup(sq.n, sq.nslots, len(sq.lags))
+    # -- run_simulation's sampler protocol: static at every `every`-th output step, dynamic at the stops of schedule() -
+    def _begin(self, dev, run):
+        self._period, self._total_steps = run.frequency * self.every, run.total_steps
+        self._stops, self._events = self.schedule(run.total_steps)
+        self._select(run.unitcell)
+        dev.sq_setup(self.n, self.nslots, len(self.lags))
 
+    def _next(self, step):
+        static = _next_multiple(step, self._period, self._total_steps)
+        dynamic = _next_stop(self._stops, step)
+        if static is None or dynamic is None:
+            return dynamic if static is None else static
+        return min(static, dynamic)
 
-def _sq_act(dev, static, event):
-    """The sampler's work at one stop: rho of the frame once, then the static sample, the correlations, the origin."""
-    smp, org = event if event is not None else ([], None)
-    dev.sq_sample(static, [a for a, _ in smp], [b for _, b in smp], org)
+    def _act(self, dev, step):
+        """The work at one stop: rho of the frame once, then the static sample, the correlations, the origin."""
+        smp, org = self._events.get(step, ([], None))
+        dev.sq_sample(step % self._period == 0, [a for a, _ in smp], [b for _, b in smp], org)
 
-
-def _sq_collect(dev, sq, n_particles, dt):
-    nst, s2, ns, corr = dev.sq_read()
-    sq._accumulate(nst, s2, ns, corr, n_particles, dt)
+    def _finish(self, dev, run, pathname):
+        nst, s2, ns, corr = dev.sq_read()
+        self._accumulate(nst, s2, ns, corr, run.n, run.dt)
+        self.write(os.path.join(pathname, "sq.txt"))
+        if self.dynamic:
+            self.write_fqt(os.path.join(pathname, "fqt.txt"))
 
 
 def compute_sq(state, params, q_max, dq=None, max_per_bin=16, seed=0):
@@ -565,9 +613,11 @@ def compute_sq(state, params, q_max, dq=None, max_per_bin=16, seed=0):
     sq = StructureFactor(q_max, dq=dq, max_per_bin=max_per_bin, seed=seed)
     dev = state.system.device
     dev.upload(x=state.system.positions, images=state.images)
-    _sq_start(dev, sq, state.unitcell)
+    sq._select(state.unitcell)
+    dev.sq_setup(sq.n, sq.nslots, len(sq.lags))
     dev.sq_sample(True)
-    _sq_collect(dev, sq, dev.n, params.dt)
+    nst, s2, ns, corr = dev.sq_read()
+    sq._accumulate(nst, s2, ns, corr, dev.n, params.dt)
     return sq
 
 
@@ -731,13 +781,26 @@ class StressTensor:
                              % ((k, t[k], cs[k]) + tuple(c[k]) + (eta[k], int(self.ncorr[k]))))
 
 
-def _stress_start(dev, stress):
-    dev.stress_setup(stress.nlags)
+    # -- run_simulation's sampler protocol: a sample at every multiple of `every` --------------------------------------
+    def _begin(self, dev, run):
+        if run.brownian:
+            raise ValueError("stress= needs velocities: not available with the Brownian ensemble")
+        self._total_steps = run.total_steps
+        dev.stress_setup(self.nlags)
 
+    def _next(self, step):
+        return _next_multiple(step, self.every, self._total_steps)
 
-def _stress_collect(dev, stress, n_particles, unitcell, dt):
-    ns, sk, sv, ncorr, corr = dev.stress_read()
-    stress._accumulate(ns, sk, sv, ncorr, corr, n_particles, unitcell, dt)
+    def _act(self, dev, step):
+        dev.stress_sample()
+
+    def _finish(self, dev, run, pathname):
+        ns, sk, sv, ncorr, corr = dev.stress_read()
+        self._accumulate(ns, sk, sv, ncorr, corr, run.n, run.unitcell, run.dt)
+        if self.nsamples > 0:
+            self.write(os.path.join(pathname, "stress.txt"))
+        if self.nsamples > 0 and self.nlags > 0:
+            self.write_acf(os.path.join(pathname, "stress_acf.txt"))
 
 
 def compute_stress(state, params):

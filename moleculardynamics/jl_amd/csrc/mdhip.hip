@@ -1427,6 +1427,16 @@ inline void require_state(md_ctx *c, const char *who)
                                           "incomplete; upload x, v and f again (md_upload) before going on");
 }
 
+// The sampler `member` of the handle (md_ctx::rdf, dyn, sq, stress; `x` is its name in md_<x>_setup), once its setup has
+// succeeded.
+template <class S> inline S &sampler_of(md_ctx *ctx, S md_ctx::*member, const char *who, const char *x)
+{
+    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
+    S &s = ctx->*member;
+    if (!s.on) throw HipError(std::string(who) + ": no setup (call md_" + x + "_setup first)");
+    return s;
+}
+
 #define API_BEGIN                                                                                                   \
     if (!ctx) return fail(nullptr, "null handle");                                                                  \
     try {                                                                                                           \
@@ -1903,19 +1913,77 @@ int md_neighbor_pairs(md_ctx *ctx, int32_t *pairs, int64_t cap, int64_t *count)
 }
 
 // ---------------------------------------------------------------------------------------------
+// Shared by the sampler entry points below (md_rdf_*, md_dyn_*, md_sq_*, md_stress_*), with sampler_of above.
+static void check_range(const char *who, const char *name, int v, int lo, int hi)
+{
+    if (v >= lo && v <= hi) return;
+    char b[200];
+    snprintf(b, sizeof b, "%s: %s must be in %d..%d, got %d", who, name, lo, hi, v);
+    throw HipError(b);
+}
+
+// Squared bin edges e2[k] = (k delta)^2, delta = r_max / nbins, k = 0..nbins: the table decides every bin of the g(r)
+// and the van Hove histograms.  All zeros when nbins == 0.
+static std::vector<double> squared_edges(double r_max, int nbins)
+{
+#pragma clang fp contract(off)
+    std::vector<double> e2(nbins + 1, 0.0);
+    if (nbins > 0) {
+        const double delta = r_max / nbins;
+        for (int k = 0; k <= nbins; ++k) {
+            double rk = (double)k * delta;
+            e2[k] = rk * rk;
+        }
+    }
+    return e2;
+}
+
+// The (slot, row) pairs of one md_dyn_sample / md_sq_sample call: every slot holds an origin, every row exists.
+static void check_batch(const char *who, const int32_t *slots, const int32_t *rows, int count, int nslots, int nrows,
+                        const std::vector<char> &filled, const char *empty_hint)
+{
+    char b[200];
+    if (count < 0) {
+        snprintf(b, sizeof b, "%s: count must be >= 0, got %d", who, count);
+        throw HipError(b);
+    }
+    if (count > 0 && (!slots || !rows)) throw HipError(std::string(who) + ": slots / rows is null");
+    for (int i = 0; i < count; ++i) {
+        if (slots[i] < 0 || slots[i] >= nslots) {
+            snprintf(b, sizeof b, "%s: slot %d is out of range 0..%d", who, (int)slots[i], nslots - 1);
+            throw HipError(b);
+        }
+        if (rows[i] < 0 || rows[i] >= nrows) {
+            snprintf(b, sizeof b, "%s: row %d is out of range 0..%d", who, (int)rows[i], nrows - 1);
+            throw HipError(b);
+        }
+        if (!filled[slots[i]]) {
+            snprintf(b, sizeof b, "%s: slot %d is empty (%s)", who, (int)slots[i], empty_hint);
+            throw HipError(b);
+        }
+    }
+}
+
+// The gather md_download makes, of the wrapped coordinates and image counts only, into a sampler's own frame buffers.
+static void export_frame(md_ctx *ctx, double *x, int32_t *im)
+{
+    DevState s = ctx->dev(ctx->cur);
+    if (ctx->dim == 3)
+        k_export<3><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
+    else
+        k_export<2><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
+    HIPCHK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------------------------------------
 // Radial distribution function (md_rdf.hpp): a sample reads the state and writes only the rdf scratch, so the step
 // loop, the list and the cell order are exactly what they would have been without it.
 int md_rdf_setup(md_ctx *ctx, double r_max, int nbins)
 {
-#pragma clang fp contract(off)
     API_BEGIN
     if (ctx->dom.on) throw HipError("md_rdf_setup: not available on a slab-decomposition handle");
     if (!(r_max > 0.0) || !std::isfinite(r_max)) throw HipError("md_rdf_setup: r_max must be finite and > 0");
-    if (nbins < 1 || nbins > MD_RDF_MAX_BINS) {
-        char b[160];
-        snprintf(b, sizeof b, "md_rdf_setup: nbins must be in 1..%d, got %d", MD_RDF_MAX_BINS, nbins);
-        throw HipError(b);
-    }
+    check_range("md_rdf_setup", "nbins", nbins, 1, MD_RDF_MAX_BINS);
     for (int c = 0; c < ctx->dim; ++c)
         if (ctx->perp[c] < 3.0 * r_max) {
             char b[320];
@@ -1953,13 +2021,7 @@ int md_rdf_setup(md_ctx *ctx, double r_max, int nbins)
         g.A[c] = ctx->A[c];
         g.Ainv[c] = ctx->Ainv[c];
     }
-    // squared bin edges: e2[k] = (k delta)^2, delta = r_max / nbins; the table decides every bin
-    std::vector<double> e2(nbins + 1);
-    const double delta = r_max / nbins;
-    for (int k = 0; k <= nbins; ++k) {
-        double rk = (double)k * delta;
-        e2[k] = rk * rk;
-    }
+    const std::vector<double> e2 = squared_edges(r_max, nbins);
     hipStream_t st = ctx->stream;
     R.e2.alloc(nbins + 1);
     R.hist.alloc(nbins);
@@ -1995,8 +2057,7 @@ int md_rdf_sample(md_ctx *ctx)
 {
     API_BEGIN
     require_state(ctx, "md_rdf_sample");
-    md_ctx::Rdf &R = ctx->rdf;
-    if (!R.on) throw HipError("md_rdf_sample: no setup (call md_rdf_setup first)");
+    md_ctx::Rdf &R = sampler_of(ctx, &md_ctx::rdf, "md_rdf_sample", "rdf");
     const int n = (int)ctx->n;
     const RdfGrid &g = R.grid;
     hipStream_t st = ctx->stream;
@@ -2034,8 +2095,7 @@ int md_rdf_sample(md_ctx *ctx)
 int md_rdf_read(md_ctx *ctx, int64_t *counts, int64_t *nsamples)
 {
     API_BEGIN
-    md_ctx::Rdf &R = ctx->rdf;
-    if (!R.on) throw HipError("md_rdf_read: no setup (call md_rdf_setup first)");
+    md_ctx::Rdf &R = sampler_of(ctx, &md_ctx::rdf, "md_rdf_read", "rdf");
     std::vector<unsigned long long> h(R.nbins);
     HIPCHK(hipMemcpyAsync(h.data(), R.hist.p, sizeof(unsigned long long) * R.nbins, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -2048,8 +2108,7 @@ int md_rdf_read(md_ctx *ctx, int64_t *counts, int64_t *nsamples)
 int md_rdf_reset(md_ctx *ctx)
 {
     API_BEGIN
-    md_ctx::Rdf &R = ctx->rdf;
-    if (!R.on) throw HipError("md_rdf_reset: no setup (call md_rdf_setup first)");
+    md_ctx::Rdf &R = sampler_of(ctx, &md_ctx::rdf, "md_rdf_reset", "rdf");
     HIPCHK(hipMemsetAsync(R.hist.p, 0, sizeof(unsigned long long) * R.nbins, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     R.nsamples = 0;
@@ -2060,51 +2119,24 @@ int md_rdf_reset(md_ctx *ctx)
 // Self dynamics (md_dyn.hpp): an origin store and a sample each launch k_export -- the gather md_download makes -- into the
 // sampler's own buffers and read nothing else of the state, so the step loop, the list and the cell order are exactly
 // what they would have been without them.
-static md_ctx::Dyn &dyn_of(md_ctx *ctx, const char *who)
-{
-    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
-    if (!ctx->dyn.on) throw HipError(std::string(who) + ": no setup (call md_dyn_setup first)");
-    return ctx->dyn;
-}
-
-static void dyn_export(md_ctx *ctx, double *x, int32_t *im)
-{
-    DevState s = ctx->dev(ctx->cur);
-    if (ctx->dim == 3)
-        k_export<3><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
-    else
-        k_export<2><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
-    HIPCHK(hipGetLastError());
-}
-
 int md_dyn_setup(md_ctx *ctx, int nslots, int nrows, const double *q, int nq, double r_max, int nbins)
 {
-#pragma clang fp contract(off)
     API_BEGIN
     if (ctx->dom.on) throw HipError("md_dyn_setup: not available on a slab-decomposition handle");
     char b[320];
-    if (nslots < 1 || nslots > MD_DYN_MAX_SLOTS) {
-        snprintf(b, sizeof b, "md_dyn_setup: nslots must be in 1..%d, got %d", MD_DYN_MAX_SLOTS, nslots);
-        throw HipError(b);
-    }
+    check_range("md_dyn_setup", "nslots", nslots, 1, MD_DYN_MAX_SLOTS);
     if (nrows < 1) {
         snprintf(b, sizeof b, "md_dyn_setup: nrows must be >= 1, got %d", nrows);
         throw HipError(b);
     }
-    if (nq < 0 || nq > MD_DYN_MAX_Q) {
-        snprintf(b, sizeof b, "md_dyn_setup: nq must be in 0..%d, got %d", MD_DYN_MAX_Q, nq);
-        throw HipError(b);
-    }
+    check_range("md_dyn_setup", "nq", nq, 0, MD_DYN_MAX_Q);
     if (nq > 0 && !q) throw HipError("md_dyn_setup: q is null");
     for (int j = 0; j < nq; ++j)
         if (!std::isfinite(q[j])) {
             snprintf(b, sizeof b, "md_dyn_setup: q[%d] must be finite", j);
             throw HipError(b);
         }
-    if (nbins < 0 || nbins > MD_DYN_MAX_BINS) {
-        snprintf(b, sizeof b, "md_dyn_setup: nbins must be in 0..%d, got %d", MD_DYN_MAX_BINS, nbins);
-        throw HipError(b);
-    }
+    check_range("md_dyn_setup", "nbins", nbins, 0, MD_DYN_MAX_BINS);
     if (nbins > 0 && (!(r_max > 0.0) || !std::isfinite(r_max)))
         throw HipError("md_dyn_setup: r_max must be finite and > 0 when nbins > 0");
     md_ctx::Dyn &Y = ctx->dyn;
@@ -2139,15 +2171,7 @@ int md_dyn_setup(md_ctx *ctx, int nslots, int nrows, const double *q, int nq, do
     Y.sums.alloc((size_t)nrows * nquant);
     Y.hist.alloc((size_t)nrows * std::max(nbins, 1));
     Y.e2.alloc((size_t)nbins + 1);
-    // squared bin edges exactly as md_rdf_setup builds them: e2[k] = (k delta)^2, delta = r_max / nbins
-    std::vector<double> e2(nbins + 1, 0.0);
-    if (nbins > 0) {
-        const double delta = r_max / nbins;
-        for (int k = 0; k <= nbins; ++k) {
-            double rk = (double)k * delta;
-            e2[k] = rk * rk;
-        }
-    }
+    const std::vector<double> e2 = squared_edges(r_max, nbins);
     hipStream_t st = ctx->stream;
     HIPCHK(hipMemcpyAsync(Y.e2.p, e2.data(), sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(Y.sums.p, 0, sizeof(double) * nrows * nquant, st));
@@ -2168,7 +2192,7 @@ int md_dyn_setup(md_ctx *ctx, int nslots, int nrows, const double *q, int nq, do
 int md_dyn_origin(md_ctx *ctx, int slot)
 {
     API_BEGIN
-    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_origin");
+    md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_origin", "dyn");
     require_state(ctx, "md_dyn_origin");
     if (slot < 0 || slot >= Y.nslots) {
         char b[160];
@@ -2176,7 +2200,7 @@ int md_dyn_origin(md_ctx *ctx, int slot)
         throw HipError(b);
     }
     const size_t frame = (size_t)ctx->n * ctx->dim;
-    dyn_export(ctx, Y.ox + (size_t)slot * frame, Y.oi + (size_t)slot * frame);
+    export_frame(ctx, Y.ox + (size_t)slot * frame, Y.oi + (size_t)slot * frame);
     Y.filled[slot] = 1;
     API_END
 }
@@ -2185,32 +2209,13 @@ int md_dyn_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int co
 {
 #pragma clang fp contract(off)
     API_BEGIN
-    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_sample");
+    md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_sample", "dyn");
     require_state(ctx, "md_dyn_sample");
-    char b[200];
-    if (count < 0) {
-        snprintf(b, sizeof b, "md_dyn_sample: count must be >= 0, got %d", count);
-        throw HipError(b);
-    }
-    if (count > 0 && (!slots || !rows)) throw HipError("md_dyn_sample: slots / rows is null");
-    for (int i = 0; i < count; ++i) {
-        if (slots[i] < 0 || slots[i] >= Y.nslots) {
-            snprintf(b, sizeof b, "md_dyn_sample: slot %d is out of range 0..%d", (int)slots[i], Y.nslots - 1);
-            throw HipError(b);
-        }
-        if (rows[i] < 0 || rows[i] >= Y.nrows) {
-            snprintf(b, sizeof b, "md_dyn_sample: row %d is out of range 0..%d", (int)rows[i], Y.nrows - 1);
-            throw HipError(b);
-        }
-        if (!Y.filled[slots[i]]) {
-            snprintf(b, sizeof b, "md_dyn_sample: slot %d is empty (store an origin with md_dyn_origin first)",
-                     (int)slots[i]);
-            throw HipError(b);
-        }
-    }
+    check_batch("md_dyn_sample", slots, rows, count, Y.nslots, Y.nrows, Y.filled,
+                "store an origin with md_dyn_origin first");
     if (count == 0) return 0;
     hipStream_t st = ctx->stream;
-    dyn_export(ctx, Y.cx.p, Y.ci.p);
+    export_frame(ctx, Y.cx.p, Y.ci.p);
     DynParams P{};
     P.n = (int)ctx->n;
     P.dim = ctx->dim;
@@ -2245,7 +2250,7 @@ int md_dyn_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int co
 int md_dyn_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *hist)
 {
     API_BEGIN
-    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_read");
+    md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_read", "dyn");
     const size_t ns = (size_t)Y.nrows * (2 + Y.nq), nh = (size_t)Y.nrows * Y.nbins;
     hipStream_t st = ctx->stream;
     std::vector<unsigned long long> h(nh);
@@ -2262,7 +2267,7 @@ int md_dyn_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *hist)
 int md_dyn_reset(md_ctx *ctx)
 {
     API_BEGIN
-    md_ctx::Dyn &Y = dyn_of(ctx, "md_dyn_reset");
+    md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_reset", "dyn");
     hipStream_t st = ctx->stream;
     HIPCHK(hipMemsetAsync(Y.sums.p, 0, sizeof(double) * Y.nrows * (2 + Y.nq), st));
     HIPCHK(hipMemsetAsync(Y.hist.p, 0, sizeof(unsigned long long) * Y.nrows * std::max(Y.nbins, 1), st));
@@ -2274,27 +2279,14 @@ int md_dyn_reset(md_ctx *ctx)
 // ---------------------------------------------------------------------------------------------
 // Density modes, S(q) and coherent F(q, t) (md_sq.hpp): a sample launches k_export into the sampler's own frame buffer and
 // reads nothing else of the state, so the step loop, the list and the cell order are what they would have been without it.
-static md_ctx::Sq &sq_of(md_ctx *ctx, const char *who)
-{
-    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
-    if (!ctx->sq.on) throw HipError(std::string(who) + ": no setup (call md_sq_setup first)");
-    return ctx->sq;
-}
-
 int md_sq_setup(md_ctx *ctx, const int32_t *nvecs, int nvec, int nslots, int nrows)
 {
     API_BEGIN
     if (ctx->dom.on) throw HipError("md_sq_setup: not available on a slab-decomposition handle");
     char b[240];
-    if (nvec < 1 || nvec > MD_SQ_MAX_VEC) {
-        snprintf(b, sizeof b, "md_sq_setup: nvec must be in 1..%d, got %d", MD_SQ_MAX_VEC, nvec);
-        throw HipError(b);
-    }
+    check_range("md_sq_setup", "nvec", nvec, 1, MD_SQ_MAX_VEC);
     if (!nvecs) throw HipError("md_sq_setup: n is null");
-    if (nslots < 0 || nslots > MD_SQ_MAX_SLOTS) {
-        snprintf(b, sizeof b, "md_sq_setup: nslots must be in 0..%d, got %d", MD_SQ_MAX_SLOTS, nslots);
-        throw HipError(b);
-    }
+    check_range("md_sq_setup", "nslots", nslots, 0, MD_SQ_MAX_SLOTS);
     if (nrows < 0) {
         snprintf(b, sizeof b, "md_sq_setup: nrows must be >= 0, got %d", nrows);
         throw HipError(b);
@@ -2357,41 +2349,22 @@ int md_sq_setup(md_ctx *ctx, const int32_t *nvecs, int nvec, int nslots, int nro
 int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_t *rows, int count, int origin_slot)
 {
     API_BEGIN
-    md_ctx::Sq &S = sq_of(ctx, "md_sq_sample");
+    md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_sample", "sq");
     require_state(ctx, "md_sq_sample");
-    char b[200];
-    if (count < 0) {
-        snprintf(b, sizeof b, "md_sq_sample: count must be >= 0, got %d", count);
-        throw HipError(b);
-    }
-    if (count > 0 && (!slots || !rows)) throw HipError("md_sq_sample: slots / rows is null");
-    for (int i = 0; i < count; ++i) {
-        if (slots[i] < 0 || slots[i] >= S.nslots) {
-            snprintf(b, sizeof b, "md_sq_sample: slot %d is out of range 0..%d", (int)slots[i], S.nslots - 1);
-            throw HipError(b);
-        }
-        if (rows[i] < 0 || rows[i] >= S.nrows) {
-            snprintf(b, sizeof b, "md_sq_sample: row %d is out of range 0..%d", (int)rows[i], S.nrows - 1);
-            throw HipError(b);
-        }
-        if (!S.filled[slots[i]]) {
-            snprintf(b, sizeof b, "md_sq_sample: slot %d is empty (store an origin with origin_slot first)", (int)slots[i]);
-            throw HipError(b);
-        }
-    }
+    check_batch("md_sq_sample", slots, rows, count, S.nslots, S.nrows, S.filled,
+                "store an origin with origin_slot first");
     if (origin_slot < -1 || origin_slot >= S.nslots) {
+        char b[200];
         snprintf(b, sizeof b, "md_sq_sample: origin slot %d is out of range -1..%d", origin_slot, S.nslots - 1);
         throw HipError(b);
     }
     hipStream_t st = ctx->stream;
     const int n = (int)ctx->n;
-    DevState s = ctx->dev(ctx->cur);
+    export_frame(ctx, S.cx.p, S.ci.p);
     if (ctx->dim == 3) {
-        k_export<3><<<ctx->nblk, MD_BLOCK, 0, st>>>(n, s, ctx->grid, S.cx.p, nullptr, nullptr, S.ci.p);
         k_sq_frac<3><<<nblocks(n), MD_BLOCK, 0, st>>>(n, ctx->grid, S.cx.p, S.fr.p);
         k_sq_rho<3><<<dim3(S.nblk, S.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(n, S.nblk, S.fr.p, S.nd.p, S.part.p);
     } else {
-        k_export<2><<<ctx->nblk, MD_BLOCK, 0, st>>>(n, s, ctx->grid, S.cx.p, nullptr, nullptr, S.ci.p);
         k_sq_frac<2><<<nblocks(n), MD_BLOCK, 0, st>>>(n, ctx->grid, S.cx.p, S.fr.p);
         k_sq_rho<2><<<dim3(S.nblk, S.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(n, S.nblk, S.fr.p, S.nd.p, S.part.p);
     }
@@ -2421,7 +2394,7 @@ int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_
 int md_sq_rho(md_ctx *ctx, double *rho)
 {
     API_BEGIN
-    md_ctx::Sq &S = sq_of(ctx, "md_sq_rho");
+    md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_rho", "sq");
     if (!S.sampled) throw HipError("md_sq_rho: no frame has been sampled since md_sq_setup");
     if (!rho) throw HipError("md_sq_rho: rho is null");
     HIPCHK(hipMemcpyAsync(rho, S.rho.p, sizeof(double) * S.nvec * 2, hipMemcpyDeviceToHost, ctx->stream));
@@ -2432,7 +2405,7 @@ int md_sq_rho(md_ctx *ctx, double *rho)
 int md_sq_read(md_ctx *ctx, int64_t *nstatic, double *s2, int64_t *nsamples, double *corr)
 {
     API_BEGIN
-    md_ctx::Sq &S = sq_of(ctx, "md_sq_read");
+    md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_read", "sq");
     hipStream_t st = ctx->stream;
     if (s2) HIPCHK(hipMemcpyAsync(s2, S.s2.p, sizeof(double) * S.nvec, hipMemcpyDeviceToHost, st));
     if (corr && S.nrows)
@@ -2447,7 +2420,7 @@ int md_sq_read(md_ctx *ctx, int64_t *nstatic, double *s2, int64_t *nsamples, dou
 int md_sq_reset(md_ctx *ctx)
 {
     API_BEGIN
-    md_ctx::Sq &S = sq_of(ctx, "md_sq_reset");
+    md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_reset", "sq");
     hipStream_t st = ctx->stream;
     HIPCHK(hipMemsetAsync(S.s2.p, 0, sizeof(double) * S.nvec, st));
     if (S.nrows) HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * S.nrows * S.nvec, st));
@@ -2461,23 +2434,12 @@ int md_sq_reset(md_ctx *ctx)
 // Pressure tensor and its lag correlations (md_stress.hpp): a sample walks the OUTER rows -- valid for the current
 // positions whenever the list is, as md_compute_forces relies on -- reads positions and velocities and writes only the
 // sampler's own buffers, so the step loop, the list and the cell order are exactly what they would have been without it.
-static md_ctx::Stress &stress_of(md_ctx *ctx, const char *who)
-{
-    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
-    if (!ctx->stress.on) throw HipError(std::string(who) + ": no setup (call md_stress_setup first)");
-    return ctx->stress;
-}
-
 int md_stress_setup(md_ctx *ctx, int nlags)
 {
     API_BEGIN
     if (ctx->dom.on) throw HipError("md_stress_setup: not available on a slab-decomposition handle");
     if (ctx->pot_kind == POT_CUSTOM) throw HipError("md_stress_setup: not available with a user potential (MD_POT_CUSTOM)");
-    if (nlags < 0 || nlags > MD_STRESS_MAX_LAGS) {
-        char b[160];
-        snprintf(b, sizeof b, "md_stress_setup: nlags must be in 0..%d, got %d", MD_STRESS_MAX_LAGS, nlags);
-        throw HipError(b);
-    }
+    check_range("md_stress_setup", "nlags", nlags, 0, MD_STRESS_MAX_LAGS);
     md_ctx::Stress &S = ctx->stress;
     S.on = false;
     const int nc = stress_nc(ctx);
@@ -2498,7 +2460,7 @@ int md_stress_sample(md_ctx *ctx)
 {
     API_BEGIN
     require_state(ctx, "md_stress_sample");
-    md_ctx::Stress &S = stress_of(ctx, "md_stress_sample");
+    md_ctx::Stress &S = sampler_of(ctx, &md_ctx::stress, "md_stress_sample", "stress");
     if (ctx->pot_kind == POT_CUSTOM) throw HipError("md_stress_sample: not available with a user potential (MD_POT_CUSTOM)");
     if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
     const int nc = stress_nc(ctx);
@@ -2521,7 +2483,7 @@ int md_stress_sample(md_ctx *ctx)
 int md_stress_tensor(md_ctx *ctx, double *kin, double *vir)
 {
     API_BEGIN
-    md_ctx::Stress &S = stress_of(ctx, "md_stress_tensor");
+    md_ctx::Stress &S = sampler_of(ctx, &md_ctx::stress, "md_stress_tensor", "stress");
     if (!S.sampled) throw HipError("md_stress_tensor: no frame sampled yet (call md_stress_sample first)");
     const int nc = stress_nc(ctx);
     double h[12];
@@ -2537,7 +2499,7 @@ int md_stress_tensor(md_ctx *ctx, double *kin, double *vir)
 int md_stress_read(md_ctx *ctx, int64_t *nsamples, double *sum_kin, double *sum_vir, int64_t *ncorr, double *corr)
 {
     API_BEGIN
-    md_ctx::Stress &S = stress_of(ctx, "md_stress_read");
+    md_ctx::Stress &S = sampler_of(ctx, &md_ctx::stress, "md_stress_read", "stress");
     const int nc = stress_nc(ctx);
     double h[12];
     HIPCHK(hipMemcpyAsync(h, S.sums.p, sizeof(double) * 2 * nc, hipMemcpyDeviceToHost, ctx->stream));
@@ -2558,7 +2520,7 @@ int md_stress_read(md_ctx *ctx, int64_t *nsamples, double *sum_kin, double *sum_
 int md_stress_reset(md_ctx *ctx)
 {
     API_BEGIN
-    stress_of(ctx, "md_stress_reset");
+    sampler_of(ctx, &md_ctx::stress, "md_stress_reset", "stress");
     stress_zero(ctx);
     API_END
 }

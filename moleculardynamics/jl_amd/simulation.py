@@ -6,6 +6,7 @@ so step 0 is always an output step), draws the thermostat's random numbers on th
 reference's order, and writes the thermo / trajectory files.
 """
 import os
+import types
 
 import numpy as np
 
@@ -77,22 +78,12 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     # Brownian method (src/simulation.jl:181-308): the device's noise stream is keyed by one draw of state.rng;
     # the virial is sampled every 10th step and averaged at the output steps (:253-266)
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
-    if rdf is not None:
-        _analysis._start(dev, rdf)
-    dyn_stops, dyn_events, dyn_i = [], {}, 0
-    if dynamics is not None:
-        dyn_stops, dyn_events = dynamics.schedule(total_steps)
-        _analysis._dyn_start(dev, dynamics)
-    sq_stops, sq_events, sq_i = [], {}, 0
-    if sq is not None:
-        sq_stops, sq_events = sq.schedule(total_steps)
-        _analysis._sq_start(dev, sq, state.unitcell)
-    st_stops, st_i = [], 0
-    if stress is not None:
-        if brownian:
-            raise ValueError("stress= needs velocities: not available with the Brownian ensemble")
-        st_stops = stress.schedule(total_steps)
-        _analysis._stress_start(dev, stress)
+    # the samplers (analysis.py's protocol), in the order their device calls are made at a step they share
+    samplers = [s for s in (rdf, dynamics, sq, stress) if s is not None]
+    run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
+                                unitcell=state.unitcell, brownian=brownian)
+    for s in samplers:
+        s._begin(dev, run)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -113,9 +104,7 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         return dev.run(nsteps, params.dt, ens_kind, tau, state.nf, kt, r1, r2, thermo=True)
 
     # log-spaced snapshots (src/simulation.jl:80-87,153-171): step 0 plus generate_log_times()
-    snapshot_times, snap_i = None, 0
-    if log_times:
-        snapshot_times = [0] + _io.generate_log_times()
+    snapshot_times = [0] + _io.generate_log_times() if log_times else []
     writer = _io.AsyncWriter()      # frames are formatted and written while the next segment runs
     # A frame is exported asynchronously (md_snapshot_begin: gather + copy to pinned memory on a copy stream) and collected
     # AFTER the next segment has been run: the device-to-host copy overlaps that segment, the formatting and the file
@@ -131,29 +120,16 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
 
     step = 0
     while step < total_steps:
-        # run up to and including the next output step (thermo / trajectory cadence, or a snapshot time)
-        next_out = step if step % frequency == 0 else (step // frequency + 1) * frequency
-        if snapshot_times is not None:
-            while snap_i < len(snapshot_times) and snapshot_times[snap_i] < step:
-                snap_i += 1
-            if snap_i < len(snapshot_times):
-                next_out = min(next_out, snapshot_times[snap_i])
-        while dyn_i < len(dyn_stops) and dyn_stops[dyn_i] < step:
-            dyn_i += 1
-        if dyn_i < len(dyn_stops):
-            next_out = min(next_out, dyn_stops[dyn_i])
-        while sq_i < len(sq_stops) and sq_stops[sq_i] < step:
-            sq_i += 1
-        if sq_i < len(sq_stops):
-            next_out = min(next_out, sq_stops[sq_i])
-        while st_i < len(st_stops) and st_stops[st_i] < step:
-            st_i += 1
-        if st_i < len(st_stops):
-            next_out = min(next_out, st_stops[st_i])
-        last = min(next_out, total_steps - 1)
+        # run up to and including the next output step (thermo / trajectory cadence, a snapshot time or a sampler's stop)
+        stops = [-(-step // frequency) * frequency, _analysis._next_stop(snapshot_times, step)]
+        stops += [s._next(step) for s in samplers]
+        last = min(min(t for t in stops if t is not None), total_steps - 1)
         U, W, K = segment(step, last - step + 1)
         collect()                       # the frame exported before this segment: its copy had the whole segment to finish
         step = last + 1
+        for s in samplers:
+            if s._next(last) == last:
+                s._act(dev, last)
         want_frame = False
         if last % frequency == 0:
             if brownian:
@@ -173,26 +149,9 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             if write_trajectory:
                 pending.append((trajectory_file, last, "a"))
                 want_frame = True
-        if rdf is not None and last % frequency == 0 and (last // frequency) % rdf.every == 0:
-            dev.rdf_sample()
-        if dyn_i < len(dyn_stops) and dyn_stops[dyn_i] == last:
-            _analysis._dyn_act(dev, dyn_events[last])
-            dyn_i += 1
-        if sq is not None:
-            sq_static = last % frequency == 0 and (last // frequency) % sq.every == 0
-            sq_event = None
-            if sq_i < len(sq_stops) and sq_stops[sq_i] == last:
-                sq_event = sq_events[last]
-                sq_i += 1
-            if sq_static or sq_event is not None:
-                _analysis._sq_act(dev, sq_static, sq_event)
-        if st_i < len(st_stops) and st_stops[st_i] == last:
-            dev.stress_sample()
-            st_i += 1
-        if snapshot_times is not None and snap_i < len(snapshot_times) and snapshot_times[snap_i] == last:
+        if _analysis._next_stop(snapshot_times, last) == last:
             pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w"))
             want_frame = True
-            snap_i += 1
         if want_frame:
             dev.snapshot_begin()
 
@@ -208,25 +167,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     # finalize_simulation!: src/simulation.jl:11-36
     _io.write_to_file(os.path.join(pathname, "final.xyz"), total_steps, state.unitcell, n, x, state.diameters, dim,
                       mode="w")
-    if rdf is not None:
-        _analysis._collect(dev, rdf, n, state.unitcell)
-        rdf.write(os.path.join(pathname, "rdf.txt"))
-    if dynamics is not None:
-        _analysis._dyn_collect(dev, dynamics, n, dim, params.dt)
-        dynamics.write(os.path.join(pathname, "dynamics.txt"))
-        if dynamics.nbins > 0:
-            dynamics.write_van_hove(os.path.join(pathname, "vanhove.txt"))
-    if sq is not None:
-        _analysis._sq_collect(dev, sq, n, params.dt)
-        sq.write(os.path.join(pathname, "sq.txt"))
-        if sq.dynamic:
-            sq.write_fqt(os.path.join(pathname, "fqt.txt"))
-    if stress is not None:
-        _analysis._stress_collect(dev, stress, n, state.unitcell, params.dt)
-        if stress.nsamples > 0:
-            stress.write(os.path.join(pathname, "stress.txt"))
-        if stress.nsamples > 0 and stress.nlags > 0:
-            stress.write_acf(os.path.join(pathname, "stress_acf.txt"))
+    for s in samplers:
+        s._finish(dev, run, pathname)
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
