@@ -266,6 +266,56 @@ int md_stress_tensor(md_ctx *ctx, double *kin, double *vir);
 int md_stress_read(md_ctx *ctx, int64_t *nsamples, double *sum_kin, double *sum_vir, int64_t *ncorr, double *corr);
 int md_stress_reset(md_ctx *ctx);
 
+/* Bond-orientational order, sampled on the device (new relative to the reference, whose users dump frames to learn
+ * whether the system crystallised): Steinhardt q_l and its neighbour-averaged (Lechner-Dellago) form for l = 4 or 6 in
+ * 3-D, the k-fold psi_k (1 <= k <= 12) in 2-D, and ten Wolde's solid-bond count.  The potential is never evaluated: the
+ * sampler serves every potential, MD_POT_CUSTOM included.
+ *
+ * Neighbours: j is a neighbour of i iff d2 < rn2, with del = x_j(+periodic translation) - x_i as the force kernels form
+ * it, d2 = (del0*del0 + del1*del1) + del2*del2 (no fma) and rn2 = r_neigh*r_neigh rounded once on the host;
+ * 0 < r_neigh <= list_cutoff (the rows are complete only up to list_cutoff).  n_i = number of neighbours of i.
+ *
+ * 3-D, u = del/|del|:  Y_lm(u) = sqrt((2l+1)/(4 pi) (l-m)!/(l+m)!) P_l^m(cos theta) e^{i m phi}, Condon-Shortley phase,
+ * evaluated in fp64 as c_lm D_l^m(u_z) (u_x + i u_y)^m, D_l^m = d^m P_l/dz^m, c_lm = (-1)^m times the square root above.
+ * Only m = 0..l is stored (NM = l + 1 complex numbers per particle); Y_{l,-m} = (-1)^m conj(Y_lm).
+ *   q_lm(i) = (1/n_i) sum_j Y_lm(u_ij)   (0 if n_i = 0)
+ *   q_l(i)  = sqrt(4 pi/(2l+1) (|q_l0|^2 + 2 sum_{m>0} |q_lm|^2))
+ *   Q_lm(i) = (q_lm(i) + sum_{j in N(i)} q_lm(j))/(n_i + 1),   qbar_l(i) = the same invariant of Q_lm
+ *   s_ij    = Re sum_{m=-l..l} q_lm(i) conj(q_lm(j)) / (|q_l(i)| |q_l(j)|), |.| the 2-norm over all m (0 if either is 0)
+ *   c_i     = number of neighbours with s_ij > threshold;  i is solid iff c_i >= min_conn
+ * 2-D (NM = 1): psi_k(i) = (1/n_i) sum_j ((del_x + i del_y)/|del|)^k, the invariant is |psi_k(i)|; Q, qbar and s_ij are
+ * the same formulas with that single component.
+ *
+ * The frame vector fr[8]: sum_i q, sum_i q^2, sum_i qbar, sum_i qbar^2, sum_i n_i, sum_i c_i, the number of solid
+ * particles, and the global order parameter sqrt(4 pi/(2l+1) sum_m |sum_i n_i q_lm(i) / sum_i n_i|^2)  (2-D:
+ * |sum_i n_i psi_k(i) / sum_i n_i|).  Summation: each particle walks its outer neighbour row in row order; then the 64
+ * lanes of a wave, the 4 waves of a block in order and the blocks in block order -- no floating-point atomics.  The
+ * per-particle sums depend on the handle's row order: reproducible for one handle history, not a function of the frame
+ * alone (two handles holding the same frame agree to rounding, ~1e-14).
+ *
+ * Accumulated on the device since setup or the last reset: sum_fr[8] += fr and nsamples; integer histograms
+ * hist_q[nbins], hist_qbar[nbins] over [0, 1], bin = min((int)(value*nbins), nbins-1); hist_nnb[33] and hist_conn[33],
+ * counts of n_i and c_i clamped to 32; sample number m < nseries also writes fr into series[m*8 .. m*8+8).
+ *
+ * md_boo_setup: order = l (4 or 6) in 3-D, k (1..12) in 2-D; 1 <= nbins <= 8192; threshold finite; 0 <= min_conn <= 32;
+ * 0 <= nseries <= 2^20; everything zeroed; calling it again starts over.  md_boo_sample does not wait and changes nothing
+ * the handle computes afterwards: it writes only the sampler's own buffers; if the neighbour list is not valid (first
+ * call after md_upload) it builds it exactly as md_compute_forces would.  md_boo_particles waits and returns the last
+ * SAMPLED frame in particle-id order, whatever the handle did since (md_run, list rebuilds, md_upload): nnb[N], q[N],
+ * qbar[N], nconn[N] (any may be NULL).  md_boo_qlm waits and returns
+ * qlm[(i*NM + m)*2 + {0, 1}] = Re, Im of q_lm(i) of the last frame.  md_boo_read waits and returns nsamples, sum_fr[8],
+ * the four histograms and series[nseries*8] (rows past nsamples are zero; any pointer may be NULL).  md_boo_reset zeroes
+ * the sums, the histograms, the series and the count; it keeps the setup.  Refused: a slab-decomposition handle,
+ * r_neigh > list_cutoff, an argument out of range, any call before md_boo_setup, md_boo_particles or md_boo_qlm before
+ * the first sample.                                                                                                  */
+int md_boo_setup(md_ctx *ctx, double r_neigh, int order, int nbins, double threshold, int min_conn, int64_t nseries);
+int md_boo_sample(md_ctx *ctx);
+int md_boo_particles(md_ctx *ctx, int32_t *nnb, double *q, double *qbar, int32_t *nconn);
+int md_boo_qlm(md_ctx *ctx, double *qlm);
+int md_boo_read(md_ctx *ctx, int64_t *nsamples, double *sum_fr, int64_t *hist_q, int64_t *hist_qbar, int64_t *hist_nnb,
+                int64_t *hist_conn, double *series);
+int md_boo_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

@@ -28,6 +28,7 @@ EXPORTS = [
     "md_dyn_setup", "md_dyn_origin", "md_dyn_sample", "md_dyn_read", "md_dyn_reset",
     "md_sq_setup", "md_sq_sample", "md_sq_rho", "md_sq_read", "md_sq_reset",
     "md_stress_setup", "md_stress_sample", "md_stress_tensor", "md_stress_read", "md_stress_reset",
+    "md_boo_setup", "md_boo_sample", "md_boo_particles", "md_boo_qlm", "md_boo_read", "md_boo_reset",
 ]
 
 
@@ -174,6 +175,18 @@ def load():
     L.md_stress_read.restype = C.c_int
     L.md_stress_reset.argtypes = [vp]
     L.md_stress_reset.restype = C.c_int
+    L.md_boo_setup.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int64]
+    L.md_boo_setup.restype = C.c_int
+    L.md_boo_sample.argtypes = [vp]
+    L.md_boo_sample.restype = C.c_int
+    L.md_boo_particles.argtypes = [vp, ip, dp, dp, ip]
+    L.md_boo_particles.restype = C.c_int
+    L.md_boo_qlm.argtypes = [vp, dp]
+    L.md_boo_qlm.restype = C.c_int
+    L.md_boo_read.argtypes = [vp, i64p, dp, i64p, i64p, i64p, i64p, dp]
+    L.md_boo_read.restype = C.c_int
+    L.md_boo_reset.argtypes = [vp]
+    L.md_boo_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

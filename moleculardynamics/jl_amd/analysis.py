@@ -1,6 +1,7 @@
 """Structure and dynamics of a simulated configuration, sampled on the device: the radial distribution function g(r),
-the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes, S(q), coherent F(q, t)) and the stress
-(pressure tensor, stress autocorrelations, Green-Kubo viscosity).
+the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes, S(q), coherent F(q, t)), the stress
+(pressure tensor, stress autocorrelations, Green-Kubo viscosity) and the bond-orientational order (Steinhardt q_l, the
+neighbour-averaged qbar_l, psi_k in 2-D, the solid-particle count).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -817,3 +818,183 @@ def compute_stress(state, params):
     dev.stress_sample()
     kin, vir = dev.stress_tensor()
     return _tensor(kin, dev.dim), _tensor(vir, dev.dim)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Bond-orientational order: Steinhardt q_l(i) (l = 4, 6) and its neighbour-averaged form qbar_l(i) in 3-D, |psi_k(i)| in
+# 2-D, and ten Wolde's solid particles (at least min_connections neighbours with bond coherence s_ij > threshold), sampled
+# on the device (md_boo_*) from the positions and the neighbour rows the handle already holds.  The potential is never
+# evaluated: it works with every potential and every ensemble.
+
+_BOO_FR = ("sum_q", "sum_q2", "sum_qbar", "sum_qbar2", "sum_n", "sum_c", "n_solid", "global_order")
+
+
+class BondOrder:
+    """Local bond-orientational order, accumulated on the device until reset().
+
+    r_neigh: the neighbour radius (<= the list cutoff of the handle).  order: l (4 or 6) in 3-D, k (1..12) in 2-D.
+    Passed to run_simulation(..., bond_order=...), it takes a sample at every `every`-th output step; `nseries` rows of
+    the per-sample series are kept (default: one per sample of the run).
+
+    Fields: nsamples, sum_fr (the 8 frame sums added over the samples: sum q, q^2, qbar, qbar^2, n, c, solid particles,
+    global order), hist_q, hist_qbar (nbins bins over [0, 1]), hist_nnb, hist_conn (33 bins, clamped to 32), steps and
+    frames (the series: the step and the frame vector of each recorded sample)."""
+
+    def __init__(self, r_neigh, order=6, every=1, nbins=100, threshold=0.7, min_connections=7, nseries=None):
+        r_neigh, threshold = float(r_neigh), float(threshold)
+        if not (r_neigh > 0.0 and math.isfinite(r_neigh)):
+            raise ValueError("r_neigh must be finite and > 0")
+        if int(order) != order or not 1 <= int(order) <= 12:
+            raise ValueError("order must be 4 or 6 (3-D) or in 1..12 (2-D)")
+        if int(every) != every or int(every) < 1:
+            raise ValueError("every must be a positive integer")
+        if int(nbins) != nbins or not 1 <= int(nbins) <= 8192:
+            raise ValueError("nbins must be in 1..8192")
+        if not math.isfinite(threshold):
+            raise ValueError("threshold must be finite")
+        if int(min_connections) != min_connections or not 0 <= int(min_connections) <= 32:
+            raise ValueError("min_connections must be in 0..32")
+        if nseries is not None and (int(nseries) != nseries or not 0 <= int(nseries) <= 1 << 20):
+            raise ValueError("nseries must be in 0..1048576")
+        self.r_neigh, self.order, self.every, self.nbins = r_neigh, int(order), int(every), int(nbins)
+        self.threshold, self.min_connections = threshold, int(min_connections)
+        self.nseries = None if nseries is None else int(nseries)
+        self.edges = np.arange(self.nbins + 1, dtype=np.float64) / self.nbins
+        self.centres = 0.5 * (self.edges[:-1] + self.edges[1:])
+        self.n_particles = 0
+        self.reset()
+
+    def reset(self):
+        self.nsamples = 0
+        self.sum_fr = np.zeros(8)
+        self.hist_q = np.zeros(self.nbins, dtype=np.int64)
+        self.hist_qbar = np.zeros(self.nbins, dtype=np.int64)
+        self.hist_nnb = np.zeros(33, dtype=np.int64)
+        self.hist_conn = np.zeros(33, dtype=np.int64)
+        self.steps = np.zeros(0, dtype=np.int64)
+        self.frames = np.zeros((0, 8))
+
+    def schedule(self, total_steps, frequency):
+        """The steps of one run at which a sample is taken: the multiples of frequency * every below total_steps."""
+        return list(range(0, int(total_steps), int(frequency) * self.every))
+
+    def _accumulate(self, nsamples, sum_fr, hist_q, hist_qbar, hist_nnb, hist_conn, series, steps, n_particles):
+        if self.nsamples > 0 and int(n_particles) != self.n_particles:
+            raise ValueError("the number of particles differs from the one already accumulated; reset() first")
+        self.nsamples += int(nsamples)
+        self.sum_fr += np.asarray(sum_fr, dtype=np.float64).reshape(8)
+        self.hist_q += np.asarray(hist_q, dtype=np.int64).reshape(self.nbins)
+        self.hist_qbar += np.asarray(hist_qbar, dtype=np.int64).reshape(self.nbins)
+        self.hist_nnb += np.asarray(hist_nnb, dtype=np.int64).reshape(33)
+        self.hist_conn += np.asarray(hist_conn, dtype=np.int64).reshape(33)
+        series = np.asarray(series, dtype=np.float64).reshape(-1, 8)
+        steps = np.asarray(steps, dtype=np.int64)[: len(series)]
+        self.frames = np.concatenate([self.frames, series[: len(steps)]])
+        self.steps = np.concatenate([self.steps, steps])
+        self.n_particles = int(n_particles)
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    def _per_particle(self, k):
+        if self.nsamples == 0 or self.n_particles == 0:
+            raise ValueError("no sample yet")
+        return float(self.sum_fr[k]) / (self.nsamples * self.n_particles)
+
+    def mean_q(self):
+        """<q_l(i)> (2-D: <|psi_k(i)|>) over particles and samples."""
+        return self._per_particle(0)
+
+    def mean_qbar(self):
+        """<qbar_l(i)>, the neighbour-averaged invariant, over particles and samples."""
+        return self._per_particle(2)
+
+    def mean_neighbours(self):
+        return self._per_particle(4)
+
+    def solid_fraction(self):
+        """Fraction of particles with at least min_connections solid bonds, over the samples."""
+        return self._per_particle(6)
+
+    def global_order(self):
+        """The global order parameter (the invariant of the n_i-weighted mean of q_lm), averaged over the samples."""
+        if self.nsamples == 0:
+            raise ValueError("no sample yet")
+        return float(self.sum_fr[7]) / self.nsamples
+
+    def histogram(self, which="q"):
+        """(bin centres, density normalised to integral 1 over [0, 1], counts) of `which`: "q" or "qbar"; for "neighbours"
+        or "connections" the centres are 0..32 (the last bin holds everything above) and the density sums to 1."""
+        if which in ("q", "qbar"):
+            counts = self.hist_q if which == "q" else self.hist_qbar
+            tot = counts.sum()
+            dens = counts * (self.nbins / tot) if tot > 0 else np.zeros(self.nbins)
+            return self.centres.copy(), dens, counts.copy()
+        if which in ("neighbours", "connections"):
+            counts = self.hist_nnb if which == "neighbours" else self.hist_conn
+            tot = counts.sum()
+            return np.arange(33, dtype=np.float64), (counts / tot if tot > 0 else np.zeros(33)), counts.copy()
+        raise ValueError('which must be "q", "qbar", "neighbours" or "connections"')
+
+    def series(self):
+        """(steps, columns): per recorded sample, the step and <q>, <qbar>, <n>, solid fraction, global order."""
+        n = max(self.n_particles, 1)
+        f = self.frames
+        cols = np.stack([f[:, 0] / n, f[:, 2] / n, f[:, 4] / n, f[:, 6] / n, f[:, 7]], axis=1) if len(f) else np.zeros((0, 5))
+        return self.steps.copy(), cols
+
+    def write(self, path):
+        """A header with the means, then # bin q_density qbar_density count_q count_qbar, one row per bin."""
+        _, dq, cq = self.histogram("q")
+        _, db, cb = self.histogram("qbar")
+        with open(path, "w") as io:
+            io.write("# order %d r_neigh %.6f threshold %.6f min_connections %d nsamples %d\n"
+                     % (self.order, self.r_neigh, self.threshold, self.min_connections, self.nsamples))
+            io.write("# mean_q %.8f mean_qbar %.8f mean_neighbours %.6f solid_fraction %.8f global_order %.8f\n"
+                     % (self.mean_q(), self.mean_qbar(), self.mean_neighbours(), self.solid_fraction(),
+                        self.global_order()))
+            io.write("# bin q_density qbar_density count_q count_qbar\n")
+            for k in range(self.nbins):
+                io.write("%.6f %.6e %.6e %d %d\n" % (self.centres[k], dq[k], db[k], cq[k], cb[k]))
+
+    def write_series(self, path):
+        """# step <q> <qbar> <n> solid_fraction global_order, one row per recorded sample."""
+        steps, cols = self.series()
+        with open(path, "w") as io:
+            io.write("# step <q> <qbar> <n> solid_fraction global_order\n")
+            for s, c in zip(steps, cols):
+                io.write("%d %.8f %.8f %.6f %.8f %.8f\n" % ((int(s),) + tuple(c)))
+
+    # -- run_simulation's sampler protocol: a sample at every `every`-th output step ---------------------------------
+    def _begin(self, dev, run):
+        self._period, self._total_steps = run.frequency * self.every, run.total_steps
+        self._run_steps = self.schedule(run.total_steps, run.frequency)
+        ns = len(self._run_steps) if self.nseries is None else self.nseries
+        dev.boo_setup(self.r_neigh, self.order, self.nbins, self.threshold, self.min_connections, min(ns, 1 << 20))
+
+    def _next(self, step):
+        return _next_multiple(step, self._period, self._total_steps)
+
+    def _act(self, dev, step):
+        dev.boo_sample()
+
+    def _finish(self, dev, run, pathname):
+        ns, fr, hq, hb, hn, hc, series = dev.boo_read()
+        self._accumulate(ns, fr, hq, hb, hn, hc, series, self._run_steps[:ns], run.n)
+        if self.nsamples > 0:
+            self.write(os.path.join(pathname, "bond_order.txt"))
+            self.write_series(os.path.join(pathname, "bond_order_series.txt"))
+
+
+def compute_bond_order(state, params, r_neigh, order=6, threshold=0.7, min_connections=7):
+    """One sample of the bond-orientational order of `state`'s positions, taken on its device handle (any potential);
+    returns a dict of the per-particle arrays in particle order -- neighbours, q, qbar, connections, solid (bool), qlm
+    (complex, N x (l + 1) for m = 0..l; N x 1 in 2-D) -- and the scalar global_order."""
+    from .simulation import _configure_device
+    BondOrder(r_neigh, order=order, threshold=threshold, min_connections=min_connections)    # the argument checks
+    dev = _configure_device(state, params)
+    dev.upload(x=state.system.positions, images=state.images, diameters=state.diameters)
+    dev.boo_setup(r_neigh, order, 1, threshold, min_connections, 1)
+    dev.boo_sample()
+    nnb, q, qbar, nconn = dev.boo_particles()
+    _, fr, _, _, _, _, _ = dev.boo_read()
+    return dict(neighbours=nnb, q=q, qbar=qbar, connections=nconn, solid=nconn >= int(min_connections),
+                qlm=dev.boo_qlm(), global_order=float(fr[7]))

@@ -14,6 +14,7 @@
 #include "md_dyn.hpp"
 #include "md_sq.hpp"
 #include "md_stress.hpp"
+#include "md_boo.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -333,6 +334,23 @@ struct md_ctx {
         int64_t nsamples = 0;             // since setup / reset: the next sample's number m
         DBuf<double> part, last, sums, ring, corr; // 2 nc x nblk; 2 nc; 2 nc; nlags x nc; nlags x nc
     } stress;
+
+    // bond-orientational order (md_boo_*): per-slot q_lm (component-major), its norm, n_i, q, qbar and c_i of the last
+    // frame and that frame's slot -> particle-id permutation (the handle's own changes with every list build and upload);
+    // block partials; the running sums, the series; the four histograms in one buffer
+    struct Boo {
+        bool on = false;
+        bool sampled = false;             // the per-slot arrays and last hold a frame
+        int order = 6, nm = 7, nbins = 0, min_conn = 0;
+        double rn = 0.0, rn2 = 0.0, threshold = 0.0;
+        int64_t nseries = 0;
+        int64_t nsamples = 0;             // since setup / reset: the next sample's number m
+        BooCoef coef{};
+        DBuf<double> qlm, norm, q, qbar, part, sum_fr, series, io_d; // 2 nm x n; n; n; n; (7 + 2 nm) x nblk; 8; nseries x 8
+        DBuf<int32_t> nnb, nconn, ids, io_i;
+        DBuf<unsigned long long> hist;    // 2 nbins + 2 x 33
+        size_t nhist() const { return (size_t)2 * nbins + 2 * (MD_BOO_NCLAMP + 1); }
+    } boo;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1407,6 +1425,107 @@ void stress_zero(md_ctx *c)
     HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * std::max(S.nlags, 1) * nc, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     S.nsamples = 0;
+}
+
+// ---- bond-orientational order sampler (md_boo.hpp): launches -----------------------------------------------------
+// The sampler's LDS image has 32-byte records whatever the force kernel's stride is.  The rows address the force kernel's
+// image with 16-bit byte offsets, (H + 1) * stride <= 65535 for every tile (k_build_tile / k_tile_localize refuse a
+// larger halo), so (H + 1) * 32 <= 87360 bytes for a 24-byte handle and 65536 for a 32-byte one: it always fits below the
+// force kernel's limit (md_boo.hpp asserts the arithmetic) and a tiled handle never needs another walk.  The launch
+// checks the premise on the handle -- the offsets fit 16 bits -- and the conclusion, and refuses otherwise.
+inline size_t boo_image_bytes(int max_halo) { return (((size_t)max_halo + 1) * 32 + 15) & ~(size_t)15; }
+inline bool boo_image_fits(int max_halo) { return boo_image_bytes(max_halo) <= (size_t)MD_BOO_LDS_LIMIT; }
+
+template <int D, int L, int RS>
+void launch_boo_tile(md_ctx *c, const BooAvgArgs &A)
+{
+    md_ctx::Boo &B = c->boo;
+    int n = (int)c->n;
+    int nb = c->nblk;
+    DevState s = c->dev(c->cur);
+    static int attr_dev_mask = 0; // the attribute is per device: one bit per device id
+    auto k1 = k_boo_qlm_tile<D, L, RS>;
+    auto k2 = k_boo_avg_tile<D, L, RS>;
+    if (!(attr_dev_mask & (1 << (c->device & 31)))) {
+        HIPCHK(hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
+        HIPCHK(hipFuncSetAttribute((const void *)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
+        attr_dev_mask |= 1 << (c->device & 31);
+    }
+    if (((size_t)c->hstride + 1) * RS > MD_BOO_ROW_OFFSET_MAX || !boo_image_fits(c->hstride))
+        throw HipError("internal: the bond-order sampler's LDS image does not fit");
+    const size_t lds = boo_image_bytes(c->hstride);
+    k1<<<nb, MD_TILE, lds, c->stream>>>(n, s, B.rn2, B.order, B.coef, c->nlist16.p, c->maxn, c->nmax_tile.p, c->halo.p,
+                                        c->hcap, c->halo_count.p, c->gowner.p, A.cap, B.qlm.p, B.norm.p, B.nnb.p);
+    k2<<<nb, MD_TILE, lds, c->stream>>>(n, s, B.rn2, B.coef, c->nlist16.p, c->maxn, c->nmax_tile.p, c->halo.p, c->hcap,
+                                        c->halo_count.p, c->gowner.p, A);
+}
+
+template <int D, int L>
+void launch_boo(md_ctx *c)
+{
+    md_ctx::Boo &B = c->boo;
+    int n = (int)c->n;
+    int nb = c->nblk;
+    B.part.ensure((size_t)BooShape<D, L>::NPART * std::max(nb, 1));
+    BooAvgArgs A{};
+    A.threshold = B.threshold;
+    A.min_conn = B.min_conn;
+    A.nbins = B.nbins;
+    A.cap = n;
+    A.nblk = nb;
+    A.qlm = B.qlm.p;
+    A.norm = B.norm.p;
+    A.nnb = B.nnb.p;
+    A.q = B.q.p;
+    A.qbar = B.qbar.p;
+    A.nconn = B.nconn.p;
+    A.hist = B.hist.p;
+    A.partials = B.part.p;
+    if (c->use_tiles) {
+        if (c->tile_rs == 24)
+            launch_boo_tile<D, L, 24>(c, A);
+        else if (c->tile_rs == 32)
+            launch_boo_tile<D, L, 32>(c, A);
+        else
+            throw HipError("internal: bond-order sampler and tile rows disagree on the record stride");
+    } else {
+        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
+        DevState s = c->dev(c->cur);
+        k_boo_qlm<D, L><<<nb, MD_BLOCK, 0, c->stream>>>(n, s, B.rn2, B.order, B.coef, c->nlist.p, c->maxn, c->nmax_tile.p,
+                                                        c->gowner.p, A.cap, B.qlm.p, B.norm.p, B.nnb.p);
+        k_boo_avg<D, L><<<nb, MD_BLOCK, 0, c->stream>>>(n, s, B.rn2, B.coef, c->nlist.p, c->maxn, c->nmax_tile.p,
+                                                        c->gowner.p, A);
+    }
+    k_boo_finish<D, L><<<1, 1024, 0, c->stream>>>(nb, B.part.p, B.coef, (long long)B.nsamples, (long long)B.nseries,
+                                                  B.sum_fr.p, B.series.p);
+}
+
+// c_lm = (-1)^m sqrt((2l + 1)/(4 pi) (l - m)!/(l + m)!) and 4 pi/(2l + 1); 2-D: 1 and 1
+BooCoef boo_coef(int dim, int order)
+{
+    BooCoef bc{};
+    bc.pref = 1.0;
+    bc.coef[0] = 1.0;
+    if (dim == 2) return bc;
+    const double pi = 3.14159265358979323846;
+    const int l = order;
+    bc.pref = 4.0 * pi / (2 * l + 1);
+    for (int m = 0; m <= l; ++m) {
+        double ratio = 1.0; // (l - m)! / (l + m)!
+        for (int k = l - m + 1; k <= l + m; ++k) ratio /= (double)k;
+        bc.coef[m] = ((m & 1) ? -1.0 : 1.0) * std::sqrt((2 * l + 1) / (4.0 * pi) * ratio);
+    }
+    return bc;
+}
+
+void boo_zero(md_ctx *c)
+{
+    md_ctx::Boo &B = c->boo;
+    HIPCHK(hipMemsetAsync(B.sum_fr.p, 0, sizeof(double) * MD_BOO_NFR, c->stream));
+    HIPCHK(hipMemsetAsync(B.series.p, 0, sizeof(double) * MD_BOO_NFR * std::max<int64_t>(B.nseries, 1), c->stream));
+    HIPCHK(hipMemsetAsync(B.hist.p, 0, sizeof(unsigned long long) * B.nhist(), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    B.nsamples = 0;
 }
 
 } // namespace
@@ -2522,6 +2641,157 @@ int md_stress_reset(md_ctx *ctx)
     API_BEGIN
     sampler_of(ctx, &md_ctx::stress, "md_stress_reset", "stress");
     stress_zero(ctx);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Bond-orientational order (md_boo.hpp): a sample walks the OUTER rows as md_stress_sample does, never evaluates the
+// potential -- so it serves every potential, a user's included -- reads positions only and writes only the sampler's own
+// buffers.
+int md_boo_setup(md_ctx *ctx, double r_neigh, int order, int nbins, double threshold, int min_conn, int64_t nseries)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_boo_setup: not available on a slab-decomposition handle");
+    if (!(r_neigh > 0.0) || !std::isfinite(r_neigh)) throw HipError("md_boo_setup: r_neigh must be finite and > 0");
+    if (r_neigh > ctx->rc) {
+        char b[256];
+        snprintf(b, sizeof b, "md_boo_setup: r_neigh = %.17g exceeds the list cutoff %.17g (the rows are complete only up to it)",
+                 r_neigh, ctx->rc);
+        throw HipError(b);
+    }
+    if (ctx->dim == 3) {
+        if (order != 4 && order != 6) throw HipError("md_boo_setup: order (l) must be 4 or 6 in 3-D");
+    } else {
+        check_range("md_boo_setup", "order (k)", order, 1, 12);
+    }
+    check_range("md_boo_setup", "nbins", nbins, 1, MD_BOO_MAX_BINS);
+    check_range("md_boo_setup", "min_conn", min_conn, 0, MD_BOO_NCLAMP);
+    if (!std::isfinite(threshold)) throw HipError("md_boo_setup: threshold must be finite");
+    if (nseries < 0 || nseries > MD_BOO_MAX_SERIES) throw HipError("md_boo_setup: nseries must be in 0..1048576");
+    md_ctx::Boo &B = ctx->boo;
+    B.on = false;
+    B.sampled = false;
+    B.order = order;
+    B.nm = ctx->dim == 3 ? order + 1 : 1;
+    B.nbins = nbins;
+    B.min_conn = min_conn;
+    B.threshold = threshold;
+    B.rn = r_neigh;
+    B.rn2 = r_neigh * r_neigh;
+    B.nseries = nseries;
+    B.coef = boo_coef(ctx->dim, order);
+    const size_t n = (size_t)ctx->n;
+    B.qlm.alloc(2 * (size_t)B.nm * n);
+    B.norm.alloc(n);
+    B.q.alloc(n);
+    B.qbar.alloc(n);
+    B.nnb.alloc(n);
+    B.nconn.alloc(n);
+    B.part.alloc((size_t)(7 + 2 * B.nm) * std::max(nblocks(ctx->n), 1));
+    B.sum_fr.alloc(MD_BOO_NFR);
+    B.series.alloc((size_t)MD_BOO_NFR * std::max<int64_t>(nseries, 1));
+    B.hist.alloc(B.nhist());
+    B.ids.alloc(n);
+    boo_zero(ctx);
+    B.on = true;
+    API_END
+}
+
+int md_boo_sample(md_ctx *ctx)
+{
+    API_BEGIN
+    require_state(ctx, "md_boo_sample");
+    md_ctx::Boo &B = sampler_of(ctx, &md_ctx::boo, "md_boo_sample", "boo");
+    if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
+    if (ctx->dim == 3) {
+        if (B.order == 4)
+            launch_boo<3, 4>(ctx);
+        else
+            launch_boo<3, 6>(ctx);
+    } else {
+        launch_boo<2, 0>(ctx);
+    }
+    HIPCHK(hipGetLastError());
+    // the frame's own permutation: the next list build or upload re-sorts the handle's slots, the per-slot arrays stay
+    HIPCHK(hipMemcpyAsync(B.ids.p, ctx->dev(ctx->cur).id, sizeof(int32_t) * (size_t)ctx->n, hipMemcpyDeviceToDevice,
+                          ctx->stream));
+    ++B.nsamples;
+    B.sampled = true;
+    API_END
+}
+
+// the last frame's per-slot arrays in particle-id order, into the sampler's staging buffers
+static void boo_export(md_ctx *ctx, bool want_qlm)
+{
+    md_ctx::Boo &B = ctx->boo;
+    const size_t n = (size_t)ctx->n;
+    if (want_qlm) {
+        B.io_d.ensure(2 * (size_t)B.nm * n);
+        k_boo_export<<<nblocks(ctx->n), MD_BLOCK, 0, ctx->stream>>>((int)n, B.ids.p, (int)n, B.nm, nullptr, nullptr, nullptr, nullptr,
+                                                              B.qlm.p, nullptr, nullptr, nullptr, nullptr, B.io_d.p);
+    } else {
+        B.io_d.ensure(2 * n);
+        B.io_i.ensure(2 * n);
+        k_boo_export<<<nblocks(ctx->n), MD_BLOCK, 0, ctx->stream>>>((int)n, B.ids.p, (int)n, B.nm, B.nnb.p, B.q.p, B.qbar.p, B.nconn.p,
+                                                              nullptr, B.io_i.p, B.io_d.p, B.io_d.p + n, B.io_i.p + n, nullptr);
+    }
+    HIPCHK(hipGetLastError());
+}
+
+int md_boo_particles(md_ctx *ctx, int32_t *nnb, double *q, double *qbar, int32_t *nconn)
+{
+    API_BEGIN
+    md_ctx::Boo &B = sampler_of(ctx, &md_ctx::boo, "md_boo_particles", "boo");
+    if (!B.sampled) throw HipError("md_boo_particles: no frame sampled yet (call md_boo_sample first)");
+    const size_t n = (size_t)ctx->n;
+    boo_export(ctx, false);
+    hipStream_t st = ctx->stream;
+    if (nnb) HIPCHK(hipMemcpyAsync(nnb, B.io_i.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (nconn) HIPCHK(hipMemcpyAsync(nconn, B.io_i.p + n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (q) HIPCHK(hipMemcpyAsync(q, B.io_d.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (qbar) HIPCHK(hipMemcpyAsync(qbar, B.io_d.p + n, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_boo_qlm(md_ctx *ctx, double *qlm)
+{
+    API_BEGIN
+    md_ctx::Boo &B = sampler_of(ctx, &md_ctx::boo, "md_boo_qlm", "boo");
+    if (!B.sampled) throw HipError("md_boo_qlm: no frame sampled yet (call md_boo_sample first)");
+    if (!qlm) throw HipError("md_boo_qlm: qlm is null");
+    boo_export(ctx, true);
+    HIPCHK(hipMemcpyAsync(qlm, B.io_d.p, sizeof(double) * 2 * (size_t)B.nm * (size_t)ctx->n, hipMemcpyDeviceToHost,
+                          ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    API_END
+}
+
+int md_boo_read(md_ctx *ctx, int64_t *nsamples, double *sum_fr, int64_t *hist_q, int64_t *hist_qbar, int64_t *hist_nnb,
+                int64_t *hist_conn, double *series)
+{
+    API_BEGIN
+    md_ctx::Boo &B = sampler_of(ctx, &md_ctx::boo, "md_boo_read", "boo");
+    hipStream_t st = ctx->stream;
+    const size_t nb = (size_t)B.nbins, ns = MD_BOO_NCLAMP + 1, w = sizeof(unsigned long long);
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "histogram words are read back as int64_t");
+    if (sum_fr) HIPCHK(hipMemcpyAsync(sum_fr, B.sum_fr.p, sizeof(double) * MD_BOO_NFR, hipMemcpyDeviceToHost, st));
+    if (hist_q) HIPCHK(hipMemcpyAsync(hist_q, B.hist.p, w * nb, hipMemcpyDeviceToHost, st));
+    if (hist_qbar) HIPCHK(hipMemcpyAsync(hist_qbar, B.hist.p + nb, w * nb, hipMemcpyDeviceToHost, st));
+    if (hist_nnb) HIPCHK(hipMemcpyAsync(hist_nnb, B.hist.p + 2 * nb, w * ns, hipMemcpyDeviceToHost, st));
+    if (hist_conn) HIPCHK(hipMemcpyAsync(hist_conn, B.hist.p + 2 * nb + ns, w * ns, hipMemcpyDeviceToHost, st));
+    if (series && B.nseries > 0)
+        HIPCHK(hipMemcpyAsync(series, B.series.p, sizeof(double) * MD_BOO_NFR * (size_t)B.nseries, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nsamples) *nsamples = B.nsamples;
+    API_END
+}
+
+int md_boo_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    sampler_of(ctx, &md_ctx::boo, "md_boo_reset", "boo");
+    boo_zero(ctx);
     API_END
 }
 

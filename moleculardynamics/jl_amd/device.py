@@ -300,6 +300,51 @@ class MDDevice:
     def stress_reset(self):
         self._chk(self._L.md_stress_reset(self._h))
 
+    # -- bond-orientational order ---------------------------------------------------------
+    def boo_setup(self, r_neigh, order=6, nbins=100, threshold=0.7, min_conn=7, nseries=0):
+        """Allocate the device bond-order sampler (md_boo_setup): neighbours within r_neigh <= list cutoff, order = l (4 or
+        6) in 3-D or k (1..12) in 2-D, nbins histogram bins over [0, 1], the solid-bond threshold on s_ij, the number of
+        solid bonds that makes a particle solid, and nseries rows of the per-sample series; all zeroed."""
+        self._chk(self._L.md_boo_setup(self._h, float(r_neigh), int(order), int(nbins), float(threshold), int(min_conn),
+                                       int(nseries)))
+        self._boo_shape = (int(order) + 1 if self.dim == 3 else 1, int(nbins), int(nseries))
+
+    def boo_sample(self):
+        """Add one sample of the current positions (does not wait, changes nothing the handle computes afterwards)."""
+        self._chk(self._L.md_boo_sample(self._h))
+
+    def boo_particles(self):
+        """(nnb int32[N], q float64[N], qbar float64[N], nconn int32[N]) of the last sampled frame, in particle-id order;
+        waits."""
+        nnb, nconn = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        q, qbar = np.zeros(self.n), np.zeros(self.n)
+        self._chk(self._L.md_boo_particles(self._h, _ip(nnb), _dp(q), _dp(qbar), _ip(nconn)))
+        return nnb, q, qbar, nconn
+
+    def boo_qlm(self):
+        """q_lm of the last sampled frame, complex128[N, NM] for m = 0..NM-1 (3-D: NM = l + 1; 2-D: NM = 1, psi_k); waits."""
+        nm = getattr(self, "_boo_shape", (1, 0, 0))[0]
+        out = np.zeros((self.n, nm, 2))
+        self._chk(self._L.md_boo_qlm(self._h, _dp(out)))
+        return out.view(np.complex128).reshape(self.n, nm)
+
+    def boo_read(self):
+        """(nsamples, sum_fr float64[8], hist_q int64[nbins], hist_qbar int64[nbins], hist_nnb int64[33], hist_conn int64[33],
+        series float64[min(nsamples, nseries), 8]), accumulated since setup / reset; waits."""
+        _, nbins, nseries = getattr(self, "_boo_shape", (1, 0, 0))
+        ns = C.c_int64()
+        fr = np.zeros(8)
+        hq, hb = np.zeros(max(nbins, 1), dtype=np.int64), np.zeros(max(nbins, 1), dtype=np.int64)
+        hn, hc = np.zeros(33, dtype=np.int64), np.zeros(33, dtype=np.int64)
+        series = np.zeros((max(nseries, 1), 8))
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.md_boo_read(self._h, C.byref(ns), _dp(fr), hq.ctypes.data_as(i64), hb.ctypes.data_as(i64),
+                                      hn.ctypes.data_as(i64), hc.ctypes.data_as(i64), _dp(series)))
+        return ns.value, fr, hq[:nbins], hb[:nbins], hn, hc, series[: min(ns.value, nseries)]
+
+    def boo_reset(self):
+        self._chk(self._L.md_boo_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

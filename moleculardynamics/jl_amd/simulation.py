@@ -36,7 +36,7 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, sq=None, stress=None):
+                   dynamics=None, sq=None, stress=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -58,7 +58,13 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     the device, at every step that is a multiple of stress.every (the stops are added to the loop's output steps; the step
     counter and the ring of past samples restart in every call, the sums accumulate in the object).  Written to
     pathname/stress.txt and, with nlags > 0, pathname/stress_acf.txt.  Not available with Brownian dynamics (no velocities)
-    or a user potential.  Nothing else the run produces changes."""
+    or a user potential.  Nothing else the run produces changes.
+
+    bond_order: a BondOrder (analysis.py) to sample the local bond-orientational order into (Steinhardt q_l and qbar_l in
+    3-D, psi_k in 2-D, the solid-particle count), on the device, at every bond_order.every-th output step, as rdf does.
+    Written to pathname/bond_order.txt (the means and the q / qbar histograms) and pathname/bond_order_series.txt (one row
+    per sample).  It never evaluates the potential: it works with Brownian dynamics and with user potentials.  Nothing else
+    the run produces changes."""
     brownian = isinstance(ensemble, Brownian)
     os.makedirs(pathname, exist_ok=True)
     trajectory_file, thermo_file = _io.open_files(pathname, traj_name, thermo_name)
@@ -79,7 +85,7 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     # the virial is sampled every 10th step and averaged at the output steps (:253-266)
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
     # the samplers (analysis.py's protocol), in the order their device calls are made at a step they share
-    samplers = [s for s in (rdf, dynamics, sq, stress) if s is not None]
+    samplers = [s for s in (rdf, dynamics, sq, stress, bond_order) if s is not None]
     run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
                                 unitcell=state.unitcell, brownian=brownian)
     for s in samplers:
