@@ -316,6 +316,51 @@ int md_boo_read(md_ctx *ctx, int64_t *nsamples, double *sum_fr, int64_t *hist_q,
                 int64_t *hist_conn, double *series);
 int md_boo_reset(md_ctx *ctx);
 
+/* Clusters, sampled on the device (new relative to the reference): the connected components of the bond graph over the
+ * member particles -- every particle's cluster, the cluster-size histogram, the largest cluster n_max (with
+ * MD_CLUSTER_SOLID ten Wolde, Ruiz-Montero and Frenkel's largest solid cluster).  The potential is never evaluated.
+ *
+ * Members.  MD_CLUSTER_ALL: every particle.  MD_CLUSTER_SOLID: particle id p is a member iff nconn(p) >= min_conn in the
+ * last frame md_boo_sample took; membership is carried by particle id, so what the handle did between the two samples
+ * (md_run, list rebuilds) does not matter.  Take both samples at the same step to get ten Wolde's cluster.
+ *
+ * Bonds.  Members a != b are bonded iff d2 < rb2, with del = x_b(+periodic translation) - x_a as the force kernels form
+ * it, d2 = (del0*del0 + del1*del1) + del2*del2 (no fma) and rb2 = r_bond*r_bond rounded once on the host;
+ * 0 < r_bond <= list_cutoff (the rows are complete only up to list_cutoff).  A periodic image of a particle is that
+ * particle; an image of the particle itself is ignored.  Clusters are the connected components; a cluster that reaches
+ * its own periodic image is one cluster (spanning is not detected).
+ *
+ * Per particle, of the last sampled frame: label[p] = the smallest particle id in p's cluster, size[p] = that cluster's
+ * size; a non-member has label -1 and size 0.
+ *
+ * The frame vector fr[8], all int64: 0 members; 1 clusters; 2 the largest cluster's size; 3 the second-largest's (equal to
+ * the largest on a tie, 0 if there is one cluster or none); 4 the sum over members of the degree (directed bonds);
+ * 5 sum over clusters of size^2; 6 the label of the largest cluster (the smallest label among ties, -1 if there is no
+ * member); 7 clusters of size 1.  Every entry is an integer and a function of the frame alone: the same bits for any
+ * handle history, row order or slot order.
+ *
+ * Accumulated on the device since setup or the last reset: sum_fr[8] += fr (the sum of entry 6 has no meaning) and
+ * nsamples; hist_size[max_size+1]: += 1 at index min(size, max_size) for every cluster (entry 0 stays 0, the last entry
+ * also holds everything larger); sample number m < nseries also writes fr into series[m*8 .. m*8+8).
+ *
+ * md_cluster_setup: members = MD_CLUSTER_ALL or MD_CLUSTER_SOLID; 1 <= max_size <= 65536; 0 <= nseries <= 2^20;
+ * everything zeroed; calling it again starts over.  md_cluster_sample does not wait and changes nothing the handle
+ * computes afterwards: it writes only the sampler's own buffers; if the neighbour list is not valid it builds it exactly
+ * as md_boo_sample does.  md_cluster_particles waits and returns the last SAMPLED frame in particle-id order, whatever
+ * the handle did since (md_run, list rebuilds, md_upload): label[N], size[N] (either may be NULL).  md_cluster_read waits
+ * and returns nsamples, sum_fr[8], hist_size[max_size+1] and series[nseries*8] (rows past nsamples are zero; any pointer
+ * may be NULL).  md_cluster_reset zeroes the sums, the histogram, the series and the count; it keeps the setup.
+ * Refused: a slab-decomposition handle, r_bond out of range, an unknown `members`, an argument out of range, any call
+ * before md_cluster_setup, md_cluster_particles before the first sample; with MD_CLUSTER_SOLID md_cluster_setup before
+ * md_boo_setup and md_cluster_sample before the first md_boo_sample.                                                   */
+#define MD_CLUSTER_ALL   0
+#define MD_CLUSTER_SOLID 1
+int md_cluster_setup(md_ctx *ctx, double r_bond, int members, int max_size, int64_t nseries);
+int md_cluster_sample(md_ctx *ctx);
+int md_cluster_particles(md_ctx *ctx, int32_t *label, int32_t *size);
+int md_cluster_read(md_ctx *ctx, int64_t *nsamples, int64_t *sum_fr, int64_t *hist_size, int64_t *series);
+int md_cluster_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

@@ -9,7 +9,8 @@ from .initialization import (initialize_state, initialize_velocities, lattice_po
                              SimulationState, EnergyAndForces)
 from .simulation import run_simulation
 from .analysis import (RadialDistribution, compute_rdf, SelfDynamics, StructureFactor, compute_sq, select_wave_vectors,
-                       StressTensor, compute_stress, BondOrder, compute_bond_order)
+                       StressTensor, compute_stress, BondOrder, compute_bond_order, ClusterAnalysis,
+                       compute_clusters)
 from .minimize import fire_minimize, minimize
 from .device import MDDevice
 from ._lib import MdhipError
@@ -20,5 +21,5 @@ __all__ = [
     "initialize_velocities", "Potential", "evaluate", "MDDevice", "MdhipError", "lattice_positions",
     "fire_minimize", "minimize", "LennardJonesShifted", "LennardJonesForceShifted", "LennardJonesXPLOR",
     "RadialDistribution", "compute_rdf", "SelfDynamics", "StructureFactor", "compute_sq", "select_wave_vectors",
-    "StressTensor", "compute_stress", "BondOrder", "compute_bond_order",
+    "StressTensor", "compute_stress", "BondOrder", "compute_bond_order", "ClusterAnalysis", "compute_clusters",
 ]

@@ -11,6 +11,7 @@ SO_PATH = os.path.join(_HERE, "csrc", "libmdhip.so")
 
 MD_POT_LJ, MD_POT_PSEUDOHS, MD_POT_POLYDISPERSE, MD_POT_LJ_MODIFIED, MD_POT_CUSTOM = 0, 1, 2, 3, 100
 MD_NVE, MD_NVT = 0, 1
+MD_CLUSTER_ALL, MD_CLUSTER_SOLID = 0, 1
 
 # every symbol include/mdhip.h declares
 EXPORTS = [
@@ -29,6 +30,7 @@ EXPORTS = [
     "md_sq_setup", "md_sq_sample", "md_sq_rho", "md_sq_read", "md_sq_reset",
     "md_stress_setup", "md_stress_sample", "md_stress_tensor", "md_stress_read", "md_stress_reset",
     "md_boo_setup", "md_boo_sample", "md_boo_particles", "md_boo_qlm", "md_boo_read", "md_boo_reset",
+    "md_cluster_setup", "md_cluster_sample", "md_cluster_particles", "md_cluster_read", "md_cluster_reset",
 ]
 
 
@@ -187,6 +189,16 @@ def load():
     L.md_boo_read.restype = C.c_int
     L.md_boo_reset.argtypes = [vp]
     L.md_boo_reset.restype = C.c_int
+    L.md_cluster_setup.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int64]
+    L.md_cluster_setup.restype = C.c_int
+    L.md_cluster_sample.argtypes = [vp]
+    L.md_cluster_sample.restype = C.c_int
+    L.md_cluster_particles.argtypes = [vp, ip, ip]
+    L.md_cluster_particles.restype = C.c_int
+    L.md_cluster_read.argtypes = [vp, i64p, i64p, i64p, i64p]
+    L.md_cluster_read.restype = C.c_int
+    L.md_cluster_reset.argtypes = [vp]
+    L.md_cluster_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -1,7 +1,8 @@
 """Structure and dynamics of a simulated configuration, sampled on the device: the radial distribution function g(r),
 the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes, S(q), coherent F(q, t)), the stress
-(pressure tensor, stress autocorrelations, Green-Kubo viscosity) and the bond-orientational order (Steinhardt q_l, the
-neighbour-averaged qbar_l, psi_k in 2-D, the solid-particle count).
+(pressure tensor, stress autocorrelations, Green-Kubo viscosity), the bond-orientational order (Steinhardt q_l, the
+neighbour-averaged qbar_l, psi_k in 2-D, the solid-particle count) and the clusters (connected components of the bond
+graph: sizes, the size distribution, the largest -- solid -- cluster).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -998,3 +999,159 @@ def compute_bond_order(state, params, r_neigh, order=6, threshold=0.7, min_conne
     _, fr, _, _, _, _, _ = dev.boo_read()
     return dict(neighbours=nnb, q=q, qbar=qbar, connections=nconn, solid=nconn >= int(min_connections),
                 qlm=dev.boo_qlm(), global_order=float(fr[7]))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Clusters: the connected components of the bond graph (two members closer than r_bond are bonded), sampled on the
+# device (md_cluster_*) from the positions and the neighbour rows the handle already holds.  members="all": every
+# particle (droplets, gels: the size distribution n(s), the weight-average size).  members="solid": the solid particles of
+# the bond-order sampler's frame of the same step -- the largest one is ten Wolde, Ruiz-Montero and Frenkel's n_max.
+# Everything is an integer and a function of the frame alone.
+
+_CLUSTER_FR = ("members", "clusters", "largest", "second_largest", "directed_bonds", "sum_size2", "largest_label",
+               "singletons")
+_CLUSTER_MEMBERS = {"all": 0, "solid": 1}
+
+
+class ClusterAnalysis:
+    """Cluster statistics, accumulated on the device until reset().
+
+    r_bond: the bond length (<= the list cutoff of the handle).  members: "all" or "solid" (then run_simulation needs a
+    bond_order= as well, sampled at the same steps).  Passed to run_simulation(..., clusters=...), it takes a sample at
+    every `every`-th output step; clusters larger than max_size are counted in the histogram's last entry; `nseries` rows
+    of the per-sample series are kept (default: one per sample of the run).
+
+    Fields: nsamples, sum_fr (the 8 frame entries added over the samples: members, clusters, largest, second largest,
+    directed bonds, sum of size^2, the label of the largest -- whose sum means nothing -- and size-1 clusters), hist_size
+    (max_size + 1 counts of clusters by size), steps and frames (the series: the step and the frame vector of each
+    recorded sample)."""
+
+    def __init__(self, r_bond, members="all", every=1, max_size=1024, nseries=None):
+        r_bond = float(r_bond)
+        if not (r_bond > 0.0 and math.isfinite(r_bond)):
+            raise ValueError("r_bond must be finite and > 0")
+        if members not in _CLUSTER_MEMBERS:
+            raise ValueError('members must be "all" or "solid"')
+        if int(every) != every or int(every) < 1:
+            raise ValueError("every must be a positive integer")
+        if int(max_size) != max_size or not 1 <= int(max_size) <= 65536:
+            raise ValueError("max_size must be in 1..65536")
+        if nseries is not None and (int(nseries) != nseries or not 0 <= int(nseries) <= 1 << 20):
+            raise ValueError("nseries must be in 0..1048576")
+        self.r_bond, self.members, self.every, self.max_size = r_bond, members, int(every), int(max_size)
+        self.nseries = None if nseries is None else int(nseries)
+        self.reset()
+
+    def reset(self):
+        self.nsamples = 0
+        self.sum_fr = np.zeros(8, dtype=np.int64)
+        self.hist_size = np.zeros(self.max_size + 1, dtype=np.int64)
+        self.steps = np.zeros(0, dtype=np.int64)
+        self.frames = np.zeros((0, 8), dtype=np.int64)
+
+    def schedule(self, total_steps, frequency):
+        """The steps of one run at which a sample is taken: the multiples of frequency * every below total_steps."""
+        return list(range(0, int(total_steps), int(frequency) * self.every))
+
+    def _accumulate(self, nsamples, sum_fr, hist_size, series, steps):
+        self.nsamples += int(nsamples)
+        self.sum_fr += np.asarray(sum_fr, dtype=np.int64).reshape(8)
+        self.hist_size += np.asarray(hist_size, dtype=np.int64).reshape(self.max_size + 1)
+        series = np.asarray(series, dtype=np.int64).reshape(-1, 8)
+        steps = np.asarray(steps, dtype=np.int64)[: len(series)]
+        self.frames = np.concatenate([self.frames, series[: len(steps)]])
+        self.steps = np.concatenate([self.steps, steps])
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    def _mean(self, k):
+        if self.nsamples == 0:
+            raise ValueError("no sample yet")
+        return float(self.sum_fr[k]) / self.nsamples
+
+    def mean_largest(self):
+        """<n_max>: the size of the largest cluster, averaged over the samples."""
+        return self._mean(2)
+
+    def mean_clusters(self):
+        """The number of clusters, averaged over the samples."""
+        return self._mean(1)
+
+    def mean_members(self):
+        return self._mean(0)
+
+    def weight_average_size(self):
+        """sum_s s^2 n(s) / sum_s s n(s) over all samples (0 when there was no member)."""
+        if self.nsamples == 0:
+            raise ValueError("no sample yet")
+        return float(self.sum_fr[5]) / float(self.sum_fr[0]) if self.sum_fr[0] > 0 else 0.0
+
+    def size_distribution(self):
+        """(s, n(s)): the sizes 0..max_size and the number of clusters of that size per sample; the last entry also holds
+        every larger cluster, entry 0 is 0."""
+        if self.nsamples == 0:
+            raise ValueError("no sample yet")
+        return np.arange(self.max_size + 1, dtype=np.int64), self.hist_size / float(self.nsamples)
+
+    def series(self):
+        """(steps, frames): per recorded sample, the step and the eight frame entries (int64)."""
+        return self.steps.copy(), self.frames.copy()
+
+    def write(self, path):
+        """A header with the means, then # s n(s), one row per size 1..max_size (the last row holds everything larger)."""
+        s, ns = self.size_distribution()
+        with open(path, "w") as io:
+            io.write("# members %s r_bond %.6f max_size %d nsamples %d\n"
+                     % (self.members, self.r_bond, self.max_size, self.nsamples))
+            io.write("# mean_members %.6f mean_clusters %.6f mean_largest %.6f weight_average_size %.6f\n"
+                     % (self.mean_members(), self.mean_clusters(), self.mean_largest(), self.weight_average_size()))
+            io.write("# s n(s)\n")
+            for k in range(1, self.max_size + 1):
+                io.write("%d %.6e\n" % (s[k], ns[k]))
+
+    def write_series(self, path):
+        """# step and the eight frame entries, one row per recorded sample."""
+        with open(path, "w") as io:
+            io.write("# step " + " ".join(_CLUSTER_FR) + "\n")
+            for s, f in zip(self.steps, self.frames):
+                io.write("%d %s\n" % (int(s), " ".join("%d" % int(v) for v in f)))
+
+    # -- run_simulation's sampler protocol: a sample at every `every`-th output step ---------------------------------
+    def _begin(self, dev, run):
+        self._period, self._total_steps = run.frequency * self.every, run.total_steps
+        self._run_steps = self.schedule(run.total_steps, run.frequency)
+        ns = len(self._run_steps) if self.nseries is None else self.nseries
+        dev.cluster_setup(self.r_bond, _CLUSTER_MEMBERS[self.members], self.max_size, min(ns, 1 << 20))
+
+    def _next(self, step):
+        return _next_multiple(step, self._period, self._total_steps)
+
+    def _act(self, dev, step):
+        dev.cluster_sample()
+
+    def _finish(self, dev, run, pathname):
+        ns, fr, hist, series = dev.cluster_read()
+        self._accumulate(ns, fr, hist, series, self._run_steps[:ns])
+        if self.nsamples > 0:
+            self.write(os.path.join(pathname, "clusters.txt"))
+            self.write_series(os.path.join(pathname, "clusters_series.txt"))
+
+
+def compute_clusters(state, params, r_bond, members="all", bond_order=None):
+    """One sample of the clusters of `state`'s positions, taken on its device handle (any potential); returns (labels,
+    sizes, fr): per particle the smallest particle id of its cluster and the cluster's size (-1 and 0 for a non-member), and
+    the frame vector (int64[8]: members, clusters, largest, second largest, directed bonds, sum of size^2, the label of the
+    largest, size-1 clusters).  members="solid" needs a BondOrder (bond_order=): it is sampled first, on the same frame."""
+    from .simulation import _configure_device
+    ClusterAnalysis(r_bond, members=members)                # the argument checks
+    if members == "solid" and not isinstance(bond_order, BondOrder):
+        raise ValueError('members="solid" needs bond_order=BondOrder(...)')
+    dev = _configure_device(state, params)
+    dev.upload(x=state.system.positions, images=state.images, diameters=state.diameters)
+    if members == "solid":
+        dev.boo_setup(bond_order.r_neigh, bond_order.order, 1, bond_order.threshold, bond_order.min_connections, 0)
+        dev.boo_sample()
+    dev.cluster_setup(r_bond, _CLUSTER_MEMBERS[members], 1, 1)
+    dev.cluster_sample()
+    labels, sizes = dev.cluster_particles()
+    _, fr, _, _ = dev.cluster_read()
+    return labels, sizes, fr

@@ -15,6 +15,7 @@
 #include "md_sq.hpp"
 #include "md_stress.hpp"
 #include "md_boo.hpp"
+#include "md_cluster.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -351,6 +352,23 @@ struct md_ctx {
         DBuf<unsigned long long> hist;    // 2 nbins + 2 x 33
         size_t nhist() const { return (size_t)2 * nbins + 2 * (MD_BOO_NCLAMP + 1); }
     } boo;
+
+    // clusters (md_cluster_*): the union-find forest, the per-slot member flag, root, and per-root size and smallest id of
+    // the last frame with that frame's slot -> particle-id permutation; the by-id solid mask; block partials; the running
+    // sums, the series and the size histogram -- all integers
+    struct Cluster {
+        bool on = false;
+        bool sampled = false;             // root / count / minid / ids hold a frame
+        int members = 0, max_size = 0;
+        double rb = 0.0, rb2 = 0.0;
+        int64_t nseries = 0;
+        int64_t nsamples = 0;             // since setup / reset: the next sample's number m
+        DBuf<uint32_t> parent, root;      // n; n
+        DBuf<int32_t> count, minid, ids, io_i; // n; n; n; 2 n
+        DBuf<unsigned char> mem, mask;    // n (by slot); n (by particle id, SOLID only)
+        DBuf<unsigned long long> part, deg, hist; // 6 x nblk (256-slot blocks); the hook kernel's blocks; max_size + 1
+        DBuf<long long> sum_fr, series;   // 8; nseries x 8
+    } cluster;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1526,6 +1544,66 @@ void boo_zero(md_ctx *c)
     HIPCHK(hipMemsetAsync(B.hist.p, 0, sizeof(unsigned long long) * B.nhist(), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     B.nsamples = 0;
+}
+
+// ---- cluster sampler (md_cluster.hpp): launches -------------------------------------------------------------------
+// The hooks take BOO pass 1's dispatch: dimension, record stride, tiles or 32-bit rows, the same LDS image and the same
+// check of it.
+template <int D, int RS>
+void launch_cl_hook_tile(md_ctx *c)
+{
+    md_ctx::Cluster &C = c->cluster;
+    static int attr_dev_mask = 0; // the attribute is per device: one bit per device id
+    auto k1 = k_cl_hook_tile<D, RS>;
+    if (!(attr_dev_mask & (1 << (c->device & 31)))) {
+        HIPCHK(hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
+        attr_dev_mask |= 1 << (c->device & 31);
+    }
+    if (((size_t)c->hstride + 1) * RS > MD_BOO_ROW_OFFSET_MAX || !boo_image_fits(c->hstride))
+        throw HipError("internal: the cluster sampler's LDS image does not fit");
+    k1<<<c->nblk, MD_TILE, boo_image_bytes(c->hstride), c->stream>>>((int)c->n, c->dev(c->cur), C.rb2, c->nlist16.p, c->maxn,
+                                                                     c->nmax_tile.p, c->halo.p, c->hcap, c->halo_count.p,
+                                                                     c->gowner.p, C.mem.p, C.parent.p, C.deg.p);
+}
+
+template <int D>
+void launch_cluster(md_ctx *c)
+{
+    md_ctx::Cluster &C = c->cluster;
+    md_ctx::Boo &B = c->boo;
+    const int n = (int)c->n, nb = nblocks(c->n), nh = c->nblk;
+    hipStream_t st = c->stream;
+    DevState s = c->dev(c->cur);
+    C.deg.ensure((size_t)std::max(nh, 1));
+    const bool solid = C.members == MD_CLUSTER_SOLID;
+    if (solid) k_cl_mask<<<nb, MD_BLOCK, 0, st>>>(n, B.ids.p, B.nconn.p, B.min_conn, C.mask.p);
+    k_cl_init<<<nb, MD_BLOCK, 0, st>>>(n, s.id, solid ? C.mask.p : nullptr, C.parent.p, C.mem.p, C.count.p, C.minid.p);
+    if (c->use_tiles) {
+        if (c->tile_rs == 24)
+            launch_cl_hook_tile<D, 24>(c);
+        else if (c->tile_rs == 32)
+            launch_cl_hook_tile<D, 32>(c);
+        else
+            throw HipError("internal: cluster sampler and tile rows disagree on the record stride");
+    } else {
+        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
+        k_cl_hook<D><<<nh, MD_BLOCK, 0, st>>>(n, s, C.rb2, c->nlist.p, c->maxn, c->nmax_tile.p, c->gowner.p, C.mem.p, C.parent.p,
+                                              C.deg.p);
+    }
+    k_cl_flatten<<<nb, MD_BLOCK, 0, st>>>(n, s.id, C.parent.p, C.root.p, C.count.p, C.minid.p);
+    k_cl_stats<<<nb, MD_BLOCK, 0, st>>>(n, C.root.p, C.count.p, C.minid.p, C.max_size, C.hist.p, nb, C.part.p);
+    k_cl_finish<<<1, 1024, 0, st>>>(nb, C.part.p, nh, C.deg.p, (long long)C.nsamples, (long long)C.nseries, C.sum_fr.p,
+                                    C.series.p);
+}
+
+void cluster_zero(md_ctx *c)
+{
+    md_ctx::Cluster &C = c->cluster;
+    HIPCHK(hipMemsetAsync(C.sum_fr.p, 0, sizeof(long long) * MD_CL_NFR, c->stream));
+    HIPCHK(hipMemsetAsync(C.series.p, 0, sizeof(long long) * MD_CL_NFR * std::max<int64_t>(C.nseries, 1), c->stream));
+    HIPCHK(hipMemsetAsync(C.hist.p, 0, sizeof(unsigned long long) * ((size_t)C.max_size + 1), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    C.nsamples = 0;
 }
 
 } // namespace
@@ -2792,6 +2870,114 @@ int md_boo_reset(md_ctx *ctx)
     API_BEGIN
     sampler_of(ctx, &md_ctx::boo, "md_boo_reset", "boo");
     boo_zero(ctx);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Clusters (md_cluster.hpp): a sample walks the OUTER rows as md_boo_sample does, reads positions, rows and -- SOLID --
+// the bond-order sampler's last frame, and writes only the sampler's own buffers.
+int md_cluster_setup(md_ctx *ctx, double r_bond, int members, int max_size, int64_t nseries)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_cluster_setup: not available on a slab-decomposition handle");
+    if (!(r_bond > 0.0) || !std::isfinite(r_bond)) throw HipError("md_cluster_setup: r_bond must be finite and > 0");
+    if (r_bond > ctx->rc) {
+        char b[256];
+        snprintf(b, sizeof b, "md_cluster_setup: r_bond = %.17g exceeds the list cutoff %.17g (the rows are complete only up to it)",
+                 r_bond, ctx->rc);
+        throw HipError(b);
+    }
+    if (members != MD_CLUSTER_ALL && members != MD_CLUSTER_SOLID)
+        throw HipError("md_cluster_setup: members must be MD_CLUSTER_ALL or MD_CLUSTER_SOLID");
+    check_range("md_cluster_setup", "max_size", max_size, 1, MD_CL_MAX_SIZE);
+    if (nseries < 0 || nseries > MD_CL_MAX_SERIES) throw HipError("md_cluster_setup: nseries must be in 0..1048576");
+    if (members == MD_CLUSTER_SOLID && !ctx->boo.on)
+        throw HipError("md_cluster_setup: MD_CLUSTER_SOLID needs the bond-order sampler (call md_boo_setup first)");
+    md_ctx::Cluster &C = ctx->cluster;
+    C.on = false;
+    C.sampled = false;
+    C.members = members;
+    C.max_size = max_size;
+    C.rb = r_bond;
+    C.rb2 = r_bond * r_bond;
+    C.nseries = nseries;
+    const size_t n = (size_t)ctx->n;
+    C.parent.alloc(n);
+    C.root.alloc(n);
+    C.count.alloc(n);
+    C.minid.alloc(n);
+    C.ids.alloc(n);
+    C.mem.alloc(n);
+    C.mask.alloc(members == MD_CLUSTER_SOLID ? n : 1);
+    C.part.alloc((size_t)MD_CL_NPART * std::max(nblocks(ctx->n), 1));
+    C.deg.alloc((size_t)std::max(nblocks(ctx->n), 1));
+    C.hist.alloc((size_t)max_size + 1);
+    C.sum_fr.alloc(MD_CL_NFR);
+    C.series.alloc((size_t)MD_CL_NFR * std::max<int64_t>(nseries, 1));
+    cluster_zero(ctx);
+    C.on = true;
+    API_END
+}
+
+int md_cluster_sample(md_ctx *ctx)
+{
+    API_BEGIN
+    require_state(ctx, "md_cluster_sample");
+    md_ctx::Cluster &C = sampler_of(ctx, &md_ctx::cluster, "md_cluster_sample", "cluster");
+    if (C.members == MD_CLUSTER_SOLID && !(ctx->boo.on && ctx->boo.sampled))
+        throw HipError("md_cluster_sample: MD_CLUSTER_SOLID needs a bond-order frame (call md_boo_sample first)");
+    if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
+    if (ctx->dim == 3)
+        launch_cluster<3>(ctx);
+    else
+        launch_cluster<2>(ctx);
+    HIPCHK(hipGetLastError());
+    // the frame's own permutation: the next list build or upload re-sorts the handle's slots, the per-slot arrays stay
+    HIPCHK(hipMemcpyAsync(C.ids.p, ctx->dev(ctx->cur).id, sizeof(int32_t) * (size_t)ctx->n, hipMemcpyDeviceToDevice,
+                          ctx->stream));
+    ++C.nsamples;
+    C.sampled = true;
+    API_END
+}
+
+int md_cluster_particles(md_ctx *ctx, int32_t *label, int32_t *size)
+{
+    API_BEGIN
+    md_ctx::Cluster &C = sampler_of(ctx, &md_ctx::cluster, "md_cluster_particles", "cluster");
+    if (!C.sampled) throw HipError("md_cluster_particles: no frame sampled yet (call md_cluster_sample first)");
+    const size_t n = (size_t)ctx->n;
+    hipStream_t st = ctx->stream;
+    C.io_i.ensure(2 * n);
+    k_cl_export<<<nblocks(ctx->n), MD_BLOCK, 0, st>>>((int)n, C.ids.p, C.root.p, C.count.p, C.minid.p, C.io_i.p, C.io_i.p + n);
+    HIPCHK(hipGetLastError());
+    if (label) HIPCHK(hipMemcpyAsync(label, C.io_i.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (size) HIPCHK(hipMemcpyAsync(size, C.io_i.p + n, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_cluster_read(md_ctx *ctx, int64_t *nsamples, int64_t *sum_fr, int64_t *hist_size, int64_t *series)
+{
+    API_BEGIN
+    md_ctx::Cluster &C = sampler_of(ctx, &md_ctx::cluster, "md_cluster_read", "cluster");
+    hipStream_t st = ctx->stream;
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t) && sizeof(long long) == sizeof(int64_t),
+                  "the device words are read back as int64_t");
+    if (sum_fr) HIPCHK(hipMemcpyAsync(sum_fr, C.sum_fr.p, sizeof(int64_t) * MD_CL_NFR, hipMemcpyDeviceToHost, st));
+    if (hist_size)
+        HIPCHK(hipMemcpyAsync(hist_size, C.hist.p, sizeof(int64_t) * ((size_t)C.max_size + 1), hipMemcpyDeviceToHost, st));
+    if (series && C.nseries > 0)
+        HIPCHK(hipMemcpyAsync(series, C.series.p, sizeof(int64_t) * MD_CL_NFR * (size_t)C.nseries, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nsamples) *nsamples = C.nsamples;
+    API_END
+}
+
+int md_cluster_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    sampler_of(ctx, &md_ctx::cluster, "md_cluster_reset", "cluster");
+    cluster_zero(ctx);
     API_END
 }
 

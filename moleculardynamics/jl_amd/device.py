@@ -345,6 +345,41 @@ class MDDevice:
     def boo_reset(self):
         self._chk(self._L.md_boo_reset(self._h))
 
+    # -- clusters ---------------------------------------------------------------------------
+    def cluster_setup(self, r_bond, members=0, max_size=1024, nseries=0):
+        """Allocate the device cluster sampler (md_cluster_setup): members bonded within r_bond <= list cutoff, members =
+        MD_CLUSTER_ALL (0) or MD_CLUSTER_SOLID (1: the solid particles of the last bond-order frame), a size histogram of
+        max_size + 1 entries and nseries rows of the per-sample series; all zeroed."""
+        self._chk(self._L.md_cluster_setup(self._h, float(r_bond), int(members), int(max_size), int(nseries)))
+        self._cluster_shape = (int(max_size), int(nseries))
+
+    def cluster_sample(self):
+        """Add one sample of the current positions (does not wait, changes nothing the handle computes afterwards)."""
+        self._chk(self._L.md_cluster_sample(self._h))
+
+    def cluster_particles(self):
+        """(label int32[N], size int32[N]) of the last sampled frame, in particle-id order: the smallest particle id of the
+        particle's cluster and the cluster's size; -1 and 0 for a non-member; waits."""
+        label, size = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        self._chk(self._L.md_cluster_particles(self._h, _ip(label), _ip(size)))
+        return label, size
+
+    def cluster_read(self):
+        """(nsamples, sum_fr int64[8], hist_size int64[max_size + 1], series int64[min(nsamples, nseries), 8]), accumulated
+        since setup / reset; waits."""
+        max_size, nseries = getattr(self, "_cluster_shape", (0, 0))
+        ns = C.c_int64()
+        fr = np.zeros(8, dtype=np.int64)
+        hist = np.zeros(max_size + 1, dtype=np.int64)
+        series = np.zeros((max(nseries, 1), 8), dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.md_cluster_read(self._h, C.byref(ns), fr.ctypes.data_as(i64), hist.ctypes.data_as(i64),
+                                          series.ctypes.data_as(i64)))
+        return ns.value, fr, hist, series[: min(ns.value, nseries)]
+
+    def cluster_reset(self):
+        self._chk(self._L.md_cluster_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

@@ -36,7 +36,7 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, sq=None, stress=None, bond_order=None):
+                   dynamics=None, sq=None, stress=None, clusters=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -64,7 +64,20 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     3-D, psi_k in 2-D, the solid-particle count), on the device, at every bond_order.every-th output step, as rdf does.
     Written to pathname/bond_order.txt (the means and the q / qbar histograms) and pathname/bond_order_series.txt (one row
     per sample).  It never evaluates the potential: it works with Brownian dynamics and with user potentials.  Nothing else
-    the run produces changes."""
+    the run produces changes.
+
+    clusters: a ClusterAnalysis (analysis.py) to sample the connected components of the bond graph into (cluster sizes, the
+    size distribution, the largest cluster), on the device, at every clusters.every-th output step.  Written to
+    pathname/clusters.txt (the means and n(s)) and pathname/clusters_series.txt (one row per sample).  With
+    members="solid" the members are the solid particles of bond_order's sample of the same step: bond_order= is required
+    and clusters.every must be a multiple of bond_order.every.  It never evaluates the potential.  Nothing else the run
+    produces changes."""
+    if clusters is not None and clusters.members == "solid":
+        if bond_order is None:
+            raise ValueError('clusters with members="solid" needs bond_order= in the same run')
+        if clusters.every % bond_order.every != 0:
+            raise ValueError("clusters.every must be a multiple of bond_order.every: every cluster sample needs the "
+                             "bond-order sample of its step")
     brownian = isinstance(ensemble, Brownian)
     os.makedirs(pathname, exist_ok=True)
     trajectory_file, thermo_file = _io.open_files(pathname, traj_name, thermo_name)
@@ -85,7 +98,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     # the virial is sampled every 10th step and averaged at the output steps (:253-266)
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
     # the samplers (analysis.py's protocol), in the order their device calls are made at a step they share
-    samplers = [s for s in (rdf, dynamics, sq, stress, bond_order) if s is not None]
+    # (clusters after bond_order: with members="solid" it reads the bond-order frame of the same step)
+    samplers = [s for s in (rdf, dynamics, sq, stress, bond_order) + (clusters,) if s is not None]
     run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
                                 unitcell=state.unitcell, brownian=brownian)
     for s in samplers:
