@@ -225,3 +225,71 @@ def cross_face_dimers(target, L=63.0, seed=4711):
     n = x.shape[0]
     return dict(n=n, dim=3, box=np.full(3, L), x=x, v=np.zeros_like(x), f=np.zeros_like(x),
                 img=np.zeros((n, 3), dtype=np.int32), diam=np.ones(n), cat=np.array(cats))
+
+
+# ---------------------------------------------------------------------------------------------
+# Inputs of the step audit (tests/step_audit.py): systems whose neighbour rows are ragged, empty or partial, and the
+# mixed-diameter variants of the liquid.  Fixed seeds; every one stays bounded under the CPU oracle for 80 steps at the
+# time step given (tests/test_step_audit.py checks the two it runs; the others were checked the same way).
+# ---------------------------------------------------------------------------------------------
+def blob_gas_system(seed=2718):
+    """A 9^3 cubic crystallite (spacing 1.08, jitter +-0.03, kT 0.3) centred in a 24^3 box, plus 120 gas particles (kT 4.0)
+    on a jittered coarse grid (spacing 2.0, jitter +-0.2), none of them inside the crystallite's bounding box grown by 1.2;
+    ids randomly permuted.  n = 849 = 13 waves + 17 = 3 tiles + 81: neighbour counts within 2.5 run from 0 (most of the
+    gas) to 58, so rows of every length, empty ones included, share tiles, and the last tile is partial.  LJ, dt 0.004."""
+    rng = np.random.default_rng(seed)
+    L = 24.0
+    g = np.stack(np.meshgrid(*[np.arange(9)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(float)
+    blob = (g - 4.0) * 1.08 + 0.5 * L + rng.uniform(-0.03, 0.03, g.shape)
+    lo, hi = blob.min(axis=0) - 1.2, blob.max(axis=0) + 1.2
+    c = np.stack(np.meshgrid(*[np.arange(12)] * 3, indexing="ij"), -1).reshape(-1, 3).astype(float)
+    gas = (c + 0.5) * 2.0 + rng.uniform(-0.2, 0.2, c.shape)
+    gas = gas[~np.all((gas > lo) & (gas < hi), axis=1)]
+    gas = gas[rng.permutation(len(gas))[:120]]
+    x = np.concatenate([blob, gas])
+    v = np.concatenate([initialize_velocities(0.3, rng, len(blob), 3), initialize_velocities(4.0, rng, len(gas), 3)])
+    p = rng.permutation(len(x))
+    x, v = np.ascontiguousarray(x[p]), np.ascontiguousarray(v[p])
+    n = len(x)
+    return dict(n=n, dim=3, box=np.full(3, L), x=x, v=v, f=np.zeros_like(x), img=np.zeros((n, 3), dtype=np.int32),
+                diam=np.ones(n))
+
+
+def sheared(system, tilt):
+    """The same Cartesian positions in the cell whose second lattice vector is tilted by `tilt` along x (columns = lattice
+    vectors), wrapped into that cell.  A tilt that is a multiple of the system's own grid spacing keeps its periodic images
+    on the grid, so no two particles come closer than they were."""
+    box = system["box"]
+    U = np.diag(box).astype(float)
+    U[0, 1] = tilt
+    fr = np.linalg.solve(U, system["x"].T).T
+    fr -= np.floor(fr)
+    out = dict(system)
+    out["x"] = np.ascontiguousarray(fr @ U.T)
+    out["cell"] = U
+    return out
+
+
+def tiny_system(n, kT=1.0, seed_vel=1000):
+    """The geometry of tests/test_gpu_edge.py::test_tiny_systems made steppable: a loose jittered-grid cluster in a 9^3 box
+    (the box clips the default skin) plus a pair that interacts through the periodic corner, with seeded velocities.  Two
+    changes against the static test, whose corner pair sits at r = 0.17 (|F| ~ 1e11, fine for one force evaluation, not
+    for a trajectory) and whose grid spacing falls to 0.81 at n = 257: the corner pair is 0.6 * sqrt(3) = 1.04 apart, for
+    n = 2 as well (the static test's dimer does not interact), and the grid spacing is at least 1.08."""
+    rng = np.random.default_rng(n)
+    m = int(np.ceil(n ** (1 / 3)))
+    g = np.stack(np.meshgrid(*[np.arange(m)] * 3, indexing="ij"), -1).reshape(-1, 3)[:n].astype(float)
+    x = 1.2 + g * max((6.0 / max(m, 2)) * 0.95, 1.08) + rng.uniform(-0.03, 0.03, (n, 3))
+    x[0] = [0.05, 0.05, 0.05]
+    x[1] = [8.45, 8.45, 8.45]
+    v = initialize_velocities(kT, np.random.default_rng(seed_vel + n), n, 3)
+    return dict(n=n, dim=3, box=np.full(3, 9.0), x=np.ascontiguousarray(x), v=v, f=np.zeros_like(x),
+                img=np.zeros((n, 3), dtype=np.int32), diam=np.ones(n))
+
+
+def with_diameters(system, lo, hi=None, seed=11):
+    """A copy of `system` with diameters U[lo, hi] (fixed seed), or all equal to lo."""
+    out = dict(system)
+    n = system["n"]
+    out["diam"] = np.full(n, float(lo)) if hi is None else np.random.default_rng(seed).uniform(lo, hi, n)
+    return out
