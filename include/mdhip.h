@@ -361,6 +361,56 @@ int md_cluster_particles(md_ctx *ctx, int32_t *label, int32_t *size);
 int md_cluster_read(md_ctx *ctx, int64_t *nsamples, int64_t *sum_fr, int64_t *hist_size, int64_t *series);
 int md_cluster_reset(md_ctx *ctx);
 
+/* Cage-relative dynamics and bond breaking, sampled on the device (new relative to the reference): displacements measured
+ * relative to the neighbours a particle had at the time origin -- free of the long-wavelength (Mermin-Wagner) drift that
+ * makes the plain MSD and F_s of md_dyn_* decay in 2-D although nobody left its cage -- and the bond-breaking
+ * correlation C_B(t) of Yamamoto and Onuki.  The potential is never evaluated.
+ *
+ * Bond criterion.  sigma_ij = (sigma_i + sigma_j) / 2.0.  A radius r is passed iff d2 < (r*s)*(r*s) with s = sigma_ij if
+ * `scaled`, else 1.0; d2 = (b0*b0 + b1*b1) + b2*b2 (no fma) of the vector b in question; fp64 throughout.
+ *
+ * md_cage_origin(slot) stores the current frame (md_dyn_origin's: wrapped x, images, particle-id order) and the
+ * neighbour table of the slot: for every particle i, in the order of its neighbour-list row, the entries (j, del_ij) of
+ * the row's entries that pass the criterion with r_neigh; del_ij = x_j(+periodic translation) - x_i as the force kernels
+ * form it.  A neighbour is a (particle, periodic image) pair: in a small cell j may appear through two images.
+ * n_i = min(hits, max_neigh); every hit beyond max_neigh is dropped and counted in `overflow`.  The diameters are the
+ * origin's.  The table is keyed by particle id: list rebuilds and md_upload do not touch a stored origin.  If the
+ * neighbour list is not valid the call builds it exactly as md_boo_sample does.  It does not wait.
+ *
+ * md_cage_sample(slots, rows, count) exports the current frame once and, per (slot, row):
+ *   Del_i      the displacement since the slot's origin, by md_dyn_sample's formula
+ *   m_i        = (sum over i's entries k, in order, of Del_{j_k}) / n_i
+ *   Del^CR_i   = Del_i - m_i;  d2 = |Del^CR_i|^2, d4 = d2*d2, s_i(q) = sum over the axes c of cos(q*Del^CR_c)
+ *   bond k of i at the sample time: b = del_ij + (Del_j - Del_i) -- exact under any number of boundary crossings; it
+ *              survives iff it passes the criterion with r_break, else it is broken
+ * A particle with n_i = 0 contributes to nothing.  Added into the row, since setup or the last reset:
+ *   sums[row*(2+nq)]   sum d2, sum d4, sum s(q_0..): fp64, reduced over particle ids in md_dyn's fixed tree (no
+ *                      floating-point atomics: the same two frames and table give the same bits)
+ *   counts[row*3]      particles with n_i > 0, sum n_i, surviving bonds (directed)
+ *   hist_broken[row*33] particles with n_i > 0 by their number of broken bonds, 0..32
+ *   nsamples[row] += 1
+ * The integers are functions of the two frames alone; the fp64 sums depend on the row order the origin was stored with
+ * and agree across handles to rounding.  Neither call writes anything of the handle: a run with samples is bit-identical
+ * to one without.  md_cage_particles waits and returns, in particle-id order, n_i, d2 of Del^CR_i and the broken count
+ * of the last (slot, row) of the last md_cage_sample call (any may be NULL; 0 where n_i = 0).  md_cage_read waits and
+ * returns nsamples[nrows], sums, counts, hist_broken and overflow[1] (any may be NULL).  md_cage_reset zeroes the rows; it
+ * keeps the setup, the stored origins and -- because it belongs to them -- overflow.
+ *
+ * md_cage_setup: 1 <= nslots <= 64; nrows >= 1; finite 0 < r_neigh <= r_break; scaled 0 or 1; 1 <= max_neigh <= 32;
+ * 0 <= nq <= 16 finite q; allocates the table, nslots*N*max_neigh*(4+8*d) bytes, and zeroes everything; calling it again
+ * starts over.  MDHIP_CAGE_ALLOC_LIMIT=bytes in the environment refuses a larger table as a failed allocation is
+ * refused.  Refused: a slab-decomposition handle, an argument out of range, a failed table allocation, any call before
+ * md_cage_setup, a slot or row out of range, an empty slot, md_cage_particles before the first sample, and
+ * md_cage_origin when r_neigh (times the largest diameter if scaled) exceeds list_cutoff: the rows are complete only up
+ * to it.                                                                                                              */
+int md_cage_setup(md_ctx *ctx, int nslots, int nrows, double r_neigh, double r_break, int scaled, int max_neigh,
+                  const double *q, int nq);
+int md_cage_origin(md_ctx *ctx, int slot);
+int md_cage_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int count);
+int md_cage_particles(md_ctx *ctx, int32_t *nnb, double *d2cr, int32_t *broken);
+int md_cage_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *counts, int64_t *hist_broken, int64_t *overflow);
+int md_cage_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

@@ -17,6 +17,7 @@ export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, Pseudo
        initialize_state, initialize_velocities, run_simulation!, LinearRamp, ExponentialRamp, fire_minimize!, minimize!,
        LennardJonesShifted, LennardJonesForceShifted, LennardJonesXPLOR, device_spec, RadialDistribution, compute_rdf,
        gofr, write_rdf, SelfDynamics, msd, alpha2, fs, van_hove, write_dynamics, write_van_hove,
+       CageDynamics, bond_correlation, broken_distribution, write_cage, cage_particles,
        StructureFactor, select_wave_vectors, compute_sq, sofq, fqt, fqt_normalised, write_sq, write_fqt
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
@@ -489,6 +490,108 @@ function write_van_hove(path, dyn::SelfDynamics)
     end
 end
 
+# ---- cage-relative dynamics and bond breaking, sampled on the device (md_cage_*; as analysis.py's CageDynamics) ---------
+"""
+CageDynamics(r_neigh; r_break=r_neigh, scaled=false, max_neighbours=16, q=(2π,), lags=nothing, origin_every=nothing):
+the MSD, alpha2 and F_s(q,t) of the displacement relative to the mean displacement of the neighbours a particle had at
+the time origin (closer than r_neigh, times sigma_ij if scaled), and the bond-breaking correlation C_B(t) (a bond is
+broken when it is at least r_break long), accumulated across run_simulation! calls until reset!.  The schedule is
+SelfDynamics' own.  More than max_neighbours (<= 32) neighbours at an origin is an error at the end of the run.
+"""
+mutable struct CageDynamics
+    r_neigh::Float64
+    r_break::Float64
+    scaled::Bool
+    max_neighbours::Int
+    sched::SelfDynamics             # q, lags, origin_every, nslots: the schedule is SelfDynamics' own
+    nsamples::Vector{Int64}
+    sums::Matrix{Float64}           # (2 + nq) x nlags: sum d2, sum d4, sum s(q) per q, of the cage-relative displacement
+    counts::Matrix{Int64}           # 3 x nlags: particles with neighbours, sum n_i, surviving bonds
+    hist_broken::Matrix{Int64}      # 33 x nlags: particles by their number of broken bonds
+    dimension::Int
+    dt::Float64
+end
+function CageDynamics(r_neigh; r_break=nothing, scaled::Bool=false, max_neighbours::Int=16, q=(2π,), lags=nothing,
+                      origin_every=nothing)
+    (r_neigh > 0 && isfinite(r_neigh)) || error("r_neigh must be finite and > 0")
+    rb = r_break === nothing ? Float64(r_neigh) : Float64(r_break)
+    (isfinite(rb) && rb >= r_neigh) || error("r_break must be finite and >= r_neigh")
+    1 <= max_neighbours <= 32 || error("max_neighbours must be in 1..32")
+    sched = SelfDynamics(; q=q, lags=lags, origin_every=origin_every)
+    nl = length(sched.lags)
+    return CageDynamics(Float64(r_neigh), rb, scaled, max_neighbours, sched, zeros(Int64, nl),
+                        zeros(2 + length(sched.q), nl), zeros(Int64, 3, nl), zeros(Int64, 33, nl), 3, 1.0)
+end
+reset!(cg::CageDynamics) = (cg.nsamples .= 0; cg.sums .= 0; cg.counts .= 0; cg.hist_broken .= 0; cg)
+cage_schedule(cg::CageDynamics, T::Int) = dyn_schedule(cg.sched, T)
+
+function cage_setup!(dev::Device, cg::CageDynamics)
+    check(dev, ccall((:md_cage_setup, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Float64, Float64, Cint, Cint, Ptr{Float64}, Cint),
+                     dev.h, cg.sched.nslots, length(cg.sched.lags), cg.r_neigh, cg.r_break, cg.scaled ? 1 : 0,
+                     cg.max_neighbours, cg.sched.q, length(cg.sched.q)))
+end
+cage_origin!(dev::Device, slot::Integer) = check(dev, ccall((:md_cage_origin, LIB), Cint, (Ptr{Cvoid}, Cint), dev.h, slot))
+function cage_sample!(dev::Device, slots::Vector{Int32}, rows::Vector{Int32})
+    check(dev, ccall((:md_cage_sample, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Cint), dev.h, slots, rows,
+                     length(slots)))
+end
+cage_reset!(dev::Device) = check(dev, ccall((:md_cage_reset, LIB), Cint, (Ptr{Cvoid},), dev.h))
+"n_i, |Del^CR|^2 and the broken bonds of the last (slot, row) of the last cage_sample! call, in particle-id order"
+function cage_particles(dev::Device)
+    nnb = zeros(Int32, dev.n); d2 = zeros(dev.n); broken = zeros(Int32, dev.n)
+    check(dev, ccall((:md_cage_particles, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}), dev.h, nnb, d2,
+                     broken))
+    return nnb, d2, broken
+end
+function cage_act!(dev::Device, ev)
+    smp, org = ev
+    isempty(smp) || cage_sample!(dev, Int32[a for (a, _) in smp], Int32[b for (_, b) in smp])
+    org >= 0 && cage_origin!(dev, org)
+end
+function cage_collect!(dev::Device, cg::CageDynamics, dimension, dt)
+    nl = length(cg.sched.lags)
+    ns = zeros(Int64, nl); sums = zeros(2 + length(cg.sched.q), nl); counts = zeros(Int64, 3, nl)
+    hist = zeros(Int64, 33, nl); overflow = zeros(Int64, 1)
+    check(dev, ccall((:md_cage_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}),
+                     dev.h, ns, sums, counts, hist, overflow))
+    overflow[1] == 0 || error("CageDynamics: $(overflow[1]) neighbours did not fit max_neighbours = $(cg.max_neighbours) " *
+                              "entries per particle at the origins of this run: raise max_neighbours (at most 32) or " *
+                              "lower r_neigh; nothing was accumulated")
+    cg.nsamples .+= ns; cg.sums .+= sums; cg.counts .+= counts; cg.hist_broken .+= hist
+    cg.dimension = dimension; cg.dt = dt
+    return cg
+end
+
+_per(cg::CageDynamics, v) = [cg.counts[1, k] > 0 ? v[k] / cg.counts[1, k] : NaN for k in eachindex(v)]
+"<|Del^CR|^2> per lag, over the particles that had neighbours"
+msd(cg::CageDynamics) = _per(cg, cg.sums[1, :])
+alpha2(cg::CageDynamics) = (d = cg.dimension; d .* _per(cg, cg.sums[2, :]) ./ ((d + 2) .* msd(cg) .^ 2) .- 1.0)
+"cage-relative F_s(q, t): nlags x nq"
+fs(cg::CageDynamics) = [cg.counts[1, k] > 0 ? cg.sums[2 + j, k] / (cg.dimension * cg.counts[1, k]) : NaN
+                        for k in eachindex(cg.sched.lags), j in eachindex(cg.sched.q)]
+"C_B(t) per lag: surviving bonds / origin bonds"
+bond_correlation(cg::CageDynamics) = [cg.counts[2, k] > 0 ? cg.counts[3, k] / cg.counts[2, k] : NaN
+                                      for k in eachindex(cg.sched.lags)]
+"nlags x 33: the fraction of particles that lost b = 0..32 bonds"
+broken_distribution(cg::CageDynamics) = [cg.counts[1, k] > 0 ? cg.hist_broken[b, k] / cg.counts[1, k] : NaN
+                                         for k in eachindex(cg.sched.lags), b in 1:33]
+
+function write_cage(path, cg::CageDynamics; dt=cg.dt)
+    m = msd(cg); a = alpha2(cg); f = fs(cg); cb = bond_correlation(cg)
+    open(path, "w") do io
+        print(io, "# lag time msd_cr alpha2_cr")
+        for q in cg.sched.q; print(io, " Fs_cr(q=", @sprintf("%.6g", q), ")"); end
+        println(io, " C_B nsamples")
+        for (k, l) in enumerate(cg.sched.lags)
+            cg.nsamples[k] > 0 || continue
+            @printf(io, "%d %.6e %.6e %.6e", l, l * dt, m[k], a[k])
+            for j in eachindex(cg.sched.q); @printf(io, " %.6e", f[k, j]); end
+            @printf(io, " %.6e %d\n", cb[k], cg.nsamples[k])
+        end
+    end
+end
+
+
 # ---- density modes, S(q) and coherent F(q,t), sampled on the device (md_sq_*; normalisation and file formats as analysis.py)
 """
 select_wave_vectors(unitcell, q_max; dq=nothing, max_per_bin=16, seed=0) -> (n, q, bin): every integer vector n of the half
@@ -764,14 +867,16 @@ steps (step % frequency == 0, 0-based), draws the thermostat's random numbers on
 order, and writes the thermo line, the LAMMPS frames, the log-spaced snapshots and final.xyz.  With rdf a
 RadialDistribution, g(r) is sampled on the device at every rdf.every-th output step and written to pathname/rdf.txt.
 With sq a StructureFactor, S(q) is sampled the same way (pathname/sq.txt) and, if it is dynamic, the coherent F(q,t) on its
-schedule (pathname/fqt.txt).
+schedule (pathname/fqt.txt).  With cage a CageDynamics, the cage-relative MSD, alpha2, F_s(q,t) and the bond-breaking
+correlation are sampled on SelfDynamics' schedule (pathname/cage.txt).
 """
 function run_simulation!(state::SimulationState, params::Parameters, ensemble::Ensemble, total_steps::Int,
                          frequency::Int, pathname::String; traj_name::String="trajectory.xyz",
                          thermo_name::String="thermo.txt", compress::Bool=false, log_times::Bool=false,
                          rdf::Union{Nothing,RadialDistribution}=nothing,
                          dynamics::Union{Nothing,SelfDynamics}=nothing,
-                         sq::Union{Nothing,StructureFactor}=nothing)
+                         sq::Union{Nothing,StructureFactor}=nothing,
+                         cage::Union{Nothing,CageDynamics}=nothing)
     dev = state.system.device; d = state.dimension; n = params.n_particles
     brownian = ensemble isa Brownian
     configure!(dev, params.potential)
@@ -785,6 +890,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
     sq_stops, sq_events = sq === nothing ? (Int[], nothing) : sq_schedule(sq, total_steps)
     sq === nothing || sq_setup!(dev, sq, state.unitcell)
     sq_i = 1
+    # cage-relative dynamics: SelfDynamics' stops; its device calls come after every other sampler's at a shared step
+    cage_stops, cage_events = cage === nothing ? (Int[], nothing) : cage_schedule(cage, total_steps)
+    cage === nothing || cage_setup!(dev, cage)
+    cage_i = 1
     trajectory_file, thermo_file = open_files(pathname, traj_name, thermo_name)
     open(io -> println(io, "# Step Energy Temperature Pressure"), thermo_file, "a")
     volume = abs(det(state.unitcell))                                                # src/simulation.jl:7-9
@@ -818,6 +927,8 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         dyn_i <= length(dyn_stops) && (next_out = min(next_out, dyn_stops[dyn_i]))
         while sq_i <= length(sq_stops) && sq_stops[sq_i] < step; sq_i += 1; end
         sq_i <= length(sq_stops) && (next_out = min(next_out, sq_stops[sq_i]))
+        while cage_i <= length(cage_stops) && cage_stops[cage_i] < step; cage_i += 1; end
+        cage_i <= length(cage_stops) && (next_out = min(next_out, cage_stops[cage_i]))
         last = min(next_out, total_steps - 1)
         ns = last - step + 1
         if brownian
@@ -873,6 +984,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
             end
             (sq_static || sq_ev !== nothing) && sq_act!(dev, sq_static, sq_ev)   # rho once: static, samples, origin
         end
+        if cage_i <= length(cage_stops) && cage_stops[cage_i] == last
+            cage_act!(dev, cage_events[last])        # the samples, then the new origin and its neighbour table
+            cage_i += 1
+        end
         if log_times && snap_i <= length(snapshot_times) && snapshot_times[snap_i] == last   # :153-171
             push!(pending, (joinpath(pathname, "snapshot.$(last)"), last, "w"))
             snap_i += 1
@@ -899,6 +1014,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         sq_collect!(dev, sq, params.dt)
         write_sq(joinpath(pathname, "sq.txt"), sq)
         sq.dynamic && write_fqt(joinpath(pathname, "fqt.txt"), sq)
+    end
+    if cage !== nothing
+        cage_collect!(dev, cage, d, params.dt)
+        write_cage(joinpath(pathname, "cage.txt"), cage)
     end
     compress && isfile(trajectory_file) && compress_zstd(trajectory_file)
     return nothing

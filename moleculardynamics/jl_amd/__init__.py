@@ -10,7 +10,7 @@ from .initialization import (initialize_state, initialize_velocities, lattice_po
 from .simulation import run_simulation
 from .analysis import (RadialDistribution, compute_rdf, SelfDynamics, StructureFactor, compute_sq, select_wave_vectors,
                        StressTensor, compute_stress, BondOrder, compute_bond_order, ClusterAnalysis,
-                       compute_clusters)
+                       compute_clusters, CageDynamics)
 from .minimize import fire_minimize, minimize
 from .device import MDDevice
 from ._lib import MdhipError
@@ -21,5 +21,5 @@ __all__ = [
     "initialize_velocities", "Potential", "evaluate", "MDDevice", "MdhipError", "lattice_positions",
     "fire_minimize", "minimize", "LennardJonesShifted", "LennardJonesForceShifted", "LennardJonesXPLOR",
     "RadialDistribution", "compute_rdf", "SelfDynamics", "StructureFactor", "compute_sq", "select_wave_vectors",
-    "StressTensor", "compute_stress", "BondOrder", "compute_bond_order", "ClusterAnalysis", "compute_clusters",
+    "StressTensor", "compute_stress", "BondOrder", "compute_bond_order", "ClusterAnalysis", "compute_clusters", "CageDynamics",
 ]

@@ -31,6 +31,7 @@ EXPORTS = [
     "md_stress_setup", "md_stress_sample", "md_stress_tensor", "md_stress_read", "md_stress_reset",
     "md_boo_setup", "md_boo_sample", "md_boo_particles", "md_boo_qlm", "md_boo_read", "md_boo_reset",
     "md_cluster_setup", "md_cluster_sample", "md_cluster_particles", "md_cluster_read", "md_cluster_reset",
+    "md_cage_setup", "md_cage_origin", "md_cage_sample", "md_cage_particles", "md_cage_read", "md_cage_reset",
 ]
 
 
@@ -199,6 +200,18 @@ def load():
     L.md_cluster_read.restype = C.c_int
     L.md_cluster_reset.argtypes = [vp]
     L.md_cluster_reset.restype = C.c_int
+    L.md_cage_setup.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, dp, C.c_int]
+    L.md_cage_setup.restype = C.c_int
+    L.md_cage_origin.argtypes = [vp, C.c_int]
+    L.md_cage_origin.restype = C.c_int
+    L.md_cage_sample.argtypes = [vp, ip, ip, C.c_int]
+    L.md_cage_sample.restype = C.c_int
+    L.md_cage_particles.argtypes = [vp, ip, dp, ip]
+    L.md_cage_particles.restype = C.c_int
+    L.md_cage_read.argtypes = [vp, i64p, dp, i64p, i64p, i64p]
+    L.md_cage_read.restype = C.c_int
+    L.md_cage_reset.argtypes = [vp]
+    L.md_cage_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -2,7 +2,8 @@
 the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes, S(q), coherent F(q, t)), the stress
 (pressure tensor, stress autocorrelations, Green-Kubo viscosity), the bond-orientational order (Steinhardt q_l, the
 neighbour-averaged qbar_l, psi_k in 2-D, the solid-particle count) and the clusters (connected components of the bond
-graph: sizes, the size distribution, the largest -- solid -- cluster).
+graph: sizes, the size distribution, the largest -- solid -- cluster) and the cage-relative dynamics (displacements
+relative to the origin neighbours' mean, the bond-breaking correlation C_B).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -1155,3 +1156,136 @@ def compute_clusters(state, params, r_bond, members="all", bond_order=None):
     labels, sizes = dev.cluster_particles()
     _, fr, _, _ = dev.cluster_read()
     return labels, sizes, fr
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Cage-relative dynamics and bond breaking, sampled on the device (md_cage_*): displacements measured relative to the
+# mean displacement of the neighbours a particle had at the time origin, and the fraction of origin bonds that survive.
+
+class CageDynamics:
+    """Cage-relative self dynamics and the bond-breaking correlation, accumulated on the device over the samples of a
+    schedule until reset().
+
+    r_neigh: particles closer than r_neigh at an origin are neighbours (bonded); r_break >= r_neigh (default r_neigh): a
+    bond counts as broken at a sample when it is at least r_break long.  scaled=True multiplies both radii by
+    sigma_ij = (sigma_i + sigma_j) / 2 per pair.  r_neigh (times the largest diameter if scaled) must not exceed the list
+    cutoff of the handle.  max_neighbours <= 32 entries are kept per particle: more neighbours than that is an error at the
+    end of the run (a truncated cage would bias every column).  q: up to 16 wavenumbers for the cage-relative F_s(q, t).
+    The schedule (lags, origin_every) is SelfDynamics': log-time by default, samples before the new origin at a shared step.
+
+    Fields: lags, nsamples (per lag), sums (per lag: sum d2, sum d4, sum s(q) per q, of Del^CR), counts (per lag: particles
+    with neighbours, sum n_i, surviving bonds), hist_broken (per lag: particles by their number of broken bonds, 0..32)."""
+
+    def __init__(self, r_neigh, r_break=None, scaled=False, max_neighbours=16, q=(2.0 * math.pi,), lags=None,
+                 origin_every=None):
+        r_neigh = float(r_neigh)
+        if not (r_neigh > 0.0 and math.isfinite(r_neigh)):
+            raise ValueError("r_neigh must be finite and > 0")
+        r_break = r_neigh if r_break is None else float(r_break)
+        if not (math.isfinite(r_break) and r_break >= r_neigh):
+            raise ValueError("r_break must be finite and >= r_neigh")
+        if int(max_neighbours) != max_neighbours or not 1 <= int(max_neighbours) <= 32:
+            raise ValueError("max_neighbours must be in 1..32")
+        q = np.array([float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64))], dtype=np.float64)
+        if q.size > 16:
+            raise ValueError("at most 16 wavenumbers q")
+        if not np.all(np.isfinite(q)):
+            raise ValueError("every q must be finite")
+        self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+        self.r_neigh, self.r_break, self.scaled, self.max_neighbours = r_neigh, r_break, bool(scaled), int(max_neighbours)
+        self.q = q
+        self.lags = np.array(lag_list, dtype=np.int64)
+        nl = len(lag_list)
+        self.nsamples = np.zeros(nl, dtype=np.int64)
+        self.sums = np.zeros((nl, 2 + q.size))
+        self.counts = np.zeros((nl, 3), dtype=np.int64)
+        self.hist_broken = np.zeros((nl, 33), dtype=np.int64)
+        self.dimension = 3
+        self.dt = 1.0
+
+    def reset(self):
+        self.nsamples[:] = 0
+        self.sums[:] = 0.0
+        self.counts[:] = 0
+        self.hist_broken[:] = 0
+
+    def schedule(self, total_steps):
+        """(stops, events) for one run of `total_steps` steps, exactly SelfDynamics.schedule's."""
+        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    def _accumulate(self, nsamples, sums, counts, hist_broken, dimension, dt):
+        self.nsamples += np.asarray(nsamples, dtype=np.int64)
+        self.sums += np.asarray(sums, dtype=np.float64)
+        self.counts += np.asarray(counts, dtype=np.int64)
+        self.hist_broken += np.asarray(hist_broken, dtype=np.int64)
+        self.dimension, self.dt = int(dimension), float(dt)
+
+    def _per(self, col):
+        cnt = self.counts[:, 0].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cnt > 0, self.sums[:, col] / cnt, np.nan)
+
+    def msd(self):
+        """<|Del^CR|^2> per lag over the particles that had neighbours; nan where a lag has none."""
+        return self._per(0)
+
+    def alpha2(self):
+        """Non-Gaussian parameter d <d^4> / ((d + 2) <d^2>^2) - 1 of the cage-relative displacement, per lag."""
+        d = self.dimension
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return d * self._per(1) / ((d + 2) * self.msd() ** 2) - 1.0
+
+    def fs(self):
+        """Cage-relative F_s(q, t), (nlags, nq): sum s / (d count)."""
+        cnt = self.counts[:, 0].astype(np.float64)[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cnt > 0, self.sums[:, 2:] / (self.dimension * cnt), np.nan)
+
+    def bond_correlation(self):
+        """C_B(t) per lag: surviving bonds / origin bonds (directed); nan where a lag has no bond."""
+        nb = self.counts[:, 1].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(nb > 0, self.counts[:, 2] / nb, np.nan)
+
+    def broken_distribution(self):
+        """(nlags, 33): the fraction of particles (with neighbours) that lost b = 0..32 bonds, per lag."""
+        cnt = self.counts[:, 0].astype(np.float64)[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cnt > 0, self.hist_broken / cnt, np.nan)
+
+    def write(self, path, dt=None):
+        """# lag time msd_cr alpha2_cr Fs_cr(q=..)... C_B nsamples, one row per lag that has a sample, time = lag dt."""
+        dt = self.dt if dt is None else float(dt)
+        msd, a2, fs, cb = self.msd(), self.alpha2(), self.fs(), self.bond_correlation()
+        fmt = "%d %.6e %.6e %.6e" + " %.6e" * self.q.size + " %.6e %d\n"
+        with open(path, "w") as io:
+            io.write("# lag time msd_cr alpha2_cr" + "".join(" Fs_cr(q=%.6g)" % v for v in self.q) + " C_B nsamples\n")
+            for k, l in enumerate(self.lags):
+                if self.nsamples[k] > 0:
+                    io.write(fmt % ((int(l), l * dt, msd[k], a2[k]) + tuple(fs[k]) + (cb[k], int(self.nsamples[k]))))
+
+    # -- run_simulation's sampler protocol: the stops of schedule() ---------------------------------------------------
+    def _begin(self, dev, run):
+        self._stops, self._events = self.schedule(run.total_steps)
+        dev.cage_setup(self.nslots, len(self.lags), self.r_neigh, self.r_break, self.scaled, self.max_neighbours, self.q)
+
+    def _next(self, step):
+        return _next_stop(self._stops, step)
+
+    def _act(self, dev, step):
+        """The work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
+        smp, org = self._events[step]
+        if smp:
+            dev.cage_sample([a for a, _ in smp], [b for _, b in smp])
+        if org is not None:
+            dev.cage_origin(org)
+
+    def _finish(self, dev, run, pathname):
+        ns, sums, counts, hist, overflow = dev.cage_read()
+        if overflow != 0:
+            raise ValueError(f"CageDynamics: {int(overflow)} neighbours did not fit max_neighbours = {self.max_neighbours} "
+                             "entries per particle at the origins of this run: raise max_neighbours (at most 32) or lower "
+                             "r_neigh; nothing was accumulated")
+        self._accumulate(ns, sums, counts, hist, run.dim, run.dt)
+        self.write(os.path.join(pathname, "cage.txt"))

@@ -16,6 +16,7 @@
 #include "md_stress.hpp"
 #include "md_boo.hpp"
 #include "md_cluster.hpp"
+#include "md_cage.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -165,6 +166,7 @@ struct md_ctx {
     RtcModule *rtc = nullptr; // run-time compiled kernels of a user potential (POT_CUSTOM)
     bool uniform_sigma = true;
     double sigma_u = 1.0;
+    double sigma_max = 1.0; // the largest diameter uploaded (pos[].w starts at 1)
     int device = 0;
     hipStream_t stream = nullptr;     // the stream every kernel of the handle runs on
     hipStream_t own_stream = nullptr; // the one created with the handle (stream may be the caller's: md_set_stream)
@@ -369,6 +371,32 @@ struct md_ctx {
         DBuf<unsigned long long> part, deg, hist; // 6 x nblk (256-slot blocks); the hook kernel's blocks; max_size + 1
         DBuf<long long> sum_fr, series;   // 8; nseries x 8
     } cluster;
+
+    // cage-relative dynamics and bond breaking (md_cage_*): per origin slot the frame, n_i, sigma and -- the table -- the
+    // entry lists (id_j, del_ij), all by particle id; the current frame, the displacements of one batch, block partials;
+    // per-row sums, counts and histograms; the last sample's per-particle arrays; the dropped-hit counter
+    struct Cage {
+        bool on = false;
+        bool sampled = false;             // l_nnb / l_broken / l_d2 hold a sample
+        int nslots = 0, nrows = 0, nq = 0, max_neigh = 0, scaled = 0;
+        double r_neigh = 0.0, r_break = 0.0;
+        std::vector<double> q;
+        std::vector<char> filled;         // nslots: the slot holds an origin
+        std::vector<int64_t> nsamples;    // nrows
+        int32_t *nid = nullptr;           // the table: nslots x max_neigh x n ids ...
+        double *del = nullptr;            // ... and nslots x max_neigh x dim x n bond components
+        DBuf<double> ox, cx, sig, disp, part, sums, l_d2; // nslots frames; frame; nslots x n; batch x dim x n; ...; nrows x (2 + nq); n
+        DBuf<int32_t> oi, ci, nnb, l_nnb, l_broken;       // nslots frames; frame; nslots x n; n; n
+        DBuf<unsigned long long> counts, hist, overflow;  // nrows x 3; nrows x 33; 1
+        void release_table()
+        {
+            if (nid) (void)hipFree(nid);
+            if (del) (void)hipFree(del);
+            nid = nullptr;
+            del = nullptr;
+        }
+        ~Cage() { release_table(); }
+    } cage;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1606,6 +1634,76 @@ void cluster_zero(md_ctx *c)
     C.nsamples = 0;
 }
 
+// ---- cage-relative dynamics (md_cage.hpp): launches ----------------------------------------------------------------
+// The origin walk takes BOO pass 1's dispatch: dimension, record stride, tiles or 32-bit rows, the same LDS image and the
+// same check of it.  The walk's own test is the list cutoff (the rows are complete up to it); the bond criterion is the
+// lane's.
+template <int D, int RS>
+void launch_cage_origin_tile(md_ctx *c, const CageOrigin &T)
+{
+    static int attr_dev_mask = 0; // the attribute is per device: one bit per device id
+    auto k1 = k_cage_origin_tile<D, RS>;
+    if (!(attr_dev_mask & (1 << (c->device & 31)))) {
+        HIPCHK(hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
+        attr_dev_mask |= 1 << (c->device & 31);
+    }
+    if (((size_t)c->hstride + 1) * RS > MD_BOO_ROW_OFFSET_MAX || !boo_image_fits(c->hstride))
+        throw HipError("internal: the cage sampler's LDS image does not fit");
+    k1<<<c->nblk, MD_TILE, boo_image_bytes(c->hstride), c->stream>>>((int)c->n, c->dev(c->cur), c->rc * c->rc, c->nlist16.p,
+                                                                     c->maxn, c->nmax_tile.p, c->halo.p, c->hcap,
+                                                                     c->halo_count.p, c->gowner.p, T);
+}
+
+template <int D>
+void launch_cage_origin(md_ctx *c, int slot)
+{
+    md_ctx::Cage &G = c->cage;
+    const size_t n = (size_t)c->n, mn = (size_t)G.max_neigh;
+    CageOrigin T{};
+    T.n = (int)n;
+    T.max_neigh = G.max_neigh;
+    T.scaled = G.scaled;
+    T.r_neigh = G.r_neigh;
+    T.nnb = G.nnb.p + (size_t)slot * n;
+    T.nid = G.nid + (size_t)slot * mn * n;
+    T.del = G.del + (size_t)slot * mn * D * n;
+    T.sig = G.sig.p + (size_t)slot * n;
+    T.overflow = G.overflow.p;
+    if (c->use_tiles) {
+        if (c->tile_rs == 24)
+            launch_cage_origin_tile<D, 24>(c, T);
+        else if (c->tile_rs == 32)
+            launch_cage_origin_tile<D, 32>(c, T);
+        else
+            throw HipError("internal: cage sampler and tile rows disagree on the record stride");
+    } else {
+        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
+        k_cage_origin<D><<<c->nblk, MD_BLOCK, 0, c->stream>>>((int)n, c->dev(c->cur), c->rc * c->rc, c->nlist.p, c->maxn,
+                                                              c->nmax_tile.p, c->gowner.p, T);
+    }
+}
+
+template <int D>
+void launch_cage_sample(md_ctx *c, const DynParams &P, const DynBatch &B, const CageSample &A)
+{
+    md_ctx::Cage &G = c->cage;
+    hipStream_t st = c->stream;
+    dim3 g1((unsigned)((c->n + MD_DYN_BLOCK - 1) / MD_DYN_BLOCK), B.count), g2(P.nblk, B.count);
+    k_cage_disp<D><<<g1, MD_DYN_BLOCK, 0, st>>>(P, B, G.cx.p, G.ci.p, G.ox.p, G.oi.p, G.disp.p);
+    k_cage_sample<D><<<g2, MD_DYN_BLOCK, 0, st>>>(P, B, A);
+    k_dyn_reduce<<<1, MD_DYN_REDUCE_BLOCK, 0, st>>>(P, B, G.part.p, G.sums.p);
+}
+
+void cage_zero(md_ctx *c)
+{
+    md_ctx::Cage &G = c->cage;
+    HIPCHK(hipMemsetAsync(G.sums.p, 0, sizeof(double) * G.nrows * (2 + G.nq), c->stream));
+    HIPCHK(hipMemsetAsync(G.counts.p, 0, sizeof(unsigned long long) * G.nrows * MD_CAGE_NCOUNT, c->stream));
+    HIPCHK(hipMemsetAsync(G.hist.p, 0, sizeof(unsigned long long) * G.nrows * MD_CAGE_NHIST, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::fill(G.nsamples.begin(), G.nsamples.end(), (int64_t)0);
+}
+
 } // namespace
 
 struct FusedScope { // md_run / slab windows: marks the handle's state invalid when the fused loop is left by an exception
@@ -1958,6 +2056,7 @@ int md_upload(md_ctx *ctx, const double *x, const double *v, const double *f, co
             }
         ctx->uniform_sigma = uni && !getenv("MDHIP_PROBE_NONUNIFORM"); // (probe: time the 32-byte-record kernels on the bench workload)
         ctx->sigma_u = diameters[0];
+        ctx->sigma_max = *std::max_element(diameters, diameters + ctx->n);
         configure_potential(ctx);
     }
     DevState s = ctx->dev(ctx->cur);
@@ -2978,6 +3077,218 @@ int md_cluster_reset(md_ctx *ctx)
     API_BEGIN
     sampler_of(ctx, &md_ctx::cluster, "md_cluster_reset", "cluster");
     cluster_zero(ctx);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cage-relative dynamics and bond breaking (md_cage.hpp): an origin store walks the OUTER rows as md_boo_sample does and
+// never evaluates the potential -- so it serves every potential, a user's included -- and a sample reads two exported
+// frames and the table; both write only the sampler's own buffers.
+int md_cage_setup(md_ctx *ctx, int nslots, int nrows, double r_neigh, double r_break, int scaled, int max_neigh,
+                  const double *q, int nq)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_cage_setup: not available on a slab-decomposition handle");
+    char b[360];
+    check_range("md_cage_setup", "nslots", nslots, 1, MD_DYN_MAX_SLOTS);
+    if (nrows < 1) {
+        snprintf(b, sizeof b, "md_cage_setup: nrows must be >= 1, got %d", nrows);
+        throw HipError(b);
+    }
+    if (!(r_neigh > 0.0) || !std::isfinite(r_neigh)) throw HipError("md_cage_setup: r_neigh must be finite and > 0");
+    if (!std::isfinite(r_break) || !(r_break >= r_neigh)) {
+        snprintf(b, sizeof b, "md_cage_setup: r_break must be finite and >= r_neigh = %.17g, got %.17g", r_neigh, r_break);
+        throw HipError(b);
+    }
+    check_range("md_cage_setup", "scaled", scaled, 0, 1);
+    check_range("md_cage_setup", "max_neigh", max_neigh, 1, MD_CAGE_MAX_NEIGH);
+    check_range("md_cage_setup", "nq", nq, 0, MD_DYN_MAX_Q);
+    if (nq > 0 && !q) throw HipError("md_cage_setup: q is null");
+    for (int j = 0; j < nq; ++j)
+        if (!std::isfinite(q[j])) {
+            snprintf(b, sizeof b, "md_cage_setup: q[%d] must be finite", j);
+            throw HipError(b);
+        }
+    md_ctx::Cage &G = ctx->cage;
+    G.on = false;
+    G.sampled = false;
+    G.release_table();
+    const int64_t n = ctx->n;
+    const int d = ctx->dim;
+    const size_t entries = (size_t)nslots * (size_t)n * (size_t)max_neigh;
+    const size_t bytes = entries * (4 + 8 * (size_t)d);
+    // MDHIP_CAGE_ALLOC_LIMIT=bytes: a table above this size is refused as if the device had run out of memory (a debug
+    // switch: the message can be checked at a test size)
+    const char *lim = getenv("MDHIP_CAGE_ALLOC_LIMIT");
+    hipError_t ea = hipSuccess, eb = hipSuccess;
+    if (lim && bytes > (size_t)strtoull(lim, nullptr, 10))
+        ea = hipErrorOutOfMemory;
+    else {
+        ea = hipMalloc((void **)&G.nid, entries * sizeof(int32_t));
+        if (ea == hipSuccess) eb = hipMalloc((void **)&G.del, entries * d * sizeof(double));
+    }
+    if (ea != hipSuccess || eb != hipSuccess) {
+        (void)hipGetLastError();
+        G.release_table();
+        snprintf(b, sizeof b,
+                 "md_cage_setup: cannot allocate %zu bytes for the neighbour table (nslots*N*max_neigh*(4+8*d) = "
+                 "%d*%lld*%d*(4+8*%d)): %s",
+                 bytes, nslots, (long long)n, max_neigh, d, hipGetErrorString(ea != hipSuccess ? ea : eb));
+        throw HipError(b);
+    }
+    const size_t frame = (size_t)n * d;
+    const int nquant = 2 + nq;
+    const int nblk = (int)((n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
+    G.ox.alloc((size_t)nslots * frame);
+    G.oi.alloc((size_t)nslots * frame);
+    G.nnb.alloc((size_t)nslots * n);
+    G.sig.alloc((size_t)nslots * n);
+    G.cx.alloc(frame);
+    G.ci.alloc(frame);
+    G.part.alloc((size_t)MD_CAGE_MAX_BATCH * nquant * std::max(nblk, 1));
+    G.sums.alloc((size_t)nrows * nquant);
+    G.counts.alloc((size_t)nrows * MD_CAGE_NCOUNT);
+    G.hist.alloc((size_t)nrows * MD_CAGE_NHIST);
+    G.overflow.alloc(1);
+    G.l_nnb.alloc((size_t)n);
+    G.l_broken.alloc((size_t)n);
+    G.l_d2.alloc((size_t)n);
+    G.nslots = nslots;
+    G.nrows = nrows;
+    G.nq = nq;
+    G.max_neigh = max_neigh;
+    G.scaled = scaled;
+    G.r_neigh = r_neigh;
+    G.r_break = r_break;
+    G.q.assign(q, q + nq);
+    G.filled.assign(nslots, 0);
+    G.nsamples.assign(nrows, 0);
+    HIPCHK(hipMemsetAsync(G.overflow.p, 0, sizeof(unsigned long long), ctx->stream));
+    cage_zero(ctx);
+    G.on = true;
+    API_END
+}
+
+int md_cage_origin(md_ctx *ctx, int slot)
+{
+    API_BEGIN
+    md_ctx::Cage &G = sampler_of(ctx, &md_ctx::cage, "md_cage_origin", "cage");
+    require_state(ctx, "md_cage_origin");
+    char b[320];
+    if (slot < 0 || slot >= G.nslots) {
+        snprintf(b, sizeof b, "md_cage_origin: slot %d is out of range 0..%d", slot, G.nslots - 1);
+        throw HipError(b);
+    }
+    const double reach = G.r_neigh * (G.scaled ? ctx->sigma_max : 1.0);
+    if (reach > ctx->rc) {
+        snprintf(b, sizeof b,
+                 "md_cage_origin: the neighbour radius %.17g (r_neigh%s) exceeds the list cutoff %.17g (the rows are "
+                 "complete only up to it)",
+                 reach, G.scaled ? " times the largest diameter" : "", ctx->rc);
+        throw HipError(b);
+    }
+    if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
+    const size_t frame = (size_t)ctx->n * ctx->dim;
+    export_frame(ctx, G.ox.p + (size_t)slot * frame, G.oi.p + (size_t)slot * frame);
+    if (ctx->dim == 3)
+        launch_cage_origin<3>(ctx, slot);
+    else
+        launch_cage_origin<2>(ctx, slot);
+    HIPCHK(hipGetLastError());
+    G.filled[slot] = 1;
+    API_END
+}
+
+int md_cage_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int count)
+{
+    API_BEGIN
+    md_ctx::Cage &G = sampler_of(ctx, &md_ctx::cage, "md_cage_sample", "cage");
+    require_state(ctx, "md_cage_sample");
+    check_batch("md_cage_sample", slots, rows, count, G.nslots, G.nrows, G.filled,
+                "store an origin with md_cage_origin first");
+    if (count == 0) return 0;
+    const size_t n = (size_t)ctx->n;
+    G.disp.ensure((size_t)std::min(count, MD_CAGE_MAX_BATCH) * ctx->dim * n);
+    export_frame(ctx, G.cx.p, G.ci.p);
+    DynParams P{};
+    P.n = (int)ctx->n;
+    P.dim = ctx->dim;
+    P.nq = G.nq;
+    P.nblk = (int)((ctx->n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
+    P.nquant = 2 + G.nq;
+    for (int c = 0; c < 9; ++c) P.U[c] = ctx->A[c];
+    for (int j = 0; j < G.nq; ++j) P.q[j] = G.q[j];
+    CageSample A{};
+    A.max_neigh = G.max_neigh;
+    A.scaled = G.scaled;
+    A.r_break = G.r_break;
+    A.nnb = G.nnb.p;
+    A.nid = G.nid;
+    A.del = G.del;
+    A.sig = G.sig.p;
+    A.disp = G.disp.p;
+    A.part = G.part.p;
+    A.counts = G.counts.p;
+    A.hist = G.hist.p;
+    A.o_nnb = G.l_nnb.p;
+    A.o_broken = G.l_broken.p;
+    A.o_d2 = G.l_d2.p;
+    for (int i0 = 0; i0 < count; i0 += MD_CAGE_MAX_BATCH) {
+        DynBatch B{};
+        B.count = std::min(count - i0, MD_CAGE_MAX_BATCH);
+        for (int i = 0; i < B.count; ++i) {
+            B.slot[i] = slots[i0 + i];
+            B.row[i] = rows[i0 + i];
+        }
+        A.keep = (i0 + B.count == count) ? B.count - 1 : -1; // the call's last entry stays readable (md_cage_particles)
+        if (ctx->dim == 3)
+            launch_cage_sample<3>(ctx, P, B, A);
+        else
+            launch_cage_sample<2>(ctx, P, B, A);
+        HIPCHK(hipGetLastError());
+        for (int i = 0; i < B.count; ++i) ++G.nsamples[B.row[i]];
+    }
+    G.sampled = true;
+    API_END
+}
+
+int md_cage_particles(md_ctx *ctx, int32_t *nnb, double *d2cr, int32_t *broken)
+{
+    API_BEGIN
+    md_ctx::Cage &G = sampler_of(ctx, &md_ctx::cage, "md_cage_particles", "cage");
+    if (!G.sampled) throw HipError("md_cage_particles: no sample taken yet (call md_cage_sample first)");
+    const size_t n = (size_t)ctx->n;
+    hipStream_t st = ctx->stream;
+    if (nnb) HIPCHK(hipMemcpyAsync(nnb, G.l_nnb.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (d2cr) HIPCHK(hipMemcpyAsync(d2cr, G.l_d2.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (broken) HIPCHK(hipMemcpyAsync(broken, G.l_broken.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_cage_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *counts, int64_t *hist_broken, int64_t *overflow)
+{
+    API_BEGIN
+    md_ctx::Cage &G = sampler_of(ctx, &md_ctx::cage, "md_cage_read", "cage");
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the device words are read back as int64_t");
+    hipStream_t st = ctx->stream;
+    const size_t nr = (size_t)G.nrows;
+    if (sums) HIPCHK(hipMemcpyAsync(sums, G.sums.p, sizeof(double) * nr * (2 + G.nq), hipMemcpyDeviceToHost, st));
+    if (counts) HIPCHK(hipMemcpyAsync(counts, G.counts.p, sizeof(int64_t) * nr * MD_CAGE_NCOUNT, hipMemcpyDeviceToHost, st));
+    if (hist_broken)
+        HIPCHK(hipMemcpyAsync(hist_broken, G.hist.p, sizeof(int64_t) * nr * MD_CAGE_NHIST, hipMemcpyDeviceToHost, st));
+    if (overflow) HIPCHK(hipMemcpyAsync(overflow, G.overflow.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nsamples)
+        for (int r = 0; r < G.nrows; ++r) nsamples[r] = G.nsamples[r];
+    API_END
+}
+
+int md_cage_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    sampler_of(ctx, &md_ctx::cage, "md_cage_reset", "cage");
+    cage_zero(ctx);
     API_END
 }
 

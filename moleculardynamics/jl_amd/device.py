@@ -380,6 +380,56 @@ class MDDevice:
     def cluster_reset(self):
         self._chk(self._L.md_cluster_reset(self._h))
 
+    # -- cage-relative dynamics and bond breaking ------------------------------------------
+    def cage_setup(self, nslots, nrows, r_neigh, r_break=None, scaled=False, max_neigh=16, q=()):
+        """Allocate the device cage sampler (md_cage_setup): nslots origin slots with a neighbour table of max_neigh <= 32
+        entries per particle (bonds d2 < (r_neigh s)^2 at the origin, s = sigma_ij if scaled else 1; broken when
+        d2 >= (r_break s)^2 at the sample), nrows zeroed rows of {sum d2, sum d4, sum s(q) per q} of the cage-relative
+        displacement, the three counts and the broken-bond histogram."""
+        qa = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+        r_break = r_neigh if r_break is None else r_break
+        self._chk(self._L.md_cage_setup(self._h, int(nslots), int(nrows), float(r_neigh), float(r_break), int(bool(scaled)),
+                                        int(max_neigh), _dp(qa) if qa.size else None, int(qa.size)))
+        self._cage_shape = (int(nrows), int(qa.size))
+
+    def cage_origin(self, slot):
+        """Store the current frame and its neighbour table in `slot` (does not wait; builds the list if it is not valid)."""
+        self._chk(self._L.md_cage_origin(self._h, int(slot)))
+
+    def cage_sample(self, slots, rows):
+        """Export the current frame once and add one sample per (slots[i], rows[i]): this frame against the origin and the
+        neighbours stored in slots[i], accumulated into rows[i] (does not wait, changes no state)."""
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        if s.shape != r.shape:
+            raise ValueError("slots and rows must have the same length")
+        self._chk(self._L.md_cage_sample(self._h, _ip(s), _ip(r), int(s.size)))
+
+    def cage_particles(self):
+        """(nnb int32[N], d2cr float64[N], broken int32[N]) of the last (slot, row) of the last cage_sample call, in
+        particle-id order: the neighbours kept at the origin, |Del^CR|^2 and the broken bonds; waits."""
+        nnb, broken = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        d2 = np.zeros(self.n)
+        self._chk(self._L.md_cage_particles(self._h, _ip(nnb), _dp(d2), _ip(broken)))
+        return nnb, d2, broken
+
+    def cage_read(self):
+        """(nsamples int64[nrows], sums float64[nrows, 2 + nq], counts int64[nrows, 3], hist_broken int64[nrows, 33],
+        overflow), summed since setup / reset (overflow: since setup); waits."""
+        nrows, nq = getattr(self, "_cage_shape", (0, 0))
+        ns = np.zeros(max(nrows, 1), dtype=np.int64)
+        sums = np.zeros((max(nrows, 1), 2 + nq))
+        counts = np.zeros((max(nrows, 1), 3), dtype=np.int64)
+        hist = np.zeros((max(nrows, 1), 33), dtype=np.int64)
+        ov = C.c_int64()
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.md_cage_read(self._h, ns.ctypes.data_as(i64), _dp(sums), counts.ctypes.data_as(i64),
+                                       hist.ctypes.data_as(i64), C.byref(ov)))
+        return ns[:nrows], sums[:nrows], counts[:nrows], hist[:nrows], ov.value
+
+    def cage_reset(self):
+        self._chk(self._L.md_cage_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""
