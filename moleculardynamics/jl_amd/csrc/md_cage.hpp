@@ -2,16 +2,17 @@
 // displacement of a particle relative to the mean displacement of the neighbours it had at the time origin (its MSD,
 // fourth moment and F_s), and the fraction of origin bonds still shorter than a break radius (Yamamoto-Onuki's C_B).
 //
-// md_cage_origin = one k_export into the slot's frame, then one walk of the OUTER rows (md_boo.hpp's walks, reused):
-//   k_cage_origin_tile / k_cage_origin   one lane per particle; every row entry that passes the bond criterion with r_neigh
-//                                        appends (id_j, del_ij) to the entry list of particle id_i, in row order, up to
-//                                        max_neigh entries; the hits beyond are counted in `overflow`
+// md_cage_origin = one k_export into the slot's frame, then one walk of the OUTER rows (md_rowwalk.hpp's kernel pair):
+//   k_rows_tile / k_rows<CageOriginLane>   one lane per particle; every row entry that passes the bond criterion with
+//                                          r_neigh appends (id_j, del_ij) to the entry list of particle id_i, in row order,
+//                                          up to max_neigh entries; the hits beyond are counted in `overflow`
 // md_cage_sample = one k_export of the current frame, then per batch of up to MD_CAGE_MAX_BATCH (slot, row) pairs:
-//   k_cage_disp     over particle ids: the displacement Del_i since the slot's origin (k_dyn_sample's formula), written
+//   k_cage_disp     over particle ids: the displacement Del_i since the slot's origin (md_dyn's dyn_disp), written
 //                   component-major by id
 //   k_cage_sample   over particle ids: gathers Del_j of the n_i entries by id, the cage-relative displacement, d2, d4 and
 //                   the cosine sums; the bond vector at t, b = del_ij + (Del_j - Del_i), against r_break; fp64 block
-//                   partials in md_dyn's fixed tree, the integers in LDS counters flushed with 64-bit integer atomics
+//                   partials in md_dyn's fixed tree (dyn_store_part), the integers in LDS counters flushed with 64-bit
+//                   integer atomics
 //   k_dyn_reduce    (md_dyn.hpp, as it is) the partials of every sample summed in block order into the rows
 // Nothing waits for the device and nothing of the handle is written.
 //
@@ -22,7 +23,7 @@
 // d2 < (r s) (r s), s = sigma_ij (scaled) or 1.0; d2 = d2_ref of the vector.  Del as in md_dyn.hpp (no fma);
 // m_i = (sum_k Del_{j_k}) / n_i in entry order, Del^CR_i = Del_i - m_i, s_i(q) = sum_c cos(q Del^CR_c).
 #pragma once
-#include "md_boo.hpp"
+#include "md_rowwalk.hpp"
 #include "md_dyn.hpp"
 
 #define MD_CAGE_MAX_NEIGH 32
@@ -50,12 +51,22 @@ __device__ __forceinline__ bool cage_bonded(double d2, double r, double s)
 
 template <int D>
 struct CageOriginLane {
+    using Args = CageOrigin;
     size_t idi;
     double sig_i;
     int hits;
-    __device__ __forceinline__ void add(const CageOrigin &T, const DevState &s, bool active, double dx, double dy, double dz,
-                                        double d2, uint32_t own)
+    bool active;
+    __device__ __forceinline__ void begin(const Args &, const DevState &s, int, int kk, bool active_, const double4 &pi)
     {
+        idi = (size_t)s.id[kk];
+        sig_i = pi.w;
+        hits = 0;
+        active = active_;
+    }
+    __device__ __forceinline__ void visit(const Args &T, const DevState &s, bool hit, double dx, double dy, double dz,
+                                          double d2, uint32_t own)
+    {
+        if (!hit) return;
         // (own is an owned slot here: the walk resolved it, and the sentinel is never within the list cutoff)
         double sc = 1.0;
         if (T.scaled) sc = (sig_i + s.pos[own].w) / 2.0;
@@ -69,7 +80,7 @@ struct CageOriginLane {
         }
         ++hits;
     }
-    __device__ __forceinline__ void store(const CageOrigin &T, bool active)
+    __device__ __forceinline__ void end(const Args &T, int, bool, int)
     {
         if (!active) return;
         const int kept = hits < T.max_neigh ? hits : T.max_neigh;
@@ -79,54 +90,9 @@ struct CageOriginLane {
     }
 };
 
-template <int D, int RS>
-__global__ void __launch_bounds__(MD_TILE)
-    k_cage_origin_tile(int n, DevState s, double rl2, const uint16_t *__restrict__ nlist16, int maxn,
-                       const int32_t *__restrict__ nmax_tile, const uint32_t *__restrict__ halo, int hcap,
-                       const int32_t *__restrict__ halo_count, const int32_t *__restrict__ gowner, CageOrigin T)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    int k = bid * MD_TILE + threadIdx.x;
-    bool active = k < n;
-    int kk = active ? k : n - 1;
-    int lane = threadIdx.x & 63;
-    int wt = bid * (MD_TILE / 64) + (threadIdx.x >> 6);
-    const ushort4 *row4 = (const ushort4 *)(nlist16 + ((size_t)wt * maxn) * 64) + lane;
-    const int m = __builtin_amdgcn_readfirstlane(nmax_tile[wt]);
-    double4 pi = s.pos[kk];
-    boo_stage<D>(smem, n, s, halo + (size_t)bid * hcap, halo_count[bid], gowner);
-    CageOriginLane<D> ln{(size_t)s.id[kk], pi.w, 0};
-    boo_walk_tile<D, RS>(smem, row4, m, pi, rl2, [&](bool hit, double dx, double dy, double dz, double d2, uint32_t own) {
-        if (hit) ln.add(T, s, active, dx, dy, dz, d2, own);
-    });
-    ln.store(T, active);
-}
-
-template <int D>
-__global__ void __launch_bounds__(MD_BLOCK)
-    k_cage_origin(int n, DevState s, double rl2, const uint32_t *__restrict__ nlist, int maxn,
-                  const int32_t *__restrict__ nmax_tile, const int32_t *__restrict__ gowner, CageOrigin T)
-{
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    int k = bid * MD_BLOCK + threadIdx.x;
-    bool active = k < n;
-    int kk = active ? k : n - 1;
-    int lane = threadIdx.x & 63;
-    int tile = kk >> 6;
-    const uint32_t *row = nlist + ((size_t)tile * maxn) * 64 + lane;
-    int m = nmax_tile[tile];
-    double4 pi = s.pos[kk];
-    CageOriginLane<D> ln{(size_t)s.id[kk], pi.w, 0};
-    boo_walk_global<D>(n, s, row, m, pi, rl2, gowner, [&](bool hit, double dx, double dy, double dz, double d2, uint32_t own) {
-        if (hit) ln.add(T, s, active, dx, dy, dz, d2, own);
-    });
-    ln.store(T, active);
-}
-
 // ------------------------------------------------------------------------------------------
-// Pass 1 of a sample: Del_i of every id against the origin of every slot of the batch (blockIdx.y), k_dyn_sample's formula:
-// the wrapped difference first, the lattice translation of the exact image difference added after, no fma.
+// Pass 1 of a sample: Del_i of every id against the origin of every slot of the batch (blockIdx.y), md_dyn's dyn_disp: the
+// wrapped difference first, the lattice translation of the exact image difference added after, no fma.
 // disp[(smp d + c) N + id]
 // ------------------------------------------------------------------------------------------
 template <int D>
@@ -141,16 +107,10 @@ __global__ void __launch_bounds__(MD_DYN_BLOCK)
     const size_t frame = (size_t)P.n * D;
     const double *__restrict__ xo = xo_all + (size_t)B.slot[smp] * frame;
     const int32_t *__restrict__ no = no_all + (size_t)B.slot[smp] * frame;
-    const size_t o = (size_t)i * D;
-    double dn[3] = {0.0, 0.0, 0.0};
+    double del[3] = {0.0, 0.0, 0.0};
+    dyn_disp<D>(P, xc, nc, xo, no, i, del);
 #pragma unroll
-    for (int c = 0; c < D; ++c) dn[c] = (double)nc[o + c] - (double)no[o + c];
-#pragma unroll
-    for (int c = 0; c < D; ++c) {
-        double t = P.U[c * 3 + 0] * dn[0] + P.U[c * 3 + 1] * dn[1];
-        if constexpr (D == 3) t = t + P.U[c * 3 + 2] * dn[2];
-        disp[((size_t)smp * D + c) * P.n + i] = (xc[o + c] - xo[o + c]) + t;
-    }
+    for (int c = 0; c < D; ++c) disp[((size_t)smp * D + c) * P.n + i] = del[c];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -263,13 +223,7 @@ __global__ void __launch_bounds__(MD_DYN_BLOCK)
         if (lane == 0) wsum[wave][2 + j] = w;
     }
     __syncthreads();
-    if (threadIdx.x < P.nquant) {
-        const int j = threadIdx.x;
-        double t = wsum[0][j];
-#pragma unroll
-        for (int w = 1; w < MD_DYN_BLOCK / 64; ++w) t = t + wsum[w][j];
-        A.part[((size_t)smp * P.nquant + j) * P.nblk + blockIdx.x] = t;
-    }
+    dyn_store_part(P, wsum, smp, A.part);
     if (threadIdx.x < MD_CAGE_NCOUNT + MD_CAGE_NHIST) {
         const uint32_t v = cnt[threadIdx.x];
         if (v) {

@@ -4,8 +4,8 @@
 // One sample = a fixed number of launches on the handle's stream, whatever the frame looks like, no host wait:
 //   k_cl_mask                    SOLID only: BOO's per-slot nconn of ITS frame -> a by-particle-id member mask
 //   k_cl_init                    parent[slot] = slot for members, CL_NONE otherwise; count = 0, minid = INT_MAX
-//   k_cl_hook_tile / k_cl_hook   BOO pass 1's staging, walk and acceptance test; every hit with owner < slot and both ends
-//                                members is one union; the lane also counts its degree (block partials)
+//   k_rows_tile / k_rows<ClLane> md_rowwalk.hpp's staging, walk and acceptance test; every hit with owner < slot and both
+//                                ends members is one union; the lane also counts its degree (block partials)
 //   k_cl_flatten                 root[slot] = find(slot); count[root] += 1; minid[root] = min(id)
 //   k_cl_stats                   roots only: the size histogram, block partials, the block's top two (size, ~label) keys
 //   k_cl_finish                  one block: the partials -> fr, sum_fr += fr, series[m] = fr
@@ -13,7 +13,7 @@
 // Every result is an integer and a function of the frame alone: integer sums are exact in any order, a label is the
 // smallest particle id of the cluster, not a slot.  No floating-point atomics.
 //
-// The union (k_cl_hook*, cl_union below) is lock-free.  parent[] is a forest over the slots; every edge points to a
+// The union (ClLane, cl_union below) is lock-free.  parent[] is a forest over the slots; every edge points to a
 // SMALLER slot of the same component, a root points to itself.  Three operations touch it, all agent-scope relaxed atomics
 // (__hip_atomic_load / compare_exchange / fetch_min, __HIP_MEMORY_SCOPE_AGENT) -- the kernel has no plain load of
 // parent[], because on this chip a CU's vector L1 is never refreshed by another CU's stores and the XCD L2s are not
@@ -35,7 +35,7 @@
 // kernel has ended every bond's two ends have been through a union that ended on a common slot, so the trees are the
 // components; k_cl_flatten, a new launch, sees all of it and only reads parent[].
 #pragma once
-#include "md_boo.hpp"
+#include "md_rowwalk.hpp"
 
 #define MD_CL_MAX_SIZE 65536
 #define MD_CL_MAX_SERIES (1 << 20)
@@ -116,78 +116,43 @@ __global__ void __launch_bounds__(MD_BLOCK)
 }
 
 // ------------------------------------------------------------------------------------------
-// The hooks: BOO pass 1's walk.  deg_part[bid] = the block's sum of degrees.
+// The hooks, a lane of md_rowwalk.hpp's walk.  deg_part[bid] = the block's sum of degrees.
 // ------------------------------------------------------------------------------------------
-struct ClLane {
-    uint32_t k;
-    bool member;
-    unsigned deg;
-    uint32_t me; // the lowest ancestor of k this lane has met: the next union starts there
-    __device__ __forceinline__ void hit(uint32_t own, const unsigned char *__restrict__ mem, uint32_t *parent)
-    {
-        if (!member || own == k || !mem[own]) return;
-        ++deg;
-        if (own < k) me = cl_union(parent, me, own);
-    }
-    // k's own edge, shortened to what the walk found (me != k: k has been seen with a parent, it is no root)
-    __device__ __forceinline__ void done(uint32_t *parent)
-    {
-        if (member && me != k) __hip_atomic_fetch_min(parent + k, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+struct ClArgs {
+    const unsigned char *mem;
+    uint32_t *parent;
+    cl_u64 *deg_part;
 };
 
-template <int D, int RS>
-__global__ void __launch_bounds__(MD_TILE)
-    k_cl_hook_tile(int n, DevState s, double rb2, const uint16_t *__restrict__ nlist16, int maxn,
-                   const int32_t *__restrict__ nmax_tile, const uint32_t *__restrict__ halo, int hcap,
-                   const int32_t *__restrict__ halo_count, const int32_t *__restrict__ gowner,
-                   const unsigned char *__restrict__ mem, uint32_t *parent, cl_u64 *__restrict__ deg_part)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ cl_u64 red[16];
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    int k = bid * MD_TILE + threadIdx.x;
-    bool active = k < n;
-    int kk = active ? k : n - 1;
-    int lane = threadIdx.x & 63;
-    int wt = bid * (MD_TILE / 64) + (threadIdx.x >> 6);
-    const ushort4 *row4 = (const ushort4 *)(nlist16 + ((size_t)wt * maxn) * 64) + lane;
-    const int m = __builtin_amdgcn_readfirstlane(nmax_tile[wt]);
-    double4 pi = s.pos[kk];
-    boo_stage<D>(smem, n, s, halo + (size_t)bid * hcap, halo_count[bid], gowner);
-    ClLane ln{(uint32_t)kk, active && mem[kk] != 0, 0u, (uint32_t)kk};
-    boo_walk_tile<D, RS>(smem, row4, m, pi, rb2, [&](bool hit, double, double, double, double, uint32_t own) {
-        if (hit) ln.hit(own, mem, parent);
-    });
-    ln.done(parent);
-    cl_u64 t = cl_block_sum((cl_u64)ln.deg, red);
-    if (threadIdx.x == 0) deg_part[bid] = t;
-}
-
-template <int D>
-__global__ void __launch_bounds__(MD_BLOCK)
-    k_cl_hook(int n, DevState s, double rb2, const uint32_t *__restrict__ nlist, int maxn,
-              const int32_t *__restrict__ nmax_tile, const int32_t *__restrict__ gowner,
-              const unsigned char *__restrict__ mem, uint32_t *parent, cl_u64 *__restrict__ deg_part)
-{
-    __shared__ cl_u64 red[16];
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    int k = bid * MD_BLOCK + threadIdx.x;
-    bool active = k < n;
-    int kk = active ? k : n - 1;
-    int lane = threadIdx.x & 63;
-    int tile = kk >> 6;
-    const uint32_t *row = nlist + ((size_t)tile * maxn) * 64 + lane;
-    int m = nmax_tile[tile];
-    double4 pi = s.pos[kk];
-    ClLane ln{(uint32_t)kk, active && mem[kk] != 0, 0u, (uint32_t)kk};
-    boo_walk_global<D>(n, s, row, m, pi, rb2, gowner, [&](bool hit, double, double, double, double, uint32_t own) {
-        if (hit) ln.hit(own, mem, parent);
-    });
-    ln.done(parent);
-    cl_u64 t = cl_block_sum((cl_u64)ln.deg, red);
-    if (threadIdx.x == 0) deg_part[bid] = t;
-}
+struct ClLane {
+    using Args = ClArgs;
+    uint32_t kk;
+    bool member;
+    unsigned deg;
+    uint32_t me; // the lowest ancestor of kk this lane has met: the next union starts there
+    __device__ __forceinline__ void begin(const Args &A, const DevState &, int, int kk_, bool active, const double4 &)
+    {
+        kk = (uint32_t)kk_;
+        member = active && A.mem[kk_] != 0;
+        deg = 0u;
+        me = (uint32_t)kk_;
+    }
+    __device__ __forceinline__ void visit(const Args &A, const DevState &, bool hit, double, double, double, double,
+                                          uint32_t own)
+    {
+        if (!hit || !member || own == kk || !A.mem[own]) return;
+        ++deg;
+        if (own < kk) me = cl_union(A.parent, me, own);
+    }
+    __device__ __forceinline__ void end(const Args &A, int, bool, int bid)
+    {
+        __shared__ cl_u64 red[16];
+        // kk's own edge, shortened to what the walk found (me != kk: kk has been seen with a parent, it is no root)
+        if (member && me != kk) __hip_atomic_fetch_min(A.parent + kk, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cl_u64 t = cl_block_sum((cl_u64)deg, red);
+        if (threadIdx.x == 0) A.deg_part[bid] = t;
+    }
+};
 
 // ------------------------------------------------------------------------------------------
 // A new launch: every hook is visible.  parent[] is only read here; the roots go to an array of their own.  One global

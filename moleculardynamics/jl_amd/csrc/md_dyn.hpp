@@ -47,6 +47,40 @@ __device__ __forceinline__ double dyn_wave_sum(double v)
     return v; // (lane 0)
 }
 
+// The displacement of particle id i between the frames (xo, no) and (xc, nc): del_c, c < D, as the contract above forms it
+template <int D>
+__device__ __forceinline__ void dyn_disp(const DynParams &P, const double *__restrict__ xc, const int32_t *__restrict__ nc,
+                                         const double *__restrict__ xo, const int32_t *__restrict__ no, int i,
+                                         double (&del)[3])
+{
+#pragma clang fp contract(off)
+    const size_t o = (size_t)i * D;
+    double dn[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int c = 0; c < D; ++c) dn[c] = (double)nc[o + c] - (double)no[o + c];
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        double t = P.U[c * 3 + 0] * dn[0] + P.U[c * 3 + 1] * dn[1];
+        if constexpr (D == 3) t = t + P.U[c * 3 + 2] * dn[2];
+        del[c] = (xc[o + c] - xo[o + c]) + t;
+    }
+}
+
+// The block's last step of the fixed tree: the wave sums of every quantity (written by lane 0 of each wave, a barrier
+// since) added in wave order, part[(smp nquant + j) nblk + block] = the block partial of quantity j
+__device__ __forceinline__ void dyn_store_part(const DynParams &P, const double (*wsum)[2 + MD_DYN_MAX_Q], int smp,
+                                               double *__restrict__ part)
+{
+#pragma clang fp contract(off)
+    if (threadIdx.x < P.nquant) {
+        const int j = threadIdx.x;
+        double s = wsum[0][j];
+#pragma unroll
+        for (int w = 1; w < MD_DYN_BLOCK / 64; ++w) s = s + wsum[w][j];
+        part[((size_t)smp * P.nquant + j) * P.nblk + blockIdx.x] = s;
+    }
+}
+
 // One sample per blockIdx.y.
 template <int D>
 __global__ void __launch_bounds__(MD_DYN_BLOCK)
@@ -78,16 +112,8 @@ __global__ void __launch_bounds__(MD_DYN_BLOCK)
         const bool act = i < P.n;
         double d2 = 0.0;
         if (act) {
-            const size_t o = (size_t)i * D;
-            double dn[3] = {0.0, 0.0, 0.0}, del[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-            for (int c = 0; c < D; ++c) dn[c] = (double)nc[o + c] - (double)no[o + c];
-#pragma unroll
-            for (int c = 0; c < D; ++c) {
-                double t = P.U[c * 3 + 0] * dn[0] + P.U[c * 3 + 1] * dn[1];
-                if constexpr (D == 3) t = t + P.U[c * 3 + 2] * dn[2];
-                del[c] = (xc[o + c] - xo[o + c]) + t;
-            }
+            double del[3] = {0.0, 0.0, 0.0};
+            dyn_disp<D>(P, xc, nc, xo, no, i, del);
             d2 = d2_ref<D>(del[0], del[1], del[2]);
             acc[0] += d2;
             acc[1] += d2 * d2;
@@ -119,13 +145,7 @@ __global__ void __launch_bounds__(MD_DYN_BLOCK)
         }
     }
     __syncthreads();
-    if (threadIdx.x < P.nquant) {
-        const int j = threadIdx.x;
-        double s = wsum[0][j];
-#pragma unroll
-        for (int w = 1; w < MD_DYN_BLOCK / 64; ++w) s = s + wsum[w][j];
-        part[((size_t)smp * P.nquant + j) * P.nblk + blockIdx.x] = s;
-    }
+    dyn_store_part(P, wsum, smp, part);
     if (nbins > 0) {
         unsigned long long *h = hist + (size_t)B.row[smp] * nbins;
         for (int b = threadIdx.x; b < nbins; b += MD_DYN_BLOCK) {

@@ -1473,39 +1473,40 @@ void stress_zero(md_ctx *c)
     S.nsamples = 0;
 }
 
-// ---- bond-orientational order sampler (md_boo.hpp): launches -----------------------------------------------------
-// The sampler's LDS image has 32-byte records whatever the force kernel's stride is.  The rows address the force kernel's
-// image with 16-bit byte offsets, (H + 1) * stride <= 65535 for every tile (k_build_tile / k_tile_localize refuse a
-// larger halo), so (H + 1) * 32 <= 87360 bytes for a 24-byte handle and 65536 for a 32-byte one: it always fits below the
-// force kernel's limit (md_boo.hpp asserts the arithmetic) and a tiled handle never needs another walk.  The launch
-// checks the premise on the handle -- the offsets fit 16 bits -- and the conclusion, and refuses otherwise.
-inline size_t boo_image_bytes(int max_halo) { return (((size_t)max_halo + 1) * 32 + 15) & ~(size_t)15; }
-inline bool boo_image_fits(int max_halo) { return boo_image_bytes(max_halo) <= (size_t)MD_BOO_LDS_LIMIT; }
-
-template <int D, int L, int RS>
-void launch_boo_tile(md_ctx *c, const BooAvgArgs &A)
+// ---- the row-walking samplers (md_rowwalk.hpp): one launch decision ---------------------------------------------------
+// Tiles or 32-bit rows, the record stride, and -- tiled -- the walk's LDS image.  The rows address the force kernel's image
+// with 16-bit byte offsets, (H + 1) * stride <= 65535 for every tile (k_build_tile / k_tile_localize refuse a larger
+// halo), so the walk's own 32-byte image always fits below the force kernel's limit (md_rowwalk.hpp asserts the
+// arithmetic).  The launch checks the premise on the handle -- the offsets fit 16 bits -- and the conclusion, and refuses
+// otherwise.  r2 is the pass's own walk radius; `who` names the sampler in the refusals.
+template <int D, class Lane>
+void launch_rows(md_ctx *c, double r2, const typename Lane::Args &A, const char *who)
 {
-    md_ctx::Boo &B = c->boo;
-    int n = (int)c->n;
-    int nb = c->nblk;
+    const int n = (int)c->n;
     DevState s = c->dev(c->cur);
-    static int attr_dev_mask = 0; // the attribute is per device: one bit per device id
-    auto k1 = k_boo_qlm_tile<D, L, RS>;
-    auto k2 = k_boo_avg_tile<D, L, RS>;
-    if (!(attr_dev_mask & (1 << (c->device & 31)))) {
-        HIPCHK(hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
-        HIPCHK(hipFuncSetAttribute((const void *)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
-        attr_dev_mask |= 1 << (c->device & 31);
+    if (!c->use_tiles) {
+        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
+        k_rows<D, Lane><<<c->nblk, MD_BLOCK, 0, c->stream>>>(RowsGlobal{n, s, c->nlist.p, c->maxn, c->nmax_tile.p, c->gowner.p},
+                                                             r2, A);
+        return;
     }
-    if (((size_t)c->hstride + 1) * RS > MD_BOO_ROW_OFFSET_MAX || !boo_image_fits(c->hstride))
-        throw HipError("internal: the bond-order sampler's LDS image does not fit");
-    const size_t lds = boo_image_bytes(c->hstride);
-    k1<<<nb, MD_TILE, lds, c->stream>>>(n, s, B.rn2, B.order, B.coef, c->nlist16.p, c->maxn, c->nmax_tile.p, c->halo.p,
-                                        c->hcap, c->halo_count.p, c->gowner.p, A.cap, B.qlm.p, B.norm.p, B.nnb.p);
-    k2<<<nb, MD_TILE, lds, c->stream>>>(n, s, B.rn2, B.coef, c->nlist16.p, c->maxn, c->nmax_tile.p, c->halo.p, c->hcap,
-                                        c->halo_count.p, c->gowner.p, A);
+    void (*kern)(RowsTile, double, typename Lane::Args) = c->tile_rs == 24   ? k_rows_tile<D, 24, Lane>
+                                                          : c->tile_rs == 32 ? k_rows_tile<D, 32, Lane>
+                                                                             : nullptr;
+    if (!kern) throw HipError(std::string("internal: ") + who + " sampler and tile rows disagree on the record stride");
+    static int attr_dev_mask[2] = {0, 0}; // the attribute is per kernel (stride 24, 32) and per device: one bit per device id
+    int &mask = attr_dev_mask[c->tile_rs == 32];
+    if (!(mask & (1 << (c->device & 31)))) {
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_ROW_LDS_LIMIT));
+        mask |= 1 << (c->device & 31);
+    }
+    if (((size_t)c->hstride + 1) * c->tile_rs > MD_ROW_OFFSET_MAX || !row_image_fits(c->hstride))
+        throw HipError(std::string("internal: the ") + who + " sampler's LDS image does not fit");
+    kern<<<c->nblk, MD_TILE, row_image_bytes(c->hstride), c->stream>>>(
+        RowsTile{n, s, c->nlist16.p, c->maxn, c->nmax_tile.p, c->halo.p, c->hcap, c->halo_count.p, c->gowner.p}, r2, A);
 }
 
+// ---- bond-orientational order sampler (md_boo.hpp): launches -----------------------------------------------------
 template <int D, int L>
 void launch_boo(md_ctx *c)
 {
@@ -1519,6 +1520,7 @@ void launch_boo(md_ctx *c)
     A.nbins = B.nbins;
     A.cap = n;
     A.nblk = nb;
+    A.bc = B.coef;
     A.qlm = B.qlm.p;
     A.norm = B.norm.p;
     A.nnb = B.nnb.p;
@@ -1527,21 +1529,8 @@ void launch_boo(md_ctx *c)
     A.nconn = B.nconn.p;
     A.hist = B.hist.p;
     A.partials = B.part.p;
-    if (c->use_tiles) {
-        if (c->tile_rs == 24)
-            launch_boo_tile<D, L, 24>(c, A);
-        else if (c->tile_rs == 32)
-            launch_boo_tile<D, L, 32>(c, A);
-        else
-            throw HipError("internal: bond-order sampler and tile rows disagree on the record stride");
-    } else {
-        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
-        DevState s = c->dev(c->cur);
-        k_boo_qlm<D, L><<<nb, MD_BLOCK, 0, c->stream>>>(n, s, B.rn2, B.order, B.coef, c->nlist.p, c->maxn, c->nmax_tile.p,
-                                                        c->gowner.p, A.cap, B.qlm.p, B.norm.p, B.nnb.p);
-        k_boo_avg<D, L><<<nb, MD_BLOCK, 0, c->stream>>>(n, s, B.rn2, B.coef, c->nlist.p, c->maxn, c->nmax_tile.p,
-                                                        c->gowner.p, A);
-    }
+    launch_rows<D, BooQlmLane<D, L>>(c, B.rn2, BooQlmArgs{B.order, n, B.coef, B.qlm.p, B.norm.p, B.nnb.p}, "bond-order");
+    launch_rows<D, BooAvgLane<D, L>>(c, B.rn2, A, "bond-order");
     k_boo_finish<D, L><<<1, 1024, 0, c->stream>>>(nb, B.part.p, B.coef, (long long)B.nsamples, (long long)B.nseries,
                                                   B.sum_fr.p, B.series.p);
 }
@@ -1575,25 +1564,6 @@ void boo_zero(md_ctx *c)
 }
 
 // ---- cluster sampler (md_cluster.hpp): launches -------------------------------------------------------------------
-// The hooks take BOO pass 1's dispatch: dimension, record stride, tiles or 32-bit rows, the same LDS image and the same
-// check of it.
-template <int D, int RS>
-void launch_cl_hook_tile(md_ctx *c)
-{
-    md_ctx::Cluster &C = c->cluster;
-    static int attr_dev_mask = 0; // the attribute is per device: one bit per device id
-    auto k1 = k_cl_hook_tile<D, RS>;
-    if (!(attr_dev_mask & (1 << (c->device & 31)))) {
-        HIPCHK(hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
-        attr_dev_mask |= 1 << (c->device & 31);
-    }
-    if (((size_t)c->hstride + 1) * RS > MD_BOO_ROW_OFFSET_MAX || !boo_image_fits(c->hstride))
-        throw HipError("internal: the cluster sampler's LDS image does not fit");
-    k1<<<c->nblk, MD_TILE, boo_image_bytes(c->hstride), c->stream>>>((int)c->n, c->dev(c->cur), C.rb2, c->nlist16.p, c->maxn,
-                                                                     c->nmax_tile.p, c->halo.p, c->hcap, c->halo_count.p,
-                                                                     c->gowner.p, C.mem.p, C.parent.p, C.deg.p);
-}
-
 template <int D>
 void launch_cluster(md_ctx *c)
 {
@@ -1606,18 +1576,7 @@ void launch_cluster(md_ctx *c)
     const bool solid = C.members == MD_CLUSTER_SOLID;
     if (solid) k_cl_mask<<<nb, MD_BLOCK, 0, st>>>(n, B.ids.p, B.nconn.p, B.min_conn, C.mask.p);
     k_cl_init<<<nb, MD_BLOCK, 0, st>>>(n, s.id, solid ? C.mask.p : nullptr, C.parent.p, C.mem.p, C.count.p, C.minid.p);
-    if (c->use_tiles) {
-        if (c->tile_rs == 24)
-            launch_cl_hook_tile<D, 24>(c);
-        else if (c->tile_rs == 32)
-            launch_cl_hook_tile<D, 32>(c);
-        else
-            throw HipError("internal: cluster sampler and tile rows disagree on the record stride");
-    } else {
-        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
-        k_cl_hook<D><<<nh, MD_BLOCK, 0, st>>>(n, s, C.rb2, c->nlist.p, c->maxn, c->nmax_tile.p, c->gowner.p, C.mem.p, C.parent.p,
-                                              C.deg.p);
-    }
+    launch_rows<D, ClLane>(c, C.rb2, ClArgs{C.mem.p, C.parent.p, C.deg.p}, "cluster");
     k_cl_flatten<<<nb, MD_BLOCK, 0, st>>>(n, s.id, C.parent.p, C.root.p, C.count.p, C.minid.p);
     k_cl_stats<<<nb, MD_BLOCK, 0, st>>>(n, C.root.p, C.count.p, C.minid.p, C.max_size, C.hist.p, nb, C.part.p);
     k_cl_finish<<<1, 1024, 0, st>>>(nb, C.part.p, nh, C.deg.p, (long long)C.nsamples, (long long)C.nseries, C.sum_fr.p,
@@ -1635,25 +1594,7 @@ void cluster_zero(md_ctx *c)
 }
 
 // ---- cage-relative dynamics (md_cage.hpp): launches ----------------------------------------------------------------
-// The origin walk takes BOO pass 1's dispatch: dimension, record stride, tiles or 32-bit rows, the same LDS image and the
-// same check of it.  The walk's own test is the list cutoff (the rows are complete up to it); the bond criterion is the
-// lane's.
-template <int D, int RS>
-void launch_cage_origin_tile(md_ctx *c, const CageOrigin &T)
-{
-    static int attr_dev_mask = 0; // the attribute is per device: one bit per device id
-    auto k1 = k_cage_origin_tile<D, RS>;
-    if (!(attr_dev_mask & (1 << (c->device & 31)))) {
-        HIPCHK(hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MD_BOO_LDS_LIMIT));
-        attr_dev_mask |= 1 << (c->device & 31);
-    }
-    if (((size_t)c->hstride + 1) * RS > MD_BOO_ROW_OFFSET_MAX || !boo_image_fits(c->hstride))
-        throw HipError("internal: the cage sampler's LDS image does not fit");
-    k1<<<c->nblk, MD_TILE, boo_image_bytes(c->hstride), c->stream>>>((int)c->n, c->dev(c->cur), c->rc * c->rc, c->nlist16.p,
-                                                                     c->maxn, c->nmax_tile.p, c->halo.p, c->hcap,
-                                                                     c->halo_count.p, c->gowner.p, T);
-}
-
+// The origin walk's own test is the list cutoff (the rows are complete up to it); the bond criterion is the lane's.
 template <int D>
 void launch_cage_origin(md_ctx *c, int slot)
 {
@@ -1669,18 +1610,7 @@ void launch_cage_origin(md_ctx *c, int slot)
     T.del = G.del + (size_t)slot * mn * D * n;
     T.sig = G.sig.p + (size_t)slot * n;
     T.overflow = G.overflow.p;
-    if (c->use_tiles) {
-        if (c->tile_rs == 24)
-            launch_cage_origin_tile<D, 24>(c, T);
-        else if (c->tile_rs == 32)
-            launch_cage_origin_tile<D, 32>(c, T);
-        else
-            throw HipError("internal: cage sampler and tile rows disagree on the record stride");
-    } else {
-        if (!c->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
-        k_cage_origin<D><<<c->nblk, MD_BLOCK, 0, c->stream>>>((int)n, c->dev(c->cur), c->rc * c->rc, c->nlist.p, c->maxn,
-                                                              c->nmax_tile.p, c->gowner.p, T);
-    }
+    launch_rows<D, CageOriginLane<D>>(c, c->rc * c->rc, T, "cage");
 }
 
 template <int D>

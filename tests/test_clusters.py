@@ -43,7 +43,7 @@ def test_exports():
 
 
 def test_the_union_uses_agent_scope_atomics_only():
-    """The hook kernels have no plain access to parent[]: every one goes through the three helpers, and those are
+    """The hooks have no plain access to parent[]: every one goes through the three helpers, and those are
     agent-scope relaxed atomics."""
     src = open(os.path.join(ROOT, "moleculardynamics", "jl_amd", "csrc", "md_cluster.hpp")).read()
     src = re.sub(r"//[^\n]*", "", src)                      # the code, not what the comments say about it
@@ -51,7 +51,10 @@ def test_the_union_uses_agent_scope_atomics_only():
     assert "parent[" not in body                            # only parent + x, handed to an atomic builtin
     assert body.count("__HIP_MEMORY_SCOPE_AGENT") == 3 and body.count("__ATOMIC_RELAXED") == 4
     hooks = src[src.index("struct ClLane"):src.index("k_cl_flatten")]
-    assert "parent[" not in hooks and "k_cl_hook_tile" in hooks and "k_cl_hook(" in hooks
+    assert "parent[" not in hooks and "cl_union(A.parent" in hooks and "visit(" in hooks and "end(" in hooks
+    # the hooks run as a lane of the shared row walk, whose kernels know nothing of parent[]
+    walk = open(os.path.join(ROOT, "moleculardynamics", "jl_amd", "csrc", "md_rowwalk.hpp")).read()
+    assert "k_rows_tile" in walk and "k_rows(" in walk and "parent" not in re.sub(r"//[^\n]*", "", walk)
 
 
 def test_argument_checks():

@@ -14,7 +14,7 @@ are the bins of the downloaded per-particle values exactly; sum_fr and series ar
 
 The image of the sampler (32-byte records) always fits a tiled handle -- the rows address the force kernel's image with
 16-bit byte offsets, so a tile's halo has at most 65535 / 24 records and the sampler's image at most 87360 bytes -- so no
-shape, small or large, sends a tiled handle down another walk: md_boo.hpp asserts that arithmetic at compile time and the
+shape, small or large, sends a tiled handle down another walk: md_rowwalk.hpp asserts that arithmetic at compile time and the
 launch checks its premise on the handle; the global-gather kernels are run here through a handle created without tiles."""
 import ctypes
 
@@ -303,6 +303,42 @@ def test_general_cell(oracle):
         d = _sample(dev, 1.5, 6)
         x = dev.download()[0]
     _check(d, _reference(oracle, x, U, 1.5, 6, 0.7, 7, tric=True), 7, "sheared cell")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6b: every walk the samplers share (md_rowwalk.hpp), in both dimensions, at the smallest size with a ragged last block
+
+WALKS = [(dim, rows) for dim in (3, 2) for rows in ("tile24", "tile32", "rows32")]
+
+
+def _walk_case(dim, rows, monkeypatch):
+    """(x, box, diam) of N = 257 = one full 256-lane tile + one lane -- the second block has 255 inactive lanes: a simple
+    lattice of spacing 1.1 (7^3 or 17^2 sites, shells at 1.1 and 1.556) with vacancies and a jitter of 0.04, list cutoff 1.5.
+    rows: "tile24" -- tiled rows over the 24-byte image (built-in LJ, one diameter); "tile32" -- over the 32-byte image (the
+    diameters differ); "rows32" -- 32-bit global rows (a handle created without tiles)."""
+    rng = np.random.default_rng(257 + dim)
+    m = 7 if dim == 3 else 17
+    g = np.arange(m)
+    sites = np.stack(np.meshgrid(*([g] * dim), indexing="ij"), -1).reshape(-1, dim).astype(np.float64)
+    x = 1.1 * (rng.permutation(sites)[:257] + 0.5) + rng.normal(0.0, 0.04, (257, dim))
+    diam = rng.uniform(0.9, 1.1, 257) if rows == "tile32" else np.ones(257)
+    if rows == "rows32":
+        monkeypatch.setenv("MDHIP_NO_TILES", "1")
+    return x, np.full(dim, 1.1 * m), diam
+
+
+@pytest.mark.parametrize("dim,rows", WALKS)
+def test_every_walk_with_a_ragged_last_block(oracle, monkeypatch, dim, rows):
+    x, box, diam = _walk_case(dim, rows, monkeypatch)
+    with _handle(257, dim, box, 1.5, x, diam=diam) as dev:
+        xd = dev.download()[0]
+        d6 = _sample(dev, 1.35, 6, min_conn=3)
+        d4 = _sample(dev, 1.35, 4, min_conn=3)
+        assert dev.stats()["tiled"] == (0 if rows == "rows32" else 1)
+    for order, d in ((6, d6), (4, d4)):
+        r = _reference(oracle, xd, box, 1.35, order, 0.7, 3)
+        assert r["nnb"].min() > 0                            # every site has a neighbour, none has its full shell
+        _check(d, r, 3, "N = 257, %d-D, %s, order %d" % (dim, rows, order))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

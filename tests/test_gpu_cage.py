@@ -24,7 +24,7 @@ import pytest
 
 from tests import boo_reference as lattices
 from tests import cage_reference as ref
-from tests.test_gpu_bond_order import TRIC_U, _canon_delta, _d2, _tric_delta
+from tests.test_gpu_bond_order import TRIC_U, WALKS, _canon_delta, _d2, _tric_delta, _walk_case
 from tests.util import lj_system, poly_system
 
 pytestmark = pytest.mark.gpu
@@ -381,6 +381,34 @@ def test_2d_polydisperse(oracle, scaled, r_n, r_b):
     r = _reference(oracle, f0, f1, s["box"], r_n, r_b, s["diam"], scaled)
     _check(d, r, "poly2d scaled=%s" % scaled, 2)
     assert r["broken"].sum() > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5b: every walk of the origin store, in both dimensions, at the smallest size with a ragged last block
+
+@pytest.mark.parametrize("dim,rows", WALKS)
+def test_every_walk_with_a_ragged_last_block(oracle, monkeypatch, dim, rows):
+    """tests/test_gpu_bond_order.py's N = 257 lattice with vacancies; the second frame, by upload, moves every particle by
+    a normal step of 0.08 (some bonds break); the radii scale with sigma_ij where the diameters differ."""
+    from moleculardynamics.jl_amd import MDDevice
+    x0, box, diam = _walk_case(dim, rows, monkeypatch)
+    x1 = x0 + np.random.default_rng(99).normal(0.0, 0.08, x0.shape)
+    scaled = rows == "tile32"
+    z, zi = np.zeros_like(x0), np.zeros(x0.shape, dtype=np.int32)
+    with MDDevice(dim, 257, box, 1.5) as dev:
+        dev.set_potential(0, [1.0, 1.0, 1.5])
+        dev.upload(x0, z, z, zi, diam)
+        dev.cage_setup(1, 1, 1.3, 1.3, scaled, 32, Q2)
+        f0 = _frame(dev)
+        dev.cage_origin(0)
+        assert dev.stats()["tiled"] == (0 if rows == "rows32" else 1)
+        dev.upload(x1, None, None, zi)
+        f1 = _frame(dev)
+        dev.cage_sample([0], [0])
+        d = _result(dev, 0)
+    r = _reference(oracle, f0, f1, box, 1.3, 1.3, diam, scaled)
+    assert r["nnb"].sum() > 257 and r["broken"].sum() > 0
+    _check(d, r, "N = 257, %d-D, %s" % (dim, rows), dim)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

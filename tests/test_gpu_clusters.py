@@ -18,7 +18,7 @@ import pytest
 
 from tests import boo_reference as boo
 from tests import cluster_reference as ref
-from tests.test_gpu_bond_order import LJ, TRIC_U, _handle, _neighbour_bonds
+from tests.test_gpu_bond_order import LJ, TRIC_U, WALKS, _handle, _neighbour_bonds, _walk_case
 from tests.test_gpu_bond_order import _reference as _boo_reference
 from tests.util import lj_system, poly_system
 
@@ -207,6 +207,20 @@ def test_general_cell(oracle):
     r = _reference(oracle, x, U, 1.1, tric=True)
     assert np.count_nonzero(r["sizes"] >= 2) >= 50 and 10 <= r["fr"][2] <= 2000
     _check(d, r, "sheared cell")
+
+
+@pytest.mark.parametrize("dim,rows", WALKS)
+def test_every_walk_with_a_ragged_last_block(oracle, monkeypatch, dim, rows):
+    """tests/test_gpu_bond_order.py's N = 257 lattice with vacancies; r_bond = 1.08, just below the spacing, keeps about two
+    nearest-site bonds in five: tens of clusters, the largest of a few dozen sites."""
+    x, box, diam = _walk_case(dim, rows, monkeypatch)
+    with _handle(257, dim, box, 1.5, x, diam=diam) as dev:
+        xd = dev.download()[0]
+        d = _sample(dev, 1.08)
+        assert dev.stats()["tiled"] == (0 if rows == "rows32" else 1)
+    r = _reference(oracle, xd, box, 1.08)
+    assert np.count_nonzero(r["sizes"] >= 2) >= 20 and 10 <= r["fr"][2] <= 128     # many clusters, none of them everything
+    _check(d, r, "N = 257, %d-D, %s" % (dim, rows))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
