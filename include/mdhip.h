@@ -445,6 +445,8 @@ typedef struct {
                                the next step can start (state conversion, sort, gather, rows, host waits included) */
     int64_t fused_build;    /* 1: the rows of the last build came from the fused per-tile kernel (k_build_tile), 0: from the
                                two-kernel fallback (a tile or a cell did not fit it) */
+    int64_t own_first;      /* 1: the last step launch took the tile's own records from registers (own-first halo list of
+                               k_build_tile), 0: it gathered every record through the halo list */
 } md_stats;
 /* enable = 0: off; 1: HIP events around every force and kick-drift launch; k > 1: around every k-th launch of each
  * (an event record costs a few microseconds of device time: sampling keeps a timed run honest) */

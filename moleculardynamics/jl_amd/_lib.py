@@ -42,7 +42,7 @@ class MdStats(C.Structure):
                 ("kickdrift_launches", C.c_int64), ("kickdrift_ms", C.c_double), ("fused", C.c_int64),
                 ("walked_outer", C.c_int64), ("walked_inner", C.c_int64), ("prune_launches_timed", C.c_int64),
                 ("prune_ms", C.c_double), ("rebuilds_timed", C.c_int64), ("rebuild_ms", C.c_double),
-                ("fused_build", C.c_int64)]
+                ("fused_build", C.c_int64), ("own_first", C.c_int64)]
 
 
 class MdhipError(RuntimeError):

@@ -9,7 +9,9 @@
 //      first particle;
 //   3. sweep 0: two threads per particle (cells 0-13 / 14-26 of the fixed 27-cell order) test
 //      d^2 <= rl^2 (1 + margin) against the LDS image, mark what the tile keeps, count;
-//   4. the marked particles are compacted into the tile's halo;
+//   4. the marked particles are compacted into the tile's halo: the tile's own 256 particles take halo slots
+//      0..255 in lane order (the step kernel holds their records in registers and stages them from there, not
+//      through the list), every other referenced particle follows from slot 256 on, cell by cell;
 //   5. sweep 1 repeats the tests and writes the rows with the compact indices, padded to the
 //      wave maximum with the halo's sentinel slot.
 // The list is a superset structure: the force kernel re-tests every entry against the
@@ -19,7 +21,7 @@
 #pragma once
 
 #define MD_BT_THREADS 512
-#define MD_SCAP 3584  // staged particles per tile (LDS capacity)
+#define MD_SCAP 4096  // staged particles per tile (LDS capacity; with 80 KB per workgroup two workgroups still share a CU)
 #define MD_NCMAX 1024 // neighbour-cell candidates per tile (before dedupe)
 #define MD_NEMAX 36   // non-empty owned cells per tile (36 * 27 <= MD_NCMAX)
 #define MD_INF_CELL 0x7fffffff
@@ -121,7 +123,7 @@ __device__ __forceinline__ int tile_sweep_mark(float xi, float yi, float zi, con
 
 #define MD_BBMAX 1024    // cells of the tile's bounding box (owned cells dilated by one), local numbering
 #define MD_ROWPITCH 132  // LDS row buffer of the emit phase: 256 rows x 132 entries x 2 bytes, over the dead phase-1 arrays
-#define MD_BT_POOL 68864
+#define MD_BT_POOL 68880
 
 // Walks the set bits of the per-cell hit words and appends the hits to an LDS row as STAGED indices (the copy-out
 // translates them to halo offsets with independent, pipelined lookups -- a lookup inside this walk would put one
@@ -195,7 +197,7 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
     k_build_tile(int n, DevState s, BoxGrid g, float rl2f, const int32_t *__restrict__ cell_start,
                  const int32_t *__restrict__ cell_end, uint16_t *__restrict__ nlist16, int maxn,
                  int32_t *__restrict__ nneigh, int32_t *__restrict__ nmax_tile, uint32_t *__restrict__ halo, int hcap,
-                 int32_t *__restrict__ halo_count, Scalars *sc, long long *__restrict__ stamps, int rs)
+                 int32_t *__restrict__ halo_count, Scalars *sc, long long *__restrict__ stamps, int rs, int own_first)
 {
 #define MD_STAMP(i)                                                                                   \
     do {                                                                                              \
@@ -204,15 +206,20 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
     MD_STAMP(0);
     // phase-1 arrays carved out of one pool; phase 2 (emit) reuses the whole pool as the row buffer
     __shared__ __attribute__((aligned(16))) unsigned char pool[MD_BT_POOL];
-    float *px = (float *)pool, *py = px + MD_SCAP, *pz = py + MD_SCAP;                    // 43008 bytes
-    unsigned *refmask = (unsigned *)(pool + 43008);                                       // per unique cell, two words: which of its (<= 64) staged particles some row references
-    int *ucell = (int *)(pool + 51200);                                                   // MD_NCMAX
-    int *coff = (int *)(pool + 55296);                                                    // MD_NCMAX + 2
-    int *lcell = (int *)(pool + 59408);                                                   // bounding-box cell (local numbering) -> global cell id, -1: not needed / empty
-    uint16_t *ctab = (uint16_t *)(pool + 63504);                                          // (owned cell ci, offset nb) -> index in ucell[] (0xffff: empty)
-    uint16_t *lmap = (uint16_t *)(pool + 65552);                                          // bounding-box cell -> index in ucell[]
-    uint16_t *blk2u = (uint16_t *)(pool + 67600);                                         // staged slot 32 t -> its unique cell
-    unsigned char *ccnt = (unsigned char *)(pool + 67840);                                // real (unpadded) population of unique cell u (<= 64)
+    float *px = (float *)pool, *py = px + MD_SCAP, *pz = py + MD_SCAP;                    // 49152 bytes
+    // (lcell and lmap live in the tail of the coordinate planes: their last reader -- the ctab translation of phase 1c --
+    // is a barrier ahead of the staging that writes the planes)
+    int *lcell = (int *)(pool + 43008);                                                   // bounding-box cell (local numbering) -> global cell id, -1: not needed / empty
+    uint16_t *lmap = (uint16_t *)(pool + 47104);                                          // bounding-box cell -> index in ucell[]
+    unsigned *refmask = (unsigned *)(pool + 49152);                                       // per unique cell, two words: which of its (<= 64) staged particles some row references
+    int *ucell = (int *)(pool + 57344);                                                   // MD_NCMAX
+    int *coff = (int *)(pool + 61440);                                                    // MD_NCMAX + 2
+    uint16_t *ctab = (uint16_t *)(pool + 65552);                                          // (owned cell ci, offset nb) -> index in ucell[] (0xffff: empty)
+    uint16_t *blk2u = (uint16_t *)(pool + 67600);                                         // staged slot 32 t -> its unique cell (MD_SCAP / 32 entries)
+    unsigned char *ccnt = (unsigned char *)(pool + 67856);                                // real (unpadded) population of unique cell u (<= 64)
+    static_assert(3 * MD_SCAP * 4 == 49152 && MD_BBMAX * 6 == 49152 - 43008 && 67856 + MD_NCMAX == MD_BT_POOL &&
+                      MD_BT_POOL >= MD_TILE * MD_ROWPITCH * 2,
+                  "LDS layout of k_build_tile");
     __shared__ uint16_t newidx[MD_SCAP];
     __shared__ int cntA[MD_TILE], cntB[MD_TILE];
     __shared__ int sh_misc[16];
@@ -413,20 +420,47 @@ __global__ void __launch_bounds__(MD_BT_THREADS)
     // 4. compact the referenced particles into the halo
     int H;
     {
-        // by unique cell (halo order = staged order: cell by cell, particles of a cell in slot order)
-        const int per = (MD_NCMAX + MD_BT_THREADS - 1) / MD_BT_THREADS;
+        // own-first numbering: halo slot t < 256 is the tile's own particle t (shift code 0), referenced or not, and
+        // the own particles leave the reference masks before the others are counted.  The tile owns the consecutive
+        // slots [own0, own1), so the own particles of a cell are one run of bits of its mask (none in a ghost cell,
+        // whose slots lie behind n).  No row references the slot of an inactive lane of the last tile; it names the
+        // tile's first particle (a valid owned slot for every reader that stages the whole list).
+        const int hown = own_first ? MD_TILE : 0;
+        const int own0 = tile * MD_TILE, own1 = own_first ? min(n, own0 + MD_TILE) : own0;
+        // the others by unique cell (halo order = staged order: cell by cell, particles of a cell in slot order)
+        constexpr int per = (MD_NCMAX + MD_BT_THREADS - 1) / MD_BT_THREADS;
+        unsigned rm0[per], rm1[per];
+        int csrc[per];
         int c = 0;
+#pragma unroll
         for (int q = 0; q < per; ++q) {
             int u = tid * per + q;
-            if (u < nu) c += __popc(refmask[2 * u]) + __popc(refmask[2 * u + 1]);
+            rm0[q] = rm1[q] = 0u;
+            csrc[q] = 0;
+            if (u < nu) {
+                const int src0 = cell_start[ucell[u]];
+                const int lo = max(own0 - src0, 0), hi = min(own1 - src0, 64);
+                unsigned long long r = ((unsigned long long)refmask[2 * u + 1] << 32) | refmask[2 * u];
+                if (hi > lo) r &= ~((~0ull >> (64 - (hi - lo))) << lo);
+                rm0[q] = (unsigned)r;
+                rm1[q] = (unsigned)(r >> 32);
+                csrc[q] = src0;
+                c += __popcll(r);
+            }
         }
-        int run = block_excl_scan(c, sh_scan, &H);
+        int run = hown + block_excl_scan(c, sh_scan, &H);
+        H += hown;
         uint32_t *hrow = halo + (size_t)tile * hcap;
+        if (own_first && half == 0) {
+            if (active) newidx[self_q] = (uint16_t)pt;
+            if (pt < hcap) hrow[pt] = (uint32_t)(active ? k : own0);
+        }
+#pragma unroll
         for (int q = 0; q < per; ++q) {
             int u = tid * per + q;
             if (u >= nu) continue;
-            const int base = coff[u], src0 = cell_start[ucell[u]];
-            const unsigned r0 = refmask[2 * u], r1 = refmask[2 * u + 1];
+            const int base = coff[u], src0 = csrc[q];
+            const unsigned r0 = rm0[q], r1 = rm1[q];
             if (run + __popc(r0) + __popc(r1) <= hcap) {
                 // (the common case: the tile's halo fits, nothing to test per entry)
                 run = tile_compact_word<false>(r0, base, src0, newidx, hrow, hcap, run);

@@ -1512,7 +1512,7 @@ __global__ void __launch_bounds__(MD_TILE)
                 double *__restrict__ partials, int nblk_total, Scalars *__restrict__ sc, int step,
                 uint16_t *__restrict__ rows_in, int32_t *__restrict__ nmax_in, double rin2,
                 long long *__restrict__ stamps, uint32_t *__restrict__ halo_in, int hcap_in,
-                int32_t *__restrict__ halo_in_count, const int32_t *__restrict__ tile_list = nullptr)
+                int32_t *__restrict__ halo_in_count, int own_first, const int32_t *__restrict__ tile_list = nullptr)
 {
 #define MD_SSTAMP(i)                                                                                   \
     do {                                                                                               \
@@ -1568,45 +1568,54 @@ __global__ void __launch_bounds__(MD_TILE)
 #define MD_STAGE_NB ((!PRUNE && UNIFORM && !WANT_UW) ? 6 : 8)
 #endif
     constexpr int NB = MD_STAGE_NB;
-    for (int h0 = 0; h0 <= H; h0 += NB * MD_TILE) {
+    // Own-first lists (k_build_tile): entries [0, 256) are this tile's own particles, whose records the threads hold
+    // in registers already (a0, a1, a2) -- they go to LDS from there, below, and the gather starts at entry 256.
+    // A lane past the end of the list reads the last entry again and stores nothing: no per-record range tests or
+    // selects.  Slot numbers and record offsets fit 32 bits (slots < 2^26), so every load is a scalar base plus a
+    // 32-bit lane offset.
+    const unsigned char *hlb = (const unsigned char *)hl;
+    const unsigned char *PA0 = (const unsigned char *)RA0, *PA1 = (const unsigned char *)RA1,
+                        *PA2 = (const unsigned char *)RA2, *PA3 = (const unsigned char *)RA3;
+    for (int h0 = own_first ? MD_TILE : 0; h0 < H; h0 += NB * MD_TILE) {
         uint32_t idx[NB];
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             int h = h0 + i * MD_TILE + threadIdx.x;
-            idx[i] = (h < H) ? hl[h] : 0xffffffffu;
+            idx[i] = *(const uint32_t *)(hlb + (uint32_t)min(h, H - 1) * 4u);
         }
         double2 r0[NB], r1[NB], r2[NB], r3[NB];
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            bool ok = idx[i] != 0xffffffffu;
-            size_t j = ok ? (size_t)(idx[i] & 0x3ffffffu) : 0;
-            r0[i] = RA0[j];
-            r1[i] = RA1[j];
-            r2[i] = RA2[j];
-            if constexpr (!UNIFORM) r3[i] = RA3[j];
+            const uint32_t jo = (idx[i] & 0x3ffffffu) * 16u;
+            r0[i] = *(const double2 *)(PA0 + jo);
+            r1[i] = *(const double2 *)(PA1 + jo);
+            r2[i] = *(const double2 *)(PA2 + jo);
+            if constexpr (!UNIFORM) r3[i] = *(const double2 *)(PA3 + jo);
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             int h = h0 + i * MD_TILE + threadIdx.x;
-            bool ok = idx[i] != 0xffffffffu;
             double x = __builtin_fma(adt, r1[i].y, r0[i].x);
             double y = __builtin_fma(adt, r2[i].x, r0[i].y);
             double z = (D == 3) ? __builtin_fma(adt, r2[i].y, r1[i].x) : 0.0;
-            uint32_t code = ok ? (idx[i] >> 26) : 0u;
+            uint32_t code = idx[i] >> 26;
             if (code) shift_xyz(x, y, z, code, s.boxL, s.tric, s.cellA);
-            if (!ok) {
-                x = MD_SENTINEL_POS;
-                y = MD_SENTINEL_POS;
-                z = (D == 3) ? MD_SENTINEL_POS : 0.0;
-            }
-            if (h <= H) {
+            if (h < H) {
                 double *rec = (double *)(smem + (size_t)h * RS);
                 rec[0] = x;
                 rec[1] = y;
                 rec[2] = z;
-                if constexpr (!UNIFORM) rec[3] = ok ? r3[i].x : 1.0;
+                if constexpr (!UNIFORM) rec[3] = r3[i].x;
             }
         }
+    }
+    if (threadIdx.x == 0) {
+        // the sentinel slot behind the list: the padding of every row points here
+        double *rec = (double *)(smem + (size_t)H * RS);
+        rec[0] = MD_SENTINEL_POS;
+        rec[1] = MD_SENTINEL_POS;
+        rec[2] = (D == 3) ? MD_SENTINEL_POS : 0.0;
+        if constexpr (!UNIFORM) rec[3] = 1.0;
     }
     // the tile's own particles (their loads went out ahead of the staging): first half-kick, drift, validity check
     const double pown[3] = {a0.x, a0.y, a1.x}, vown[3] = {a1.y, a2.x, a2.y};
@@ -1621,6 +1630,14 @@ __global__ void __launch_bounds__(MD_TILE)
     }
     const double4 pi = make_double4(xn[0], xn[1], xn[2], sig_own);
     if (active) sb.posB[k] = pi;
+    if (own_first) {
+        // own-first list: LDS slot t is the tile's particle t, and xn is the fma the gather would have computed for it
+        double *rec = (double *)(smem + (size_t)threadIdx.x * RS);
+        rec[0] = active ? xn[0] : MD_SENTINEL_POS;
+        rec[1] = active ? xn[1] : MD_SENTINEL_POS;
+        rec[2] = (active || D != 3) ? xn[2] : MD_SENTINEL_POS;
+        if constexpr (!UNIFORM) rec[3] = active ? sig_own : 1.0;
+    }
     {
         // validity of the rows this step walks (see k_kickdrift): within min(inner/2, skin/2 - d1) of the prune
         // positions x1; a prune step walks the outer rows: within skin/2 of the build positions x0

@@ -191,6 +191,9 @@ struct md_ctx {
     int tile_rs = 24;
     bool allow_tiles = true;
     bool allow_fused_build = true;
+    bool allow_own_first = true;  // MDHIP_NO_OWN_FIRST=1: k_build_tile numbers the halo cell by cell throughout
+    bool own_first = false;       // halo slots [0, 256) of every tile are its own particles (rows of the last build came from k_build_tile)
+    bool own_first_staged = false; // the last step launch staged the own records from registers
     bool have_nlist32 = false; // the 32-bit global-index rows exist for the current build
     DBuf<uint64_t> keys_in, keys_out;
     DBuf<char> sort_tmp, scan_tmp;
@@ -767,6 +770,7 @@ void rebuild_t(md_ctx *c)
     double rl2 = c->rl * c->rl;
     c->use_tiles = false;
     c->have_nlist32 = false;
+    c->own_first = false;
     bool tile_ok = false;
     const int rs = (c->uniform_sigma && c->pot_kind != POT_POLYDISPERSE && c->pot_kind != POT_LJ_MOD && c->pot_kind != POT_CUSTOM) ? 24 : 32; // LDS record stride of the tiled force kernel
     auto set_tiles = [&](const Scalars &h) {
@@ -795,7 +799,7 @@ void rebuild_t(md_ctx *c)
             k_build_tile<D><<<c->nblk, MD_BT_THREADS, 0, st>>>(n, sn, g, rl2f, c->cell_start.p, c->cell_end.p,
                                                                c->nlist16.p, c->maxn, c->nneigh.p, c->nmax_tile.p,
                                                                c->halo.p, c->hcap, c->halo_count.p, c->scal.p,
-                                                               c->dbg_stamps.p, rs);
+                                                               c->dbg_stamps.p, rs, c->allow_own_first ? 1 : 0);
             if (c->dbg_stamps.p) {
                 std::vector<long long> hs((size_t)c->nblk * 10);
                 HIPCHK(hipMemcpyAsync(hs.data(), c->dbg_stamps.p, hs.size() * 8, hipMemcpyDeviceToHost, st));
@@ -819,6 +823,7 @@ void rebuild_t(md_ctx *c)
                 continue;
             }
             tile_ok = set_tiles(h);
+            c->own_first = tile_ok && c->allow_own_first;
             break;
         }
     }
@@ -1292,6 +1297,7 @@ void launch_step_tpu(md_ctx *c, bool want_uw, double dt, int step)
     const int32_t *halo_cnt = c->halo_count.p;
     size_t lds_bytes = c->tile_lds;
     uint32_t *hin_p = nullptr;
+    int own_first = c->own_first ? 1 : 0; // (the outer halo list; an inner halo image keeps its own numbering)
     if (prune_step) {
         c->inner_halo_live = false;
     } else if (use_inner && c->inner_halo_live) {
@@ -1299,7 +1305,9 @@ void launch_step_tpu(md_ctx *c, bool want_uw, double dt, int step)
         halo_cap = c->hcap_in;
         halo_cnt = c->halo_in_count.p;
         lds_bytes = c->tile_lds_in;
+        own_first = 0;
     }
+    c->own_first_staged = own_first != 0;
     const int a = c->fz_a;
     StateBufs &A = c->sb[c->cur ^ a], &B = c->sb[c->cur ^ a ^ 1];
     StepBufs sbufs{};
@@ -1325,7 +1333,7 @@ void launch_step_tpu(md_ctx *c, bool want_uw, double dt, int step)
                                                    halo_cnt, dt, skin_half, inner_half, use_d1,                     \
                                                    c->partials.p, nb, c->scal.p, step, c->nlist16_in.p,             \
                                                    c->nmax_tile_in.p, rin * rin, c->dbg_stamps.p, hin_p,            \
-                                                   c->hcap_in, c->halo_in_count.p, c->part.list);                   \
+                                                   c->hcap_in, c->halo_in_count.p, own_first, c->part.list);        \
     } while (0)
     if (whole) prof_begin(c, prune_step ? 3 : 0);
     if (prune_step) {
@@ -1743,6 +1751,7 @@ static int create_common(int dim, int64_t n_global, int64_t n_cap, bool domain, 
         }
         if (const char *e = getenv("MDHIP_NO_TILES")) ctx->allow_tiles = !(e[0] == '1');
         if (const char *e = getenv("MDHIP_NO_FUSED_BUILD")) ctx->allow_fused_build = !(e[0] == '1');
+        if (const char *e = getenv("MDHIP_NO_OWN_FIRST")) ctx->allow_own_first = !(e[0] == '1');
         if (const char *e = getenv("MDHIP_INNER_SKIN")) ctx->inner_skin_req = atof(e);
         if (const char *e = getenv("MDHIP_NO_FUSED_STEP")) ctx->allow_fused = !(e[0] == '1');
         // inner halo (md_kernels.hpp, tile_inner_halo): off unless asked for -- the box test trims only ~4 % of a
@@ -3814,6 +3823,7 @@ int md_get_stats(md_ctx *ctx, md_stats *out)
     out->rebuilds_timed = ctx->prof_rebuild_acc;
     out->rebuild_ms = ctx->prof_rebuild_ms_acc;
     out->fused_build = (ctx->list_valid && ctx->use_tiles && !ctx->have_nlist32) ? 1 : 0;
+    out->own_first = ctx->own_first_staged ? 1 : 0;
     API_END
 }
 
