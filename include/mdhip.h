@@ -411,6 +411,52 @@ int md_cage_particles(md_ctx *ctx, int32_t *nnb, double *d2cr, int32_t *broken);
 int md_cage_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *counts, int64_t *hist_broken, int64_t *overflow);
 int md_cage_reset(md_ctx *ctx);
 
+/* Four-point dynamics, sampled on the device (new relative to the reference): the self overlap Q(t0, t) = sum_i w_i with
+ * w_i = 1 iff particle i moved less than `a` between the origin t0 and t0 + t, the moments of Q behind the four-point
+ * susceptibility chi4(t) = (<Q^2> - <Q>^2) / N, and the structure factor of the slow particles
+ * S4(q, t) = <|W(q)|^2> / N, W(q) = sum_i w_i exp(+i q.x_i(t0)) (Lacevic, Starr, Schroder, Glotzer 2003), on md_sq_setup's
+ * wave vectors q_n = 2 pi U^-T n.  The potential is never evaluated.
+ *
+ * md_chi4_origin(slot) stores md_dyn_origin's frame (wrapped x and int32 images in particle-id order, written by the step
+ * loop's own export) and, if nvec > 0, md_sq_sample's f = U^-1 x of that frame, one array per axis: a slot is N*d*20
+ * bytes with vectors and N*d*12 without.  It does not wait and writes nothing of the handle.
+ *
+ * md_chi4_sample(slots, rows, count) exports the current frame once and, per (slot, row) in call order:
+ *   Del_i, d2   the displacement since the slot's origin and its square, exactly md_dyn_sample's (no fma)
+ *   w_i         = 1 iff d2 < a2, a2 = a*a formed once at setup in fp64; strict: d2 == a2 is not slow
+ *   Q           = sum_i w_i, an integer
+ *   W[v]        = sum over i with w_i = 1 of (cos 2 pi r, sin 2 pi r), the phase md_sq_sample's evaluated on the ORIGIN
+ *                 frame's f: t = (n_0 f_0 + n_1 f_1) + n_2 f_2, r = t - rint(t), the same polynomials; summed in
+ *                 md_sq_sample's tree, fixed by N alone (thread: 16 ids in order; shuffle tree; the 4 waves in order; lane l
+ *                 of the reducer takes blocks l, l + 64, ... in order), a fast particle contributing nothing (+0.0); no
+ *                 floating-point atomics, so the same two frames give the same bits on any handle.
+ *                 |W_device - W_true| <= N*(32*kappa*|n|_1 + 128)*2^-53 per component (md_sq_sample's bound and
+ *                 derivation), W_true the extended-precision sum over the same slow set from the same fp64 origin frame
+ * and adds into the row, since setup or the last reset:
+ *   sum_q[row] += Q;  sum_q2[row] += Q*Q;  nsamples[row] += 1        (integers: functions of the two frames alone)
+ *   s4[row*nvec + v] = s4[row*nvec + v] + (Re*Re + Im*Im)            (no fma, in call order)
+ * Two samples of one call on the same row are both added.  It does not wait and writes nothing of the handle: a run with
+ * origins and samples is bit-identical to one without.
+ *
+ * md_chi4_last waits and returns, of the last (slot, row) of the last md_chi4_sample call, Q, W as w[2v] = Re,
+ * w[2v+1] = Im, and slow[N], w_i as one byte per particle id (any may be NULL).  md_chi4_read waits and returns
+ * nsamples[nrows], sum_q[nrows], sum_q2[nrows] and s4[nrows*nvec] (any may be NULL).  md_chi4_reset zeroes the rows; it
+ * keeps the setup and the stored origins.
+ *
+ * md_chi4_setup: finite a > 0; 0 <= nvec <= 4096 vectors n[nvec*d] under md_sq_setup's rules (|n_c| <= 32767, n != 0);
+ * nvec = 0 samples Q only (no f is stored, no mode kernel runs); 1 <= nslots <= 64; nrows >= 1; allocates the slots and
+ * zeroes everything; calling it again starts over.  MDHIP_CHI4_ALLOC_LIMIT=bytes in the environment refuses a larger slot
+ * allocation as a failed allocation is refused (the message names the byte count).  Refused: a slab-decomposition handle,
+ * an argument out of range, a failed allocation, any call before md_chi4_setup, a slot or row out of range, an empty slot,
+ * md_chi4_last before the first sample, and a sample that could let sum_q2 overflow: the library counts the samples of a
+ * row and refuses the whole call when (nsamples[row] + 1)*N*N > 2^63 - 1 (read and reset first).                       */
+int md_chi4_setup(md_ctx *ctx, double a, const int32_t *n, int nvec, int nslots, int nrows);
+int md_chi4_origin(md_ctx *ctx, int slot);
+int md_chi4_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int count);
+int md_chi4_last(md_ctx *ctx, int64_t *q, double *w, void *slow /* uint8_t[N] */);
+int md_chi4_read(md_ctx *ctx, int64_t *nsamples, int64_t *sum_q, int64_t *sum_q2, double *s4);
+int md_chi4_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

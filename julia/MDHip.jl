@@ -18,6 +18,7 @@ export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, Pseudo
        LennardJonesShifted, LennardJonesForceShifted, LennardJonesXPLOR, device_spec, RadialDistribution, compute_rdf,
        gofr, write_rdf, SelfDynamics, msd, alpha2, fs, van_hove, write_dynamics, write_van_hove,
        CageDynamics, bond_correlation, broken_distribution, write_cage, cage_particles,
+       FourPoint, overlap, chi4, s4, s4_vectors, write_chi4, write_s4, chi4_last,
        StructureFactor, select_wave_vectors, compute_sq, sofq, fqt, fqt_normalised, write_sq, write_fqt
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
@@ -777,6 +778,146 @@ function compute_sq(state::SimulationState, params::Parameters, q_max; dq=nothin
     return sq_collect!(dev, sq, params.dt)
 end
 
+# ---- four-point dynamics, sampled on the device (md_chi4_*; normalisation and file formats as analysis.py's FourPoint) --
+"""
+FourPoint(a; q_max=nothing, dq=nothing, max_per_bin=16, seed=0, lags=nothing, origin_every=nothing): the self overlap
+Q(t0, t) = sum_i w_i, w_i = 1 iff particle i moved less than a (strict), its variance chi4(t) = (<Q^2> - <Q>^2) / N and
+S4(q, t) = <|W(q)|^2> / N, W(q) = sum_i w_i exp(+i q.x_i(t0)), on select_wave_vectors' vectors of the cell first used on
+(at most 4096; q_max=nothing: chi4 only), accumulated across run_simulation! calls until reset!.  The schedule is
+SelfDynamics' own (log-time by default; samples before the new origin at a shared step).  chi4 as measured is the
+fixed-N variance in the ensemble of the run: NVE, NVT and Brownian runs each miss the contributions of the quantities they
+hold fixed; S4(q -> 0, t) of the same run is the estimate without that loss.  The overlap is the self overlap; a
+cage-relative variant for 2-D is not provided.
+"""
+mutable struct FourPoint
+    a::Float64
+    q_max::Union{Nothing,Float64}
+    dq::Union{Nothing,Float64}
+    max_per_bin::Int
+    seed::Int
+    sched::SelfDynamics                  # lags, origin_every, nslots: the schedule is SelfDynamics' own
+    nsamples::Vector{Int64}
+    sum_q::Vector{BigInt}                # per lag: sum Q and sum Q^2, exact
+    sum_q2::Vector{BigInt}
+    unitcell::Union{Nothing,Matrix{Float64}}
+    n::Matrix{Int32}                     # d x nvec
+    qvec::Vector{Float64}
+    bin::Vector{Int}                     # per vector: index into q
+    q::Vector{Float64}                   # mean |q| of a bin
+    nvectors::Vector{Int}
+    sum_s4::Matrix{Float64}              # nvec x nlags: sum |W|^2
+    n_particles::Int
+    dt::Float64
+end
+function FourPoint(a; q_max=nothing, dq=nothing, max_per_bin::Int=16, seed::Int=0, lags=nothing, origin_every=nothing)
+    (a > 0 && isfinite(a)) || error("a must be finite and > 0")
+    (q_max === nothing || (q_max > 0 && isfinite(q_max))) || error("q_max must be finite and > 0 (or nothing for chi4 only)")
+    (dq === nothing || q_max !== nothing) || error("dq needs q_max")
+    (dq === nothing || (dq > 0 && isfinite(dq))) || error("dq must be finite and > 0")
+    max_per_bin >= 1 || error("max_per_bin must be >= 1")
+    sched = SelfDynamics(; q=Float64[], lags=lags, origin_every=origin_every)
+    nl = length(sched.lags)
+    return FourPoint(Float64(a), q_max === nothing ? nothing : Float64(q_max), dq === nothing ? nothing : Float64(dq),
+                     max_per_bin, seed, sched, zeros(Int64, nl), zeros(BigInt, nl), zeros(BigInt, nl), nothing,
+                     zeros(Int32, 0, 0), Float64[], Int[], Float64[], Int[], zeros(0, nl), 0, 1.0)
+end
+function reset!(fp::FourPoint)
+    fp.nsamples .= 0; fp.sum_q .= 0; fp.sum_q2 .= 0
+    fp.unitcell = nothing; fp.n = zeros(Int32, 0, 0); fp.qvec = Float64[]; fp.sum_s4 = zeros(0, length(fp.sched.lags))
+    return fp
+end
+chi4_schedule(fp::FourPoint, T::Int) = dyn_schedule(fp.sched, T)
+
+function chi4_setup!(dev::Device, fp::FourPoint, unitcell)
+    if fp.q_max !== nothing
+        U = Matrix{Float64}(unitcell)
+        if fp.unitcell === nothing
+            n, q, b = select_wave_vectors(U, fp.q_max; dq=fp.dq, max_per_bin=fp.max_per_bin, seed=fp.seed)
+            size(n, 2) <= 4096 || error("$(size(n, 2)) wave vectors selected; FourPoint takes at most 4096")
+            ub = sort(unique(b))
+            fp.unitcell = U; fp.n = n; fp.qvec = q; fp.bin = [searchsortedfirst(ub, x) for x in b]
+            fp.nvectors = [count(==(k), fp.bin) for k in eachindex(ub)]
+            fp.q = [sum(q[fp.bin .== k]) / fp.nvectors[k] for k in eachindex(ub)]
+            fp.sum_s4 = zeros(length(q), length(fp.sched.lags))
+        else
+            fp.unitcell == U || error("the unit cell differs from the one the wave vectors were selected for; reset! first")
+        end
+    end
+    nvec = length(fp.qvec)
+    check(dev, ccall((:md_chi4_setup, LIB), Cint, (Ptr{Cvoid}, Float64, Ptr{Int32}, Cint, Cint, Cint),
+                     dev.h, fp.a, fp.n, nvec, fp.sched.nslots, length(fp.sched.lags)))
+end
+chi4_origin!(dev::Device, slot::Integer) = check(dev, ccall((:md_chi4_origin, LIB), Cint, (Ptr{Cvoid}, Cint), dev.h, slot))
+function chi4_sample!(dev::Device, slots::Vector{Int32}, rows::Vector{Int32})
+    check(dev, ccall((:md_chi4_sample, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Cint), dev.h, slots, rows,
+                     length(slots)))
+end
+chi4_reset!(dev::Device) = check(dev, ccall((:md_chi4_reset, LIB), Cint, (Ptr{Cvoid},), dev.h))
+"Q, W (complex, per vector) and the slow mask (one byte per particle id) of the last (slot, row) of the last chi4_sample! call"
+function chi4_last(dev::Device, nvec::Int)
+    q = Ref{Int64}(0); w = zeros(2, max(nvec, 1)); slow = zeros(UInt8, dev.n)
+    check(dev, ccall((:md_chi4_last, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Cvoid}), dev.h, q, w, slow))
+    return q[], [complex(w[1, v], w[2, v]) for v in 1:nvec], slow
+end
+function chi4_act!(dev::Device, ev)
+    smp, org = ev
+    isempty(smp) || chi4_sample!(dev, Int32[a for (a, _) in smp], Int32[b for (_, b) in smp])
+    org >= 0 && chi4_origin!(dev, org)
+end
+function chi4_collect!(dev::Device, fp::FourPoint, dt)
+    nl = length(fp.sched.lags); nvec = length(fp.qvec)
+    ns = zeros(Int64, nl); sq = zeros(Int64, nl); sq2 = zeros(Int64, nl); s4 = zeros(max(nvec, 1), nl)
+    check(dev, ccall((:md_chi4_read, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                     dev.h, ns, sq, sq2, s4))
+    fp.nsamples .+= ns; fp.sum_q .+= sq; fp.sum_q2 .+= sq2
+    nvec > 0 && (fp.sum_s4 .+= s4)
+    fp.n_particles = dev.n; fp.dt = dt
+    return fp
+end
+
+"<Q> / N per lag; NaN where a lag has no sample"
+overlap(fp::FourPoint) = [fp.nsamples[k] > 0 ? Float64(fp.sum_q[k] // (BigInt(fp.nsamples[k]) * fp.n_particles)) : NaN
+                          for k in eachindex(fp.nsamples)]
+"chi4 per lag: (ns sum Q^2 - (sum Q)^2) / (ns^2 N), the numerator formed in integers"
+chi4(fp::FourPoint) = [fp.nsamples[k] > 0 ?
+                       Float64((fp.nsamples[k] * fp.sum_q2[k] - fp.sum_q[k]^2) // (BigInt(fp.nsamples[k])^2 * fp.n_particles)) :
+                       NaN for k in eachindex(fp.nsamples)]
+"S4(q_v, t): nlags x nvec, sum |W|^2 / (ns N); NaN where a lag has no sample"
+s4_vectors(fp::FourPoint) = [fp.nsamples[k] > 0 ? fp.sum_s4[v, k] / (fp.nsamples[k] * fp.n_particles) : NaN
+                             for k in eachindex(fp.nsamples), v in eachindex(fp.qvec)]
+"S4(q, t): nlags x nbins, the mean of s4_vectors over the vectors of a |q| bin"
+function s4(fp::FourPoint)
+    sv = s4_vectors(fp)
+    return [sum(sv[k, fp.bin .== b]) / fp.nvectors[b] for k in eachindex(fp.nsamples), b in eachindex(fp.q)]
+end
+
+function write_chi4(path, fp::FourPoint; dt=fp.dt)
+    ov = overlap(fp); c4 = chi4(fp)
+    open(path, "w") do io
+        println(io, "# lag time Q/N chi4 nsamples")
+        for (k, l) in enumerate(fp.sched.lags)
+            fp.nsamples[k] > 0 || continue
+            @printf(io, "%d %.6e %.6e %.6e %d\n", l, l * dt, ov[k], c4[k], fp.nsamples[k])
+        end
+    end
+end
+
+function write_s4(path, fp::FourPoint; dt=fp.dt)
+    s = s4(fp)
+    open(path, "w") do io
+        println(io, "# lag time q S4 nvectors nsamples")
+        first = true
+        for (k, l) in enumerate(fp.sched.lags)
+            fp.nsamples[k] > 0 || continue
+            first || println(io)
+            first = false
+            for b in eachindex(fp.q)
+                @printf(io, "%d %.6e %.6f %.6e %d %d\n", l, l * dt, fp.q[b], s[k, b], fp.nvectors[b], fp.nsamples[k])
+            end
+        end
+    end
+end
+
 # ---- output: src/io.jl ---------------------------------------------------------------------------------------------
 function generate_log_times(; max_iter::Int=10000, logn::Int=40, logbase::Float64=1.35, save::Bool=true)   # src/io.jl:17-36
     dtime = Int[]
@@ -868,7 +1009,8 @@ order, and writes the thermo line, the LAMMPS frames, the log-spaced snapshots a
 RadialDistribution, g(r) is sampled on the device at every rdf.every-th output step and written to pathname/rdf.txt.
 With sq a StructureFactor, S(q) is sampled the same way (pathname/sq.txt) and, if it is dynamic, the coherent F(q,t) on its
 schedule (pathname/fqt.txt).  With cage a CageDynamics, the cage-relative MSD, alpha2, F_s(q,t) and the bond-breaking
-correlation are sampled on SelfDynamics' schedule (pathname/cage.txt).
+correlation are sampled on SelfDynamics' schedule (pathname/cage.txt).  With four_point a FourPoint, the self overlap,
+chi4(t) and -- if it has wave vectors -- S4(q,t) are sampled on SelfDynamics' schedule (pathname/chi4.txt, pathname/s4.txt).
 """
 function run_simulation!(state::SimulationState, params::Parameters, ensemble::Ensemble, total_steps::Int,
                          frequency::Int, pathname::String; traj_name::String="trajectory.xyz",
@@ -876,7 +1018,8 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
                          rdf::Union{Nothing,RadialDistribution}=nothing,
                          dynamics::Union{Nothing,SelfDynamics}=nothing,
                          sq::Union{Nothing,StructureFactor}=nothing,
-                         cage::Union{Nothing,CageDynamics}=nothing)
+                         cage::Union{Nothing,CageDynamics}=nothing,
+                         four_point::Union{Nothing,FourPoint}=nothing)
     dev = state.system.device; d = state.dimension; n = params.n_particles
     brownian = ensemble isa Brownian
     configure!(dev, params.potential)
@@ -894,6 +1037,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
     cage_stops, cage_events = cage === nothing ? (Int[], nothing) : cage_schedule(cage, total_steps)
     cage === nothing || cage_setup!(dev, cage)
     cage_i = 1
+    # four-point dynamics: SelfDynamics' stops; its device calls come last at a shared step, after cage's
+    fp_stops, fp_events = four_point === nothing ? (Int[], nothing) : chi4_schedule(four_point, total_steps)
+    four_point === nothing || chi4_setup!(dev, four_point, state.unitcell)
+    fp_i = 1
     trajectory_file, thermo_file = open_files(pathname, traj_name, thermo_name)
     open(io -> println(io, "# Step Energy Temperature Pressure"), thermo_file, "a")
     volume = abs(det(state.unitcell))                                                # src/simulation.jl:7-9
@@ -929,6 +1076,8 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         sq_i <= length(sq_stops) && (next_out = min(next_out, sq_stops[sq_i]))
         while cage_i <= length(cage_stops) && cage_stops[cage_i] < step; cage_i += 1; end
         cage_i <= length(cage_stops) && (next_out = min(next_out, cage_stops[cage_i]))
+        while fp_i <= length(fp_stops) && fp_stops[fp_i] < step; fp_i += 1; end
+        fp_i <= length(fp_stops) && (next_out = min(next_out, fp_stops[fp_i]))
         last = min(next_out, total_steps - 1)
         ns = last - step + 1
         if brownian
@@ -988,6 +1137,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
             cage_act!(dev, cage_events[last])        # the samples, then the new origin and its neighbour table
             cage_i += 1
         end
+        if fp_i <= length(fp_stops) && fp_stops[fp_i] == last
+            chi4_act!(dev, fp_events[last])          # the samples, then the new origin
+            fp_i += 1
+        end
         if log_times && snap_i <= length(snapshot_times) && snapshot_times[snap_i] == last   # :153-171
             push!(pending, (joinpath(pathname, "snapshot.$(last)"), last, "w"))
             snap_i += 1
@@ -1018,6 +1171,11 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
     if cage !== nothing
         cage_collect!(dev, cage, d, params.dt)
         write_cage(joinpath(pathname, "cage.txt"), cage)
+    end
+    if four_point !== nothing
+        chi4_collect!(dev, four_point, params.dt)
+        write_chi4(joinpath(pathname, "chi4.txt"), four_point)
+        isempty(four_point.qvec) || write_s4(joinpath(pathname, "s4.txt"), four_point)
     end
     compress && isfile(trajectory_file) && compress_zstd(trajectory_file)
     return nothing

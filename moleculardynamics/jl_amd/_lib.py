@@ -32,6 +32,7 @@ EXPORTS = [
     "md_boo_setup", "md_boo_sample", "md_boo_particles", "md_boo_qlm", "md_boo_read", "md_boo_reset",
     "md_cluster_setup", "md_cluster_sample", "md_cluster_particles", "md_cluster_read", "md_cluster_reset",
     "md_cage_setup", "md_cage_origin", "md_cage_sample", "md_cage_particles", "md_cage_read", "md_cage_reset",
+    "md_chi4_setup", "md_chi4_origin", "md_chi4_sample", "md_chi4_last", "md_chi4_read", "md_chi4_reset",
 ]
 
 
@@ -212,6 +213,18 @@ def load():
     L.md_cage_read.restype = C.c_int
     L.md_cage_reset.argtypes = [vp]
     L.md_cage_reset.restype = C.c_int
+    L.md_chi4_setup.argtypes = [vp, C.c_double, ip, C.c_int, C.c_int, C.c_int]
+    L.md_chi4_setup.restype = C.c_int
+    L.md_chi4_origin.argtypes = [vp, C.c_int]
+    L.md_chi4_origin.restype = C.c_int
+    L.md_chi4_sample.argtypes = [vp, ip, ip, C.c_int]
+    L.md_chi4_sample.restype = C.c_int
+    L.md_chi4_last.argtypes = [vp, i64p, dp, vp]
+    L.md_chi4_last.restype = C.c_int
+    L.md_chi4_read.argtypes = [vp, i64p, i64p, i64p, dp]
+    L.md_chi4_read.restype = C.c_int
+    L.md_chi4_reset.argtypes = [vp]
+    L.md_chi4_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

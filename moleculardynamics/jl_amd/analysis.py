@@ -2,8 +2,9 @@
 the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes, S(q), coherent F(q, t)), the stress
 (pressure tensor, stress autocorrelations, Green-Kubo viscosity), the bond-orientational order (Steinhardt q_l, the
 neighbour-averaged qbar_l, psi_k in 2-D, the solid-particle count) and the clusters (connected components of the bond
-graph: sizes, the size distribution, the largest -- solid -- cluster) and the cage-relative dynamics (displacements
-relative to the origin neighbours' mean, the bond-breaking correlation C_B).
+graph: sizes, the size distribution, the largest -- solid -- cluster), the cage-relative dynamics (displacements
+relative to the origin neighbours' mean, the bond-breaking correlation C_B) and the four-point functions of the self
+overlap (chi4(t), S4(q, t)).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -1289,3 +1290,178 @@ class CageDynamics:
                              "r_neigh; nothing was accumulated")
         self._accumulate(ns, sums, counts, hist, run.dim, run.dt)
         self.write(os.path.join(pathname, "cage.txt"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Four-point dynamics, sampled on the device (md_chi4_*): the self overlap Q(t0, t) = sum_i w_i of the particles that
+# moved less than a, its variance chi4(t) and the structure factor S4(q, t) of the slow particles.
+
+class FourPoint:
+    """Dynamic heterogeneity from the four-point functions of the self overlap, accumulated on the device over the samples
+    of a schedule until reset().
+
+    a: particle i is slow at lag t, w_i = 1, iff |x_i(t0 + t) - x_i(t0)| < a (unwrapped displacement, strict).
+    Q = sum_i w_i; overlap() = <Q> / N; chi4() = (<Q^2> - <Q>^2) / N; S4(q, t) = <|W(q)|^2> / N with
+    W(q) = sum_i w_i exp(+i q.x_i(t0)) on the wave vectors select_wave_vectors(unitcell, q_max, dq, max_per_bin, seed) of
+    the cell the sampler is first used on (at most 4096); q_max=None samples chi4 only.  The schedule (lags, origin_every)
+    is SelfDynamics': log-time by default, explicit lags need origin_every (at most 64 origin slots), samples before the
+    new origin at a shared step.  An origin costs N d 20 bytes on the device with vectors, N d 12 without.
+
+    What chi4 means here: it is the variance of Q at fixed N in the ensemble the run samples, so NVE, NVT and Brownian
+    runs each miss the contributions of the quantities they hold fixed (density, and energy or temperature); S4(q -> 0, t)
+    of the same run is the estimate without that loss.  The overlap is the SELF overlap (a particle against its own
+    origin position, not against any particle's).  A cage-relative variant for 2-D is not provided.
+
+    Fields: lags, nsamples (per lag), sum_q, sum_q2 (per lag, Python integers), n (nvec, d), qvec, bin, q (mean |q| of a
+    bin), nvectors (per bin), sum_s4 (nlags, nvec: sum |W|^2)."""
+
+    def __init__(self, a, q_max=None, dq=None, max_per_bin=16, seed=0, lags=None, origin_every=None):
+        a = float(a)
+        if not (a > 0.0 and math.isfinite(a)):
+            raise ValueError("a must be finite and > 0")
+        if q_max is not None:
+            q_max = float(q_max)
+            if not (q_max > 0.0 and math.isfinite(q_max)):
+                raise ValueError("q_max must be finite and > 0 (or None for chi4 only)")
+        elif dq is not None:
+            raise ValueError("dq needs q_max")
+        if dq is not None and not (float(dq) > 0.0 and math.isfinite(float(dq))):
+            raise ValueError("dq must be finite and > 0")
+        if int(max_per_bin) < 1:
+            raise ValueError("max_per_bin must be >= 1")
+        self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+        self.a, self.q_max, self.dq, self.max_per_bin, self.seed = a, q_max, dq, int(max_per_bin), seed
+        self.lags = np.array(lag_list, dtype=np.int64)
+        nl = len(lag_list)
+        self.nsamples = np.zeros(nl, dtype=np.int64)
+        self.sum_q = np.array([0] * nl, dtype=object)
+        self.sum_q2 = np.array([0] * nl, dtype=object)
+        self.unitcell = None
+        self.n = self.qvec = self.bin = self.q = self.nvectors = self.sum_s4 = None
+        self.n_particles = 0
+        self.dt = 1.0
+
+    def _select(self, unitcell):
+        if self.q_max is None:
+            return
+        u = np.array(unitcell, dtype=np.float64)
+        if self.unitcell is not None:
+            if u.shape != self.unitcell.shape or not np.array_equal(u, self.unitcell):
+                raise ValueError("the unit cell differs from the one the wave vectors were selected for; reset() first")
+            return
+        n, q, b = select_wave_vectors(u, self.q_max, self.dq, self.max_per_bin, self.seed)
+        if n.shape[0] > 4096:
+            raise ValueError(f"{n.shape[0]} wave vectors selected; FourPoint takes at most 4096 (lower q_max or "
+                             "max_per_bin, or widen dq)")
+        self._set_vectors(u, n, q, b)
+
+    def _set_vectors(self, unitcell, n, q, b):
+        self.unitcell = unitcell
+        self.n, self.qvec = np.ascontiguousarray(n, dtype=np.int32), np.asarray(q, dtype=np.float64)
+        bins, self.bin = np.unique(np.asarray(b), return_inverse=True)
+        self.bin = self.bin.reshape(-1)
+        self.nvectors = np.bincount(self.bin, minlength=bins.size).astype(np.int64)
+        self.q = np.bincount(self.bin, weights=self.qvec, minlength=bins.size) / self.nvectors
+        self.sum_s4 = np.zeros((len(self.lags), self.n.shape[0]))
+
+    def reset(self):
+        """Forget the samples and the wave vectors (the next use selects them again, for the cell it meets)."""
+        self.nsamples[:] = 0
+        self.sum_q[:] = 0
+        self.sum_q2[:] = 0
+        self.unitcell = None
+        self.n = self.qvec = self.bin = self.q = self.nvectors = self.sum_s4 = None
+
+    def schedule(self, total_steps):
+        """(stops, events) for one run of `total_steps` steps, exactly SelfDynamics.schedule's."""
+        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    def _accumulate(self, nsamples, sum_q, sum_q2, s4, n_particles, dt):
+        self.nsamples += np.asarray(nsamples, dtype=np.int64)
+        for k in range(len(self.lags)):
+            self.sum_q[k] += int(sum_q[k])
+            self.sum_q2[k] += int(sum_q2[k])
+        if self.sum_s4 is not None:
+            self.sum_s4 += np.asarray(s4, dtype=np.float64)
+        self.n_particles, self.dt = int(n_particles), float(dt)
+
+    def overlap(self):
+        """<Q> / N per lag: sum Q / (ns N); nan where a lag has no sample."""
+        return np.array([int(sq) / (int(ns) * self.n_particles) if ns > 0 else np.nan
+                         for ns, sq in zip(self.nsamples, self.sum_q)], dtype=np.float64)
+
+    def chi4(self):
+        """chi4 per lag: (ns sum Q^2 - (sum Q)^2) / (ns^2 N), the numerator formed in integers (nothing cancels in floating
+        point); nan where a lag has no sample."""
+        out = np.full(len(self.lags), np.nan)
+        for k, ns in enumerate(self.nsamples):
+            ns = int(ns)
+            if ns > 0:
+                out[k] = (ns * int(self.sum_q2[k]) - int(self.sum_q[k]) ** 2) / (ns * ns * self.n_particles)
+        return out
+
+    def s4_vectors(self):
+        """S4(q_v, t), (nlags, nvec): sum |W|^2 / (ns N); nan where a lag has no sample."""
+        if self.sum_s4 is None:
+            raise ValueError("no wave vectors: give q_max (and use the sampler once) for S4")
+        ns = self.nsamples.astype(np.float64)[:, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ns > 0, self.sum_s4 / (ns * self.n_particles), np.nan)
+
+    def s4(self):
+        """S4(q, t), (nlags, nbins): sum over the bin's vectors of sum |W|^2 / (ns N M_bin)."""
+        sv = self.s4_vectors()
+        return np.array([np.bincount(self.bin, weights=sv[k], minlength=self.q.size) / self.nvectors
+                         for k in range(sv.shape[0])]).reshape(sv.shape[0], self.q.size)
+
+    def write(self, path, dt=None):
+        """# lag time Q/N chi4 nsamples, one row per lag that has a sample, time = lag dt."""
+        dt = self.dt if dt is None else float(dt)
+        ov, c4 = self.overlap(), self.chi4()
+        with open(path, "w") as io:
+            io.write("# lag time Q/N chi4 nsamples\n")
+            for k, l in enumerate(self.lags):
+                if self.nsamples[k] > 0:
+                    io.write("%d %.6e %.6e %.6e %d\n" % (int(l), l * dt, ov[k], c4[k], int(self.nsamples[k])))
+
+    def write_s4(self, path, dt=None):
+        """One block per lag that has a sample, lines `lag time q S4 nvectors nsamples`, a blank line between blocks."""
+        dt = self.dt if dt is None else float(dt)
+        s4 = self.s4()
+        with open(path, "w") as io:
+            io.write("# lag time q S4 nvectors nsamples\n")
+            first = True
+            for k, l in enumerate(self.lags):
+                if self.nsamples[k] == 0:
+                    continue
+                if not first:
+                    io.write("\n")
+                first = False
+                for b in range(self.q.size):
+                    io.write("%d %.6e %.6f %.6e %d %d\n" % (int(l), l * dt, self.q[b], s4[k, b], self.nvectors[b],
+                                                          int(self.nsamples[k])))
+
+    # -- run_simulation's sampler protocol: the stops of schedule() ---------------------------------------------------
+    def _begin(self, dev, run):
+        self._stops, self._events = self.schedule(run.total_steps)
+        self._select(run.unitcell)
+        dev.chi4_setup(self.a, self.n, self.nslots, len(self.lags))
+
+    def _next(self, step):
+        return _next_stop(self._stops, step)
+
+    def _act(self, dev, step):
+        """The work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
+        smp, org = self._events[step]
+        if smp:
+            dev.chi4_sample([a for a, _ in smp], [b for _, b in smp])
+        if org is not None:
+            dev.chi4_origin(org)
+
+    def _finish(self, dev, run, pathname):
+        ns, sq, sq2, s4 = dev.chi4_read()
+        self._accumulate(ns, sq, sq2, s4, run.n, run.dt)
+        self.write(os.path.join(pathname, "chi4.txt"))
+        if self.sum_s4 is not None:
+            self.write_s4(os.path.join(pathname, "s4.txt"))

@@ -101,9 +101,13 @@ __device__ __forceinline__ void sq_cossin(double r, double &c, double &s)
 
 // nd: the wave vectors as doubles, 3 per vector (the third 0 in 2-D), padded with zero vectors to a multiple of
 // MD_SQ_TILE.  part[(v * 2 + comp) * nblk + block].
-template <int D>
-__global__ void __launch_bounds__(MD_SQ_BLOCK)
-    k_sq_rho(int n, int nblk, const double *__restrict__ fr, const double *__restrict__ nd, double *__restrict__ part)
+// MASKED (md_chi4.hpp): the same walk over the particles whose bit is set in mask (bit l of word k = particle id
+// 64 k + l, nwords words).  The 64 ids of a wave in one iteration are consecutive from a multiple of 64, so they share one
+// word: it is loaded once per wave and iteration through a wave-uniform address, a zero word skips the iteration, and a
+// particle whose bit is clear adds nothing -- the tree of the sum is the unmasked one.
+template <int D, bool MASKED>
+__device__ __forceinline__ void sq_walk(int n, int nblk, const double *__restrict__ fr, const double *__restrict__ nd,
+                                        double *__restrict__ part, const unsigned long long *__restrict__ mask, int nwords)
 {
 #pragma clang fp contract(off)
     __shared__ double wsum[MD_SQ_BLOCK / 64][2 * MD_SQ_TILE];
@@ -120,7 +124,14 @@ __global__ void __launch_bounds__(MD_SQ_BLOCK)
     const int base = blockIdx.x * (MD_SQ_BLOCK * MD_SQ_PPT) + threadIdx.x;
     for (int m = 0; m < MD_SQ_PPT; ++m) {
         const int i = base + m * MD_SQ_BLOCK;
-        if (i < n) {
+        bool on = i < n;
+        if constexpr (MASKED) {
+            const int k = __builtin_amdgcn_readfirstlane(i) >> 6; // (the wave's first id: a multiple of 64)
+            const unsigned long long word = k < nwords ? mask[k] : 0ull;
+            if (word == 0ull) continue; // (the whole wave)
+            on = on && ((word >> lane) & 1ull);
+        }
+        if (on) {
             const double f0 = fr[i], f1 = fr[(size_t)n + i];
             double f2 = 0.0;
             if constexpr (D == 3) f2 = fr[2 * (size_t)n + i];
@@ -153,6 +164,22 @@ __global__ void __launch_bounds__(MD_SQ_BLOCK)
         for (int w = 1; w < MD_SQ_BLOCK / 64; ++w) s = s + wsum[w][j];
         part[((size_t)v0 * 2 + j) * nblk + blockIdx.x] = s;
     }
+}
+
+template <int D>
+__global__ void __launch_bounds__(MD_SQ_BLOCK)
+    k_sq_rho(int n, int nblk, const double *__restrict__ fr, const double *__restrict__ nd, double *__restrict__ part)
+{
+    sq_walk<D, false>(n, nblk, fr, nd, part, nullptr, 0);
+}
+
+// W of md_chi4.hpp: the walk over the slow particles of one (origin, current frame) pair.
+template <int D>
+__global__ void __launch_bounds__(MD_SQ_BLOCK)
+    k_chi4_modes(int n, int nblk, const double *__restrict__ fr, const double *__restrict__ nd, double *__restrict__ part,
+                 const unsigned long long *__restrict__ mask, int nwords)
+{
+    sq_walk<D, true>(n, nblk, fr, nd, part, mask, nwords);
 }
 
 // One wave per vector.  reduce != 0: rho[v] from the block partials (and |rho|^2 into s2 if add_static); otherwise rho[v]

@@ -17,6 +17,7 @@
 #include "md_boo.hpp"
 #include "md_cluster.hpp"
 #include "md_cage.hpp"
+#include "md_chi4.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -400,6 +401,34 @@ struct md_ctx {
         }
         ~Cage() { release_table(); }
     } cage;
+
+    // four-point dynamics (md_chi4_*): per origin slot the frame and -- with vectors -- its fractional coordinates; the
+    // current frame; the mask, the block partials, Q and W of the sample in flight / the last one; the rows
+    struct Chi4 {
+        bool on = false;
+        bool sampled = false;             // mask / qlast / wlast hold a sample
+        int nvec = 0, nvec_pad = 0, nslots = 0, nrows = 0, nblk = 0, nwords = 0;
+        double a = 0.0, a2 = 0.0;
+        std::vector<char> filled;         // nslots: the slot holds an origin
+        std::vector<int64_t> nsamples;    // nrows: the host's count, behind the sum_q2 overflow guard
+        double *ox = nullptr;             // nslots frames of n x dim wrapped coordinates, in particle-id order
+        int32_t *oi = nullptr;            // nslots frames of n x dim image counts
+        double *of = nullptr;             // nslots frames of dim x n fractional coordinates, one array per axis (nvec > 0)
+        DBuf<double> nd, cx, part, wlast, s4; // nvec_pad x 3; frame; (vector, comp, block); 2 nvec; nrows x nvec
+        DBuf<int32_t> ci;
+        DBuf<unsigned long long> mask, qcur; // nwords; 1
+        DBuf<long long> qlast, irow;      // 1; nrows x MD_CHI4_NROW
+        void release_slots()
+        {
+            if (ox) (void)hipFree(ox);
+            if (oi) (void)hipFree(oi);
+            if (of) (void)hipFree(of);
+            ox = nullptr;
+            oi = nullptr;
+            of = nullptr;
+        }
+        ~Chi4() { release_slots(); }
+    } chi4;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1640,6 +1669,37 @@ void cage_zero(md_ctx *c)
     HIPCHK(hipMemsetAsync(G.hist.p, 0, sizeof(unsigned long long) * G.nrows * MD_CAGE_NHIST, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     std::fill(G.nsamples.begin(), G.nsamples.end(), (int64_t)0);
+}
+
+// ---- four-point dynamics (md_chi4.hpp): launches ---------------------------------------------------------------------
+
+// One (slot, row) sample against the current frame in cx / ci: three launches (two when there are no vectors).
+template <int D>
+void launch_chi4_sample(md_ctx *c, const DynParams &P, int slot, int row)
+{
+    md_ctx::Chi4 &X = c->chi4;
+    hipStream_t st = c->stream;
+    const size_t frame = (size_t)P.n * D;
+    const int oblk = (P.n + MD_CHI4_BLOCK * MD_CHI4_PPT - 1) / (MD_CHI4_BLOCK * MD_CHI4_PPT);
+    k_chi4_overlap<D><<<oblk, MD_CHI4_BLOCK, 0, st>>>(P, X.a2, X.cx.p, X.ci.p, X.ox + (size_t)slot * frame,
+                                                      X.oi + (size_t)slot * frame, X.mask.p, X.qcur.p);
+    if (X.nvec > 0)
+        k_chi4_modes<D><<<dim3(X.nblk, X.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(
+            P.n, X.nblk, X.of + (size_t)slot * frame, X.nd.p, X.part.p, X.mask.p, X.nwords);
+    const int rblk = std::max(1, (X.nvec + MD_SQ_REDUCE_BLOCK / 64 - 1) / (MD_SQ_REDUCE_BLOCK / 64));
+    k_chi4_reduce<<<rblk, MD_SQ_REDUCE_BLOCK, 0, st>>>(X.nvec, X.nblk, X.part.p, X.wlast.p,
+                                                       X.s4.p + (size_t)row * std::max(X.nvec, 1), X.qcur.p, X.qlast.p,
+                                                       X.irow.p + (size_t)row * MD_CHI4_NROW);
+    HIPCHK(hipGetLastError());
+}
+
+void chi4_zero(md_ctx *c)
+{
+    md_ctx::Chi4 &X = c->chi4;
+    HIPCHK(hipMemsetAsync(X.irow.p, 0, sizeof(long long) * X.nrows * MD_CHI4_NROW, c->stream));
+    HIPCHK(hipMemsetAsync(X.s4.p, 0, sizeof(double) * X.nrows * std::max(X.nvec, 1), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    std::fill(X.nsamples.begin(), X.nsamples.end(), (int64_t)0);
 }
 
 } // namespace
@@ -3228,6 +3288,217 @@ int md_cage_reset(md_ctx *ctx)
     API_BEGIN
     sampler_of(ctx, &md_ctx::cage, "md_cage_reset", "cage");
     cage_zero(ctx);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Four-point dynamics (md_chi4.hpp): an origin store and a sample each launch k_export into the sampler's own buffers and
+// read nothing else of the state, so the step loop, the list and the cell order are exactly what they would have been
+// without them.
+int md_chi4_setup(md_ctx *ctx, double a, const int32_t *nvecs, int nvec, int nslots, int nrows)
+{
+#pragma clang fp contract(off)
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_chi4_setup: not available on a slab-decomposition handle");
+    char b[320];
+    if (!(a > 0.0) || !std::isfinite(a)) throw HipError("md_chi4_setup: a must be finite and > 0");
+    check_range("md_chi4_setup", "nvec", nvec, 0, MD_CHI4_MAX_VEC);
+    if (nvec > 0 && !nvecs) throw HipError("md_chi4_setup: n is null");
+    check_range("md_chi4_setup", "nslots", nslots, 1, MD_CHI4_MAX_SLOTS);
+    if (nrows < 1) {
+        snprintf(b, sizeof b, "md_chi4_setup: nrows must be >= 1, got %d", nrows);
+        throw HipError(b);
+    }
+    const int dim = ctx->dim;
+    for (int v = 0; v < nvec; ++v) {
+        bool zero = true;
+        for (int c = 0; c < dim; ++c) {
+            const int32_t k = nvecs[(size_t)v * dim + c];
+            if (k < -MD_SQ_MAX_N || k > MD_SQ_MAX_N) {
+                snprintf(b, sizeof b, "md_chi4_setup: component %d of vector %d is %d, outside -%d..%d", c, v, (int)k,
+                         MD_SQ_MAX_N, MD_SQ_MAX_N);
+                throw HipError(b);
+            }
+            zero = zero && k == 0;
+        }
+        if (zero) {
+            snprintf(b, sizeof b, "md_chi4_setup: vector %d is n = 0 (W(0) = Q carries no information)", v);
+            throw HipError(b);
+        }
+    }
+    md_ctx::Chi4 &X = ctx->chi4;
+    X.on = false;
+    X.release_slots();
+    const int64_t n = ctx->n;
+    const size_t frame = (size_t)n * dim;
+    const size_t bytes = (size_t)nslots * frame * (nvec > 0 ? 20 : 12);
+    // MDHIP_CHI4_ALLOC_LIMIT=bytes: origin slots above this size are refused as if the device had run out of memory (a
+    // debug switch: the message can be checked at a test size)
+    const char *lim = getenv("MDHIP_CHI4_ALLOC_LIMIT");
+    hipError_t ea = hipSuccess, eb = hipSuccess, ec = hipSuccess;
+    if (lim && bytes > (size_t)strtoull(lim, nullptr, 10))
+        ea = hipErrorOutOfMemory;
+    else {
+        ea = hipMalloc((void **)&X.ox, (size_t)nslots * frame * sizeof(double));
+        if (ea == hipSuccess) eb = hipMalloc((void **)&X.oi, (size_t)nslots * frame * sizeof(int32_t));
+        if (ea == hipSuccess && eb == hipSuccess && nvec > 0)
+            ec = hipMalloc((void **)&X.of, (size_t)nslots * frame * sizeof(double));
+    }
+    if (ea != hipSuccess || eb != hipSuccess || ec != hipSuccess) {
+        (void)hipGetLastError();
+        X.release_slots();
+        snprintf(b, sizeof b,
+                 "md_chi4_setup: cannot allocate %zu bytes for %d origin slots (nslots*N*d*%d = %d*%lld*%d*%d): %s", bytes,
+                 nslots, nvec > 0 ? 20 : 12, nslots, (long long)n, dim, nvec > 0 ? 20 : 12,
+                 hipGetErrorString(ea != hipSuccess ? ea : (eb != hipSuccess ? eb : ec)));
+        throw HipError(b);
+    }
+    const int nblk = (int)((n + MD_SQ_BLOCK * MD_SQ_PPT - 1) / (MD_SQ_BLOCK * MD_SQ_PPT));
+    const int nvec_pad = (nvec + MD_SQ_TILE - 1) / MD_SQ_TILE * MD_SQ_TILE;
+    const int nwords = (int)((n + 63) / 64);
+    std::vector<double> nd((size_t)nvec_pad * 3, 0.0);
+    for (int v = 0; v < nvec; ++v)
+        for (int c = 0; c < dim; ++c) nd[(size_t)v * 3 + c] = (double)nvecs[(size_t)v * dim + c];
+    X.nd.alloc(nd.size());
+    X.cx.alloc(frame);
+    X.ci.alloc(frame);
+    X.part.alloc((size_t)nvec_pad * 2 * std::max(nblk, 1));
+    X.wlast.alloc((size_t)nvec * 2);
+    X.s4.alloc((size_t)nrows * std::max(nvec, 1));
+    X.mask.alloc(nwords);
+    X.qcur.alloc(1);
+    X.qlast.alloc(1);
+    X.irow.alloc((size_t)nrows * MD_CHI4_NROW);
+    hipStream_t st = ctx->stream;
+    if (!nd.empty()) HIPCHK(hipMemcpyAsync(X.nd.p, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(X.qcur.p, 0, sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(X.qlast.p, 0, sizeof(long long), st));
+    X.nvec = nvec;
+    X.nvec_pad = nvec_pad;
+    X.nslots = nslots;
+    X.nrows = nrows;
+    X.nblk = nblk;
+    X.nwords = nwords;
+    X.a = a;
+    X.a2 = a * a;
+    X.sampled = false;
+    X.filled.assign(nslots, 0);
+    X.nsamples.assign(nrows, 0);
+    chi4_zero(ctx); // (waits: the vector table is a host vector)
+    X.on = true;
+    API_END
+}
+
+int md_chi4_origin(md_ctx *ctx, int slot)
+{
+    API_BEGIN
+    md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_origin", "chi4");
+    require_state(ctx, "md_chi4_origin");
+    if (slot < 0 || slot >= X.nslots) {
+        char b[160];
+        snprintf(b, sizeof b, "md_chi4_origin: slot %d is out of range 0..%d", slot, X.nslots - 1);
+        throw HipError(b);
+    }
+    const int n = (int)ctx->n;
+    const size_t frame = (size_t)n * ctx->dim;
+    double *ox = X.ox + (size_t)slot * frame;
+    export_frame(ctx, ox, X.oi + (size_t)slot * frame);
+    if (X.nvec > 0) {
+        double *of = X.of + (size_t)slot * frame;
+        if (ctx->dim == 3)
+            k_sq_frac<3><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, ox, of);
+        else
+            k_sq_frac<2><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, ox, of);
+        HIPCHK(hipGetLastError());
+    }
+    X.filled[slot] = 1;
+    API_END
+}
+
+int md_chi4_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int count)
+{
+    API_BEGIN
+    md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_sample", "chi4");
+    require_state(ctx, "md_chi4_sample");
+    check_batch("md_chi4_sample", slots, rows, count, X.nslots, X.nrows, X.filled,
+                "store an origin with md_chi4_origin first");
+    if (count == 0) return 0;
+    // sum_q2 gains at most N^2 per sample: refuse the call before anything is launched if a row could pass the limit
+    // (MDHIP_CHI4_SUMQ2_LIMIT=value lowers it from 2^63 - 1: a debug switch, the refusal can be checked at a test size)
+    {
+        const char *lim = getenv("MDHIP_CHI4_SUMQ2_LIMIT");
+        const __int128 limit = lim ? (__int128)strtoull(lim, nullptr, 10) : (__int128)INT64_MAX;
+        const __int128 n2 = (__int128)ctx->n * (__int128)ctx->n;
+        std::vector<int64_t> ns(X.nsamples);
+        for (int i = 0; i < count; ++i) {
+            if ((__int128)(ns[rows[i]] + 1) * n2 > limit) {
+                char b[240];
+                snprintf(b, sizeof b,
+                         "md_chi4_sample: row %d already holds %lld samples; one more could overflow sum_q2 ((nsamples + 1) "
+                         "N^2 > %s with N = %lld): read and reset first",
+                         (int)rows[i], (long long)ns[rows[i]], lim ? lim : "2^63 - 1", (long long)ctx->n);
+                throw HipError(b);
+            }
+            ++ns[rows[i]];
+        }
+    }
+    export_frame(ctx, X.cx.p, X.ci.p);
+    DynParams P{};
+    P.n = (int)ctx->n;
+    P.dim = ctx->dim;
+    for (int c = 0; c < 9; ++c) P.U[c] = ctx->A[c];
+    for (int i = 0; i < count; ++i) {
+        if (ctx->dim == 3)
+            launch_chi4_sample<3>(ctx, P, slots[i], rows[i]);
+        else
+            launch_chi4_sample<2>(ctx, P, slots[i], rows[i]);
+        ++X.nsamples[rows[i]];
+        X.sampled = true;
+    }
+    API_END
+}
+
+int md_chi4_last(md_ctx *ctx, int64_t *q, double *w, void *slow_bytes)
+{
+    uint8_t *slow = static_cast<uint8_t *>(slow_bytes);
+    API_BEGIN
+    md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_last", "chi4");
+    if (!X.sampled) throw HipError("md_chi4_last: no sample taken yet (call md_chi4_sample first)");
+    hipStream_t st = ctx->stream;
+    long long ql = 0;
+    std::vector<unsigned long long> m(slow ? X.nwords : 0);
+    if (q) HIPCHK(hipMemcpyAsync(&ql, X.qlast.p, sizeof ql, hipMemcpyDeviceToHost, st));
+    if (w && X.nvec) HIPCHK(hipMemcpyAsync(w, X.wlast.p, sizeof(double) * X.nvec * 2, hipMemcpyDeviceToHost, st));
+    if (slow) HIPCHK(hipMemcpyAsync(m.data(), X.mask.p, sizeof(unsigned long long) * X.nwords, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (q) *q = ql;
+    if (slow)
+        for (int64_t i = 0; i < ctx->n; ++i) slow[i] = (uint8_t)((m[i >> 6] >> (i & 63)) & 1ull);
+    API_END
+}
+
+int md_chi4_read(md_ctx *ctx, int64_t *nsamples, int64_t *sum_q, int64_t *sum_q2, double *s4)
+{
+    API_BEGIN
+    md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_read", "chi4");
+    hipStream_t st = ctx->stream;
+    std::vector<long long> r((size_t)X.nrows * MD_CHI4_NROW);
+    HIPCHK(hipMemcpyAsync(r.data(), X.irow.p, sizeof(long long) * r.size(), hipMemcpyDeviceToHost, st));
+    if (s4 && X.nvec) HIPCHK(hipMemcpyAsync(s4, X.s4.p, sizeof(double) * X.nrows * X.nvec, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < X.nrows; ++k) {
+        if (sum_q) sum_q[k] = r[(size_t)k * MD_CHI4_NROW];
+        if (sum_q2) sum_q2[k] = r[(size_t)k * MD_CHI4_NROW + 1];
+        if (nsamples) nsamples[k] = r[(size_t)k * MD_CHI4_NROW + 2];
+    }
+    API_END
+}
+
+int md_chi4_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    sampler_of(ctx, &md_ctx::chi4, "md_chi4_reset", "chi4");
+    chi4_zero(ctx);
     API_END
 }
 

@@ -430,6 +430,56 @@ class MDDevice:
     def cage_reset(self):
         self._chk(self._L.md_cage_reset(self._h))
 
+    # -- four-point dynamics: the overlap Q, chi4, S4(q, t) --------------------------------
+    def chi4_setup(self, a, n=None, nslots=1, nrows=1):
+        """Allocate the device four-point sampler (md_chi4_setup): a particle is slow while it has moved less than `a`
+        since the origin; the integer wave vectors n (nvec <= 4096, d) of W(q), or None / empty for chi4 only; nslots
+        origin slots; nrows zeroed rows of {sum Q, sum Q^2, samples, sum |W|^2 per vector}."""
+        na = np.zeros((0, self.dim), dtype=np.int32) if n is None else np.ascontiguousarray(n, dtype=np.int32)
+        if na.ndim != 2 or na.shape[1] != self.dim:
+            raise ValueError(f"n must have shape (nvec, {self.dim})")
+        self._chk(self._L.md_chi4_setup(self._h, float(a), _ip(na) if na.size else None, int(na.shape[0]), int(nslots),
+                                        int(nrows)))
+        self._chi4_shape = (int(nrows), int(na.shape[0]))
+
+    def chi4_origin(self, slot):
+        """Store the current frame (and, with vectors, its fractional coordinates) in `slot` (does not wait)."""
+        self._chk(self._L.md_chi4_origin(self._h, int(slot)))
+
+    def chi4_sample(self, slots, rows):
+        """Export the current frame once and add one sample per (slots[i], rows[i]), in order: the overlap of this frame
+        with the origin in slots[i] and W on the slow particles, accumulated into rows[i] (does not wait, changes no
+        state)."""
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+        if s.shape != r.shape:
+            raise ValueError("slots and rows must have the same length")
+        self._chk(self._L.md_chi4_sample(self._h, _ip(s), _ip(r), int(s.size)))
+
+    def chi4_last(self):
+        """(Q int, W complex128[nvec], slow uint8[N] by particle id) of the last (slot, row) of the last chi4_sample call;
+        waits."""
+        _, nvec = getattr(self, "_chi4_shape", (0, 0))
+        q = C.c_int64()
+        w = np.zeros((max(nvec, 1), 2))
+        slow = np.zeros(self.n, dtype=np.uint8)
+        self._chk(self._L.md_chi4_last(self._h, C.byref(q), _dp(w), slow.ctypes.data_as(C.c_void_p)))
+        return q.value, w[:nvec].copy().view(np.complex128).reshape(nvec), slow
+
+    def chi4_read(self):
+        """(nsamples int64[nrows], sum_q int64[nrows], sum_q2 int64[nrows], s4 float64[nrows, nvec]), summed since setup /
+        reset; waits."""
+        nrows, nvec = getattr(self, "_chi4_shape", (0, 0))
+        ns, sq, sq2 = (np.zeros(max(nrows, 1), dtype=np.int64) for _ in range(3))
+        s4 = np.zeros(max(nrows * nvec, 1))
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.md_chi4_read(self._h, ns.ctypes.data_as(i64), sq.ctypes.data_as(i64), sq2.ctypes.data_as(i64),
+                                       _dp(s4)))
+        return ns[:nrows], sq[:nrows], sq2[:nrows], s4[: nrows * nvec].reshape(nrows, nvec)
+
+    def chi4_reset(self):
+        self._chk(self._L.md_chi4_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

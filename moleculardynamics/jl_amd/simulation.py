@@ -36,7 +36,7 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, sq=None, stress=None, clusters=None, cage=None, bond_order=None):
+                   dynamics=None, sq=None, stress=None, four_point=None, clusters=None, cage=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -79,7 +79,13 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     steps, the schedule restarts at step 0 in every call, the samples accumulate in the object).  Written to
     pathname/cage.txt.  It never evaluates the potential: it works with Brownian dynamics and with user potentials.  More
     neighbours than cage.max_neighbours at an origin is an error at the end of the run.  Nothing else the run produces
-    changes."""
+    changes.
+
+    four_point: a FourPoint (analysis.py) to sample the self overlap Q(t), the four-point susceptibility chi4(t) and, if it
+    has wave vectors, the structure factor S4(q, t) of the slow particles into, on the device, at the steps of its
+    schedule (SelfDynamics' rules: the stops are added to the loop's output steps, the schedule restarts at step 0 in
+    every call, the samples accumulate in the object).  Written to pathname/chi4.txt and, with vectors, pathname/s4.txt.
+    It never evaluates the potential.  Nothing else the run produces changes."""
     if clusters is not None and clusters.members == "solid":
         if bond_order is None:
             raise ValueError('clusters with members="solid" needs bond_order= in the same run')
@@ -106,8 +112,9 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     # the virial is sampled every 10th step and averaged at the output steps (:253-266)
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
     # the samplers (analysis.py's protocol), in the order their device calls are made at a step they share
-    # (clusters after bond_order: with members="solid" it reads the bond-order frame of the same step; cage last)
-    samplers = [s for s in (rdf, dynamics, sq, stress, bond_order) + (clusters, cage) if s is not None]
+    # (clusters after bond_order: with members="solid" it reads the bond-order frame of the same step; then cage;
+    # four_point last)
+    samplers = [s for s in (rdf, dynamics, sq, stress, bond_order) + (clusters, cage, four_point) if s is not None]
     run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
                                 unitcell=state.unitcell, brownian=brownian)
     for s in samplers:
