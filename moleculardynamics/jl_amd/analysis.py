@@ -206,7 +206,62 @@ def _schedule(maxlog, lags, origin_every, nslots, total_steps):
     return stops, events
 
 
-class SelfDynamics:
+def _check_q(q):
+    """The wavenumbers of SelfDynamics / CageDynamics as a float64 array: at most 16, all finite."""
+    q = np.array([float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64))], dtype=np.float64)
+    if q.size > 16:
+        raise ValueError("at most 16 wavenumbers q")
+    if not np.all(np.isfinite(q)):
+        raise ValueError("every q must be finite")
+    return q
+
+
+def _write_blocks(path, header, lags, nsamples, lines):
+    """`header`, then one block per lag that has a sample -- the lines that lines(k, lag) yields -- with a blank line
+    between blocks."""
+    with open(path, "w") as io:
+        io.write(header)
+        first = True
+        for k, l in enumerate(lags):
+            if nsamples[k] == 0:
+                continue
+            if not first:
+                io.write("\n")
+            first = False
+            io.writelines(lines(k, l))
+
+
+class _Scheduled:
+    """What the samplers that correlate a frame with stored origins share: the schedule (lags, origin_every) and, for
+    run_simulation's sampler protocol, the stops of schedule() and the device calls dev.<_prefix>_sample / _origin."""
+    _prefix = None
+
+    def _set_schedule(self, lags, origin_every):
+        """maxlog, origin_every, nslots, lags and an all-zero nsamples; returns the number of lags."""
+        self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+        self.lags = np.array(lag_list, dtype=np.int64)
+        self.nsamples = np.zeros(len(lag_list), dtype=np.int64)
+        return len(lag_list)
+
+    def schedule(self, total_steps):
+        """(stops, events) for one run of `total_steps` steps: the sorted steps where the sampler acts, and per stop a
+        pair (samples, origin): samples = [(slot, row), ...] in origin order, origin = the slot the frame is stored in
+        after them, or None."""
+        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
+
+    def _next(self, step):
+        return _next_stop(self._stops, step)
+
+    def _act(self, dev, step):
+        """The work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
+        smp, org = self._events[step]
+        if smp:
+            getattr(dev, self._prefix + "_sample")([a for a, _ in smp], [b for _, b in smp])
+        if org is not None:
+            getattr(dev, self._prefix + "_origin")(org)
+
+
+class SelfDynamics(_Scheduled):
     """Self dynamics of the particles, accumulated on the device over the samples of a schedule until reset().
 
     q: up to 16 wavenumbers for F_s(q, t).  r_max, nbins: the van Hove histogram (nbins = 0: none).  The schedule:
@@ -217,13 +272,10 @@ class SelfDynamics:
     samples accumulate here across calls.
 
     Fields: lags, nsamples (per lag), sums (per lag: sum d2, sum d4, sum s(q) per q), hist (per lag and bin), edges, r."""
+    _prefix = "dyn"
 
     def __init__(self, q=(2.0 * math.pi,), r_max=None, nbins=0, lags=None, origin_every=None):
-        q = np.array([float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64))], dtype=np.float64)
-        if q.size > 16:
-            raise ValueError("at most 16 wavenumbers q")
-        if not np.all(np.isfinite(q)):
-            raise ValueError("every q must be finite")
+        q = _check_q(q)
         nbins = int(nbins)
         if not 0 <= nbins <= 8192:
             raise ValueError("nbins must be in 0..8192")
@@ -233,11 +285,8 @@ class SelfDynamics:
             r_max = float(r_max)
         else:
             r_max = None if r_max is None else float(r_max)
-        self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+        nl = self._set_schedule(lags, origin_every)
         self.q, self.r_max, self.nbins = q, r_max, nbins
-        self.lags = np.array(lag_list, dtype=np.int64)
-        nl = len(lag_list)
-        self.nsamples = np.zeros(nl, dtype=np.int64)
         self.sums = np.zeros((nl, 2 + q.size))
         self.hist = np.zeros((nl, nbins), dtype=np.int64)
         self.edges = np.arange(nbins + 1, dtype=np.float64) * (r_max / nbins) if nbins else np.zeros(1)
@@ -250,13 +299,6 @@ class SelfDynamics:
         self.nsamples[:] = 0
         self.sums[:] = 0.0
         self.hist[:] = 0
-
-    # -- schedule ---------------------------------------------------------------------------------------------------
-    def schedule(self, total_steps):
-        """(stops, events) for one run of `total_steps` steps: the sorted steps where the sampler acts, and per stop a
-        pair (samples, origin): samples = [(slot, row), ...] in origin order, origin = the slot the frame is stored in
-        after them, or None."""
-        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
 
     # -- results ----------------------------------------------------------------------------------------------------
     def _accumulate(self, nsamples, sums, hist, n_particles, dimension, dt):
@@ -310,34 +352,13 @@ class SelfDynamics:
     def write_van_hove(self, path):
         """One block per lag that has a sample, lines `lag r G_s count`, a blank line between blocks."""
         g = self.van_hove()
-        with open(path, "w") as io:
-            io.write("# lag r G_s count\n")
-            first = True
-            for k, l in enumerate(self.lags):
-                if self.nsamples[k] == 0:
-                    continue
-                if not first:
-                    io.write("\n")
-                first = False
-                for b in range(self.nbins):
-                    io.write("%d %.6f %.6e %d\n" % (int(l), self.r[b], g[k, b], self.hist[k, b]))
+        _write_blocks(path, "# lag r G_s count\n", self.lags, self.nsamples, lambda k, l: (
+            "%d %.6f %.6e %d\n" % (int(l), self.r[b], g[k, b], self.hist[k, b]) for b in range(self.nbins)))
 
-
-    # -- run_simulation's sampler protocol: the stops of schedule() ---------------------------------------------------
+    # -- run_simulation's sampler protocol: the stops of schedule() (_next and _act are _Scheduled's) -------------------
     def _begin(self, dev, run):
         self._stops, self._events = self.schedule(run.total_steps)
         dev.dyn_setup(self.nslots, len(self.lags), self.q, self.r_max or 0.0, self.nbins)
-
-    def _next(self, step):
-        return _next_stop(self._stops, step)
-
-    def _act(self, dev, step):
-        """The work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
-        smp, org = self._events[step]
-        if smp:
-            dev.dyn_sample([a for a, _ in smp], [b for _, b in smp])
-        if org is not None:
-            dev.dyn_origin(org)
 
     def _finish(self, dev, run, pathname):
         ns, sums, hist = dev.dyn_read()
@@ -451,7 +472,38 @@ def wave_vector_lengths(unitcell, n):
     return 2.0 * math.pi * np.linalg.norm(np.asarray(n, dtype=np.float64) @ np.linalg.inv(u), axis=1)
 
 
-class StructureFactor:
+class _WaveVectors:
+    """What the samplers on select_wave_vectors' vectors share: the selection for the cell of the first use (q_max=None:
+    none; at most _max_vectors, refused with the class's _too_many message), the |q| bins, the bin average."""
+    _max_vectors = _too_many = None
+
+    def _select(self, unitcell):
+        if self.q_max is None:
+            return
+        u = np.array(unitcell, dtype=np.float64)
+        if self.unitcell is not None:
+            if u.shape != self.unitcell.shape or not np.array_equal(u, self.unitcell):
+                raise ValueError("the unit cell differs from the one the wave vectors were selected for; reset() first")
+            return
+        n, q, b = select_wave_vectors(u, self.q_max, self.dq, self.max_per_bin, self.seed)
+        if self._max_vectors is not None and n.shape[0] > self._max_vectors:
+            raise ValueError(self._too_many.format(n.shape[0]))
+        self._set_vectors(u, n, q, b)
+
+    def _set_vectors(self, unitcell, n, q, b):
+        self.unitcell = unitcell
+        self.n, self.qvec = np.ascontiguousarray(n, dtype=np.int32), np.asarray(q, dtype=np.float64)
+        bins, self.bin = np.unique(np.asarray(b), return_inverse=True)
+        self.bin = self.bin.reshape(-1)
+        self.nvectors = np.bincount(self.bin, minlength=bins.size).astype(np.int64)
+        self.q = np.bincount(self.bin, weights=self.qvec, minlength=bins.size) / self.nvectors
+        self._zero_vector_sums(self.n.shape[0])
+
+    def _binned(self, per_vector):
+        return np.bincount(self.bin, weights=per_vector, minlength=self.q.size) / self.nvectors
+
+
+class StructureFactor(_Scheduled, _WaveVectors):
     """S(q) and, with dynamic=True, the coherent F(q, t), accumulated on the device until reset().
 
     The wave vectors are select_wave_vectors(unitcell, q_max, dq, max_per_bin, seed) of the cell the sampler is first used
@@ -476,37 +528,21 @@ class StructureFactor:
         self.q_max, self.dq, self.max_per_bin, self.seed, self.every = q_max, dq, max_per_bin, seed, every
         self.dynamic = bool(dynamic)
         if self.dynamic:
-            self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+            self._set_schedule(lags, origin_every)
         else:
             if lags is not None or origin_every is not None:
                 raise ValueError("lags and origin_every need dynamic=True")
-            self.maxlog, lag_list, self.origin_every, self.nslots = None, [], None, 0
-        self.lags = np.array(lag_list, dtype=np.int64)
-        self.nsamples = np.zeros(len(lag_list), dtype=np.int64)
+            self.maxlog, self.origin_every, self.nslots = None, None, 0
+            self.lags, self.nsamples = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
         self.nstatic = 0
         self.unitcell = None
         self.n = self.qvec = self.bin = self.q = self.nvectors = self.s2 = self.corr = None
         self.n_particles = 0
         self.dt = 1.0
 
-    def _select(self, unitcell):
-        u = np.array(unitcell, dtype=np.float64)
-        if self.unitcell is not None:
-            if u.shape != self.unitcell.shape or not np.array_equal(u, self.unitcell):
-                raise ValueError("the unit cell differs from the one the wave vectors were selected for; reset() first")
-            return
-        n, q, b = select_wave_vectors(u, self.q_max, self.dq, self.max_per_bin, self.seed)
-        self._set_vectors(u, n, q, b)
-
-    def _set_vectors(self, unitcell, n, q, b):
-        self.unitcell = unitcell
-        self.n, self.qvec = np.ascontiguousarray(n, dtype=np.int32), np.asarray(q, dtype=np.float64)
-        bins, self.bin = np.unique(np.asarray(b), return_inverse=True)
-        self.bin = self.bin.reshape(-1)
-        self.nvectors = np.bincount(self.bin, minlength=bins.size).astype(np.int64)
-        self.q = np.bincount(self.bin, weights=self.qvec, minlength=bins.size) / self.nvectors
-        self.s2 = np.zeros(self.n.shape[0])
-        self.corr = np.zeros((len(self.lags), self.n.shape[0]))
+    def _zero_vector_sums(self, nvec):
+        self.s2 = np.zeros(nvec)
+        self.corr = np.zeros((len(self.lags), nvec))
 
     def reset(self):
         """Forget the samples and the wave vectors (the next use selects them again, for the cell it meets)."""
@@ -517,9 +553,7 @@ class StructureFactor:
 
     def schedule(self, total_steps):
         """(stops, events) of the dynamic part, as SelfDynamics.schedule; empty without dynamic=True."""
-        if not self.dynamic:
-            return [], {}
-        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
+        return super().schedule(total_steps) if self.dynamic else ([], {})
 
     def _accumulate(self, nstatic, s2, nsamples, corr, n_particles, dt):
         self.nstatic += int(nstatic)
@@ -530,9 +564,6 @@ class StructureFactor:
         self.n_particles, self.dt = int(n_particles), float(dt)
 
     # -- results ----------------------------------------------------------------------------------------------------
-    def _binned(self, per_vector):
-        return np.bincount(self.bin, weights=per_vector, minlength=self.q.size) / self.nvectors
-
     def s_vectors(self):
         """S(q_v) per wave vector: s2_v / (nstatic N); nan before the first static sample."""
         if self.nstatic == 0:
@@ -571,19 +602,9 @@ class StructureFactor:
         """One block per lag that has a sample, lines `lag time q F F/S nsamples`, a blank line between blocks."""
         dt = self.dt if dt is None else float(dt)
         f, fn = self.f(), self.f_normalised()
-        with open(path, "w") as io:
-            io.write("# lag time q F F/S nsamples\n")
-            first = True
-            for k, l in enumerate(self.lags):
-                if self.nsamples[k] == 0:
-                    continue
-                if not first:
-                    io.write("\n")
-                first = False
-                for b in range(self.q.size):
-                    io.write("%d %.6e %.6f %.6e %.6e %d\n" % (int(l), l * dt, self.q[b], f[k, b], fn[k, b],
-                                                            int(self.nsamples[k])))
-
+        _write_blocks(path, "# lag time q F F/S nsamples\n", self.lags, self.nsamples, lambda k, l: (
+            "%d %.6e %.6f %.6e %.6e %d\n" % (int(l), l * dt, self.q[b], f[k, b], fn[k, b], int(self.nsamples[k]))
+            for b in range(self.q.size)))
 
     # -- run_simulation's sampler protocol: static at every `every`-th output step, dynamic at the stops of schedule() -
     def _begin(self, dev, run):
@@ -1163,7 +1184,7 @@ def compute_clusters(state, params, r_bond, members="all", bond_order=None):
 # Cage-relative dynamics and bond breaking, sampled on the device (md_cage_*): displacements measured relative to the
 # mean displacement of the neighbours a particle had at the time origin, and the fraction of origin bonds that survive.
 
-class CageDynamics:
+class CageDynamics(_Scheduled):
     """Cage-relative self dynamics and the bond-breaking correlation, accumulated on the device over the samples of a
     schedule until reset().
 
@@ -1176,6 +1197,7 @@ class CageDynamics:
 
     Fields: lags, nsamples (per lag), sums (per lag: sum d2, sum d4, sum s(q) per q, of Del^CR), counts (per lag: particles
     with neighbours, sum n_i, surviving bonds), hist_broken (per lag: particles by their number of broken bonds, 0..32)."""
+    _prefix = "cage"
 
     def __init__(self, r_neigh, r_break=None, scaled=False, max_neighbours=16, q=(2.0 * math.pi,), lags=None,
                  origin_every=None):
@@ -1187,17 +1209,10 @@ class CageDynamics:
             raise ValueError("r_break must be finite and >= r_neigh")
         if int(max_neighbours) != max_neighbours or not 1 <= int(max_neighbours) <= 32:
             raise ValueError("max_neighbours must be in 1..32")
-        q = np.array([float(v) for v in np.atleast_1d(np.asarray(q, dtype=np.float64))], dtype=np.float64)
-        if q.size > 16:
-            raise ValueError("at most 16 wavenumbers q")
-        if not np.all(np.isfinite(q)):
-            raise ValueError("every q must be finite")
-        self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+        q = _check_q(q)
+        nl = self._set_schedule(lags, origin_every)
         self.r_neigh, self.r_break, self.scaled, self.max_neighbours = r_neigh, r_break, bool(scaled), int(max_neighbours)
         self.q = q
-        self.lags = np.array(lag_list, dtype=np.int64)
-        nl = len(lag_list)
-        self.nsamples = np.zeros(nl, dtype=np.int64)
         self.sums = np.zeros((nl, 2 + q.size))
         self.counts = np.zeros((nl, 3), dtype=np.int64)
         self.hist_broken = np.zeros((nl, 33), dtype=np.int64)
@@ -1209,10 +1224,6 @@ class CageDynamics:
         self.sums[:] = 0.0
         self.counts[:] = 0
         self.hist_broken[:] = 0
-
-    def schedule(self, total_steps):
-        """(stops, events) for one run of `total_steps` steps, exactly SelfDynamics.schedule's."""
-        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
 
     # -- results ----------------------------------------------------------------------------------------------------
     def _accumulate(self, nsamples, sums, counts, hist_broken, dimension, dt):
@@ -1266,21 +1277,10 @@ class CageDynamics:
                 if self.nsamples[k] > 0:
                     io.write(fmt % ((int(l), l * dt, msd[k], a2[k]) + tuple(fs[k]) + (cb[k], int(self.nsamples[k]))))
 
-    # -- run_simulation's sampler protocol: the stops of schedule() ---------------------------------------------------
+    # -- run_simulation's sampler protocol: the stops of schedule() (_next and _act are _Scheduled's) -------------------
     def _begin(self, dev, run):
         self._stops, self._events = self.schedule(run.total_steps)
         dev.cage_setup(self.nslots, len(self.lags), self.r_neigh, self.r_break, self.scaled, self.max_neighbours, self.q)
-
-    def _next(self, step):
-        return _next_stop(self._stops, step)
-
-    def _act(self, dev, step):
-        """The work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
-        smp, org = self._events[step]
-        if smp:
-            dev.cage_sample([a for a, _ in smp], [b for _, b in smp])
-        if org is not None:
-            dev.cage_origin(org)
 
     def _finish(self, dev, run, pathname):
         ns, sums, counts, hist, overflow = dev.cage_read()
@@ -1296,7 +1296,7 @@ class CageDynamics:
 # Four-point dynamics, sampled on the device (md_chi4_*): the self overlap Q(t0, t) = sum_i w_i of the particles that
 # moved less than a, its variance chi4(t) and the structure factor S4(q, t) of the slow particles.
 
-class FourPoint:
+class FourPoint(_Scheduled, _WaveVectors):
     """Dynamic heterogeneity from the four-point functions of the self overlap, accumulated on the device over the samples
     of a schedule until reset().
 
@@ -1314,6 +1314,9 @@ class FourPoint:
 
     Fields: lags, nsamples (per lag), sum_q, sum_q2 (per lag, Python integers), n (nvec, d), qvec, bin, q (mean |q| of a
     bin), nvectors (per bin), sum_s4 (nlags, nvec: sum |W|^2)."""
+    _prefix = "chi4"
+    _max_vectors = 4096
+    _too_many = "{} wave vectors selected; FourPoint takes at most 4096 (lower q_max or max_per_bin, or widen dq)"
 
     def __init__(self, a, q_max=None, dq=None, max_per_bin=16, seed=0, lags=None, origin_every=None):
         a = float(a)
@@ -1329,11 +1332,8 @@ class FourPoint:
             raise ValueError("dq must be finite and > 0")
         if int(max_per_bin) < 1:
             raise ValueError("max_per_bin must be >= 1")
-        self.maxlog, lag_list, self.origin_every, self.nslots = _parse_schedule(lags, origin_every)
+        nl = self._set_schedule(lags, origin_every)
         self.a, self.q_max, self.dq, self.max_per_bin, self.seed = a, q_max, dq, int(max_per_bin), seed
-        self.lags = np.array(lag_list, dtype=np.int64)
-        nl = len(lag_list)
-        self.nsamples = np.zeros(nl, dtype=np.int64)
         self.sum_q = np.array([0] * nl, dtype=object)
         self.sum_q2 = np.array([0] * nl, dtype=object)
         self.unitcell = None
@@ -1341,28 +1341,8 @@ class FourPoint:
         self.n_particles = 0
         self.dt = 1.0
 
-    def _select(self, unitcell):
-        if self.q_max is None:
-            return
-        u = np.array(unitcell, dtype=np.float64)
-        if self.unitcell is not None:
-            if u.shape != self.unitcell.shape or not np.array_equal(u, self.unitcell):
-                raise ValueError("the unit cell differs from the one the wave vectors were selected for; reset() first")
-            return
-        n, q, b = select_wave_vectors(u, self.q_max, self.dq, self.max_per_bin, self.seed)
-        if n.shape[0] > 4096:
-            raise ValueError(f"{n.shape[0]} wave vectors selected; FourPoint takes at most 4096 (lower q_max or "
-                             "max_per_bin, or widen dq)")
-        self._set_vectors(u, n, q, b)
-
-    def _set_vectors(self, unitcell, n, q, b):
-        self.unitcell = unitcell
-        self.n, self.qvec = np.ascontiguousarray(n, dtype=np.int32), np.asarray(q, dtype=np.float64)
-        bins, self.bin = np.unique(np.asarray(b), return_inverse=True)
-        self.bin = self.bin.reshape(-1)
-        self.nvectors = np.bincount(self.bin, minlength=bins.size).astype(np.int64)
-        self.q = np.bincount(self.bin, weights=self.qvec, minlength=bins.size) / self.nvectors
-        self.sum_s4 = np.zeros((len(self.lags), self.n.shape[0]))
+    def _zero_vector_sums(self, nvec):
+        self.sum_s4 = np.zeros((len(self.lags), nvec))
 
     def reset(self):
         """Forget the samples and the wave vectors (the next use selects them again, for the cell it meets)."""
@@ -1371,10 +1351,6 @@ class FourPoint:
         self.sum_q2[:] = 0
         self.unitcell = None
         self.n = self.qvec = self.bin = self.q = self.nvectors = self.sum_s4 = None
-
-    def schedule(self, total_steps):
-        """(stops, events) for one run of `total_steps` steps, exactly SelfDynamics.schedule's."""
-        return _schedule(self.maxlog, self.lags, self.origin_every, self.nslots, total_steps)
 
     # -- results ----------------------------------------------------------------------------------------------------
     def _accumulate(self, nsamples, sum_q, sum_q2, s4, n_particles, dt):
@@ -1412,8 +1388,7 @@ class FourPoint:
     def s4(self):
         """S4(q, t), (nlags, nbins): sum over the bin's vectors of sum |W|^2 / (ns N M_bin)."""
         sv = self.s4_vectors()
-        return np.array([np.bincount(self.bin, weights=sv[k], minlength=self.q.size) / self.nvectors
-                         for k in range(sv.shape[0])]).reshape(sv.shape[0], self.q.size)
+        return np.array([self._binned(sv[k]) for k in range(sv.shape[0])]).reshape(sv.shape[0], self.q.size)
 
     def write(self, path, dt=None):
         """# lag time Q/N chi4 nsamples, one row per lag that has a sample, time = lag dt."""
@@ -1429,35 +1404,15 @@ class FourPoint:
         """One block per lag that has a sample, lines `lag time q S4 nvectors nsamples`, a blank line between blocks."""
         dt = self.dt if dt is None else float(dt)
         s4 = self.s4()
-        with open(path, "w") as io:
-            io.write("# lag time q S4 nvectors nsamples\n")
-            first = True
-            for k, l in enumerate(self.lags):
-                if self.nsamples[k] == 0:
-                    continue
-                if not first:
-                    io.write("\n")
-                first = False
-                for b in range(self.q.size):
-                    io.write("%d %.6e %.6f %.6e %d %d\n" % (int(l), l * dt, self.q[b], s4[k, b], self.nvectors[b],
-                                                          int(self.nsamples[k])))
+        _write_blocks(path, "# lag time q S4 nvectors nsamples\n", self.lags, self.nsamples, lambda k, l: (
+            "%d %.6e %.6f %.6e %d %d\n" % (int(l), l * dt, self.q[b], s4[k, b], self.nvectors[b], int(self.nsamples[k]))
+            for b in range(self.q.size)))
 
-    # -- run_simulation's sampler protocol: the stops of schedule() ---------------------------------------------------
+    # -- run_simulation's sampler protocol: the stops of schedule() (_next and _act are _Scheduled's) -------------------
     def _begin(self, dev, run):
         self._stops, self._events = self.schedule(run.total_steps)
         self._select(run.unitcell)
         dev.chi4_setup(self.a, self.n, self.nslots, len(self.lags))
-
-    def _next(self, step):
-        return _next_stop(self._stops, step)
-
-    def _act(self, dev, step):
-        """The work at one stop: the samples, then the origin (the frame is exported once for all samples)."""
-        smp, org = self._events[step]
-        if smp:
-            dev.chi4_sample([a for a, _ in smp], [b for _, b in smp])
-        if org is not None:
-            dev.chi4_origin(org)
 
     def _finish(self, dev, run, pathname):
         ns, sq, sq2, s4 = dev.chi4_read()

@@ -65,6 +65,17 @@ struct DBuf {
         HIPCHK(hipMalloc((void **)&p, count * sizeof(T)));
         n = count;
     }
+    hipError_t try_alloc(size_t count) // alloc that reports instead of throwing; the buffer stays empty on failure
+    {
+        release();
+        if (count == 0) count = 1;
+        hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+        if (e == hipSuccess)
+            n = count;
+        else
+            p = nullptr;
+        return e;
+    }
     void ensure(size_t count)
     {
         if (count > n) alloc(count + count / 4 + 16);
@@ -76,6 +87,79 @@ struct DBuf {
         n = 0;
     }
     ~DBuf() { release(); }
+};
+
+// A sampler's large storage (md_dyn / md_chi4 origin slots, the md_cage table), `bytes` in all, described by `what`: the
+// buffers are released, then allocated in order (one of count 0 stays empty).  The first failure -- or `bytes` above the
+// value of the environment variable `limit_env`, a debug switch that refuses as if the device had run out of memory, so
+// the message can be checked at a test size -- releases them all, clears the sticky error and throws.
+template <class... B>
+void alloc_or_refuse(const char *who, const char *limit_env, size_t bytes, const char *what, std::pair<B *, size_t>... bufs)
+{
+    (bufs.first->release(), ...);
+    const char *lim = getenv(limit_env);
+    hipError_t e = hipSuccess;
+    if (lim && bytes > (size_t)strtoull(lim, nullptr, 10))
+        e = hipErrorOutOfMemory;
+    else
+        (void)(... && (bufs.second == 0 || (e = bufs.first->try_alloc(bufs.second)) == hipSuccess));
+    if (e == hipSuccess) return;
+    (void)hipGetLastError();
+    (bufs.first->release(), ...);
+    char b[400];
+    snprintf(b, sizeof b, "%s: cannot allocate %zu bytes for %s: %s", who, bytes, what, hipGetErrorString(e));
+    throw HipError(b);
+}
+
+// The origin slots and lag rows of a time-correlation sampler (md_dyn, md_sq, md_cage, md_chi4), on the host
+struct SlotRows {
+    int nslots = 0, nrows = 0;
+    std::vector<char> filled;      // nslots: the slot holds an origin
+    std::vector<int64_t> nsamples; // nrows: the (slot, row) pairs sampled into the row since setup / reset
+    void init(int ns, int nr)
+    {
+        nslots = ns;
+        nrows = nr;
+        filled.assign(ns, 0);
+        nsamples.assign(nr, 0);
+    }
+    void check_slot(const char *who, int slot) const // an origin store's target
+    {
+        if (slot >= 0 && slot < nslots) return;
+        char b[160];
+        snprintf(b, sizeof b, "%s: slot %d is out of range 0..%d", who, slot, nslots - 1);
+        throw HipError(b);
+    }
+    // The (slot, row) pairs of one sample call: every slot holds an origin, every row exists.
+    void check_batch(const char *who, const int32_t *slots, const int32_t *rows, int count, const char *empty_hint) const
+    {
+        char b[200];
+        if (count < 0) {
+            snprintf(b, sizeof b, "%s: count must be >= 0, got %d", who, count);
+            throw HipError(b);
+        }
+        if (count > 0 && (!slots || !rows)) throw HipError(std::string(who) + ": slots / rows is null");
+        for (int i = 0; i < count; ++i) {
+            check_slot(who, slots[i]);
+            if (rows[i] < 0 || rows[i] >= nrows) {
+                snprintf(b, sizeof b, "%s: row %d is out of range 0..%d", who, (int)rows[i], nrows - 1);
+                throw HipError(b);
+            }
+            if (!filled[slots[i]]) {
+                snprintf(b, sizeof b, "%s: slot %d is empty (%s)", who, (int)slots[i], empty_hint);
+                throw HipError(b);
+            }
+        }
+    }
+    void count_rows(const int32_t *rows, int count)
+    {
+        for (int i = 0; i < count; ++i) ++nsamples[rows[i]];
+    }
+    void clear_counts() { std::fill(nsamples.begin(), nsamples.end(), (int64_t)0); }
+    void read_counts(int64_t *out) const
+    {
+        if (out) std::copy(nsamples.begin(), nsamples.end(), out);
+    }
 };
 
 struct StateBufs {
@@ -295,38 +379,30 @@ struct md_ctx {
         DBuf<char> sort_tmp;
     } rdf;
 
-    // self dynamics (md_dyn_*): origin frames in slots, the current frame, block partials, per-row sums and histograms
+    // self dynamics (md_dyn_*): the slot / row bookkeeping, origin frames in slots, the current frame, block partials,
+    // per-row sums and histograms
     struct Dyn {
         bool on = false;
-        int nslots = 0, nrows = 0, nq = 0, nbins = 0;
+        int nq = 0, nbins = 0;
         double r_max = 0.0;
         std::vector<double> q;
-        std::vector<char> filled;         // nslots: the slot holds an origin
-        std::vector<int64_t> nsamples;    // nrows
-        double *ox = nullptr;             // nslots frames of n x dim wrapped coordinates, in particle-id order
-        int32_t *oi = nullptr;            // nslots frames of n x dim image counts
+        SlotRows sr;
+        DBuf<double> ox;                  // nslots frames of n x dim wrapped coordinates, in particle-id order
+        DBuf<int32_t> oi;                 // nslots frames of n x dim image counts
         DBuf<double> cx, part, sums, e2;  // current frame; block partials of one batch; nrows x (2 + nq); nbins + 1
         DBuf<int32_t> ci;
         DBuf<unsigned long long> hist;    // nrows x nbins
-        void release_slots()
-        {
-            if (ox) (void)hipFree(ox);
-            if (oi) (void)hipFree(oi);
-            ox = nullptr;
-            oi = nullptr;
-        }
-        ~Dyn() { release_slots(); }
     } dyn;
 
-    // density modes (md_sq_*): the wave vectors, the current frame and its fractional coordinates, block partials, rho of
-    // the last sampled frame, the static and the correlation accumulators, rho of the stored origins
+    // density modes (md_sq_*): the slot / row bookkeeping (both may be empty), the wave vectors, the current frame and its
+    // fractional coordinates, block partials, rho of the last sampled frame, the static and the correlation accumulators,
+    // rho of the stored origins
     struct Sq {
         bool on = false;
-        int nvec = 0, nvec_pad = 0, nslots = 0, nrows = 0, nblk = 0;
+        int nvec = 0, nvec_pad = 0, nblk = 0;
         bool sampled = false;             // rho holds a frame
         int64_t nstatic = 0;
-        std::vector<char> filled;         // nslots: the slot holds an origin
-        std::vector<int64_t> nsamples;    // nrows
+        SlotRows sr;
         DBuf<double> nd;                  // nvec_pad x 3 wave vectors as doubles
         DBuf<double> cx, fr, part, rho, s2, corr, org; // frame; f per axis; (vector, comp, block); 2 nvec; nvec; nrows x nvec; nslots x nvec x 2
         DBuf<int32_t> ci;
@@ -376,58 +452,40 @@ struct md_ctx {
         DBuf<long long> sum_fr, series;   // 8; nseries x 8
     } cluster;
 
-    // cage-relative dynamics and bond breaking (md_cage_*): per origin slot the frame, n_i, sigma and -- the table -- the
-    // entry lists (id_j, del_ij), all by particle id; the current frame, the displacements of one batch, block partials;
-    // per-row sums, counts and histograms; the last sample's per-particle arrays; the dropped-hit counter
+    // cage-relative dynamics and bond breaking (md_cage_*): the slot / row bookkeeping; per origin slot the frame, n_i,
+    // sigma and -- the table -- the entry lists (id_j, del_ij), all by particle id; the current frame, the displacements of
+    // one batch, block partials; per-row sums, counts and histograms; the last sample's per-particle arrays; the
+    // dropped-hit counter
     struct Cage {
         bool on = false;
         bool sampled = false;             // l_nnb / l_broken / l_d2 hold a sample
-        int nslots = 0, nrows = 0, nq = 0, max_neigh = 0, scaled = 0;
+        int nq = 0, max_neigh = 0, scaled = 0;
         double r_neigh = 0.0, r_break = 0.0;
         std::vector<double> q;
-        std::vector<char> filled;         // nslots: the slot holds an origin
-        std::vector<int64_t> nsamples;    // nrows
-        int32_t *nid = nullptr;           // the table: nslots x max_neigh x n ids ...
-        double *del = nullptr;            // ... and nslots x max_neigh x dim x n bond components
+        SlotRows sr;
+        DBuf<int32_t> nid;                // the table: nslots x max_neigh x n ids ...
+        DBuf<double> del;                 // ... and nslots x max_neigh x dim x n bond components
         DBuf<double> ox, cx, sig, disp, part, sums, l_d2; // nslots frames; frame; nslots x n; batch x dim x n; ...; nrows x (2 + nq); n
         DBuf<int32_t> oi, ci, nnb, l_nnb, l_broken;       // nslots frames; frame; nslots x n; n; n
         DBuf<unsigned long long> counts, hist, overflow;  // nrows x 3; nrows x 33; 1
-        void release_table()
-        {
-            if (nid) (void)hipFree(nid);
-            if (del) (void)hipFree(del);
-            nid = nullptr;
-            del = nullptr;
-        }
-        ~Cage() { release_table(); }
     } cage;
 
-    // four-point dynamics (md_chi4_*): per origin slot the frame and -- with vectors -- its fractional coordinates; the
-    // current frame; the mask, the block partials, Q and W of the sample in flight / the last one; the rows
+    // four-point dynamics (md_chi4_*): the slot / row bookkeeping; per origin slot the frame and -- with vectors -- its
+    // fractional coordinates; the current frame; the mask, the block partials, Q and W of the sample in flight / the last
+    // one; the rows
     struct Chi4 {
         bool on = false;
         bool sampled = false;             // mask / qlast / wlast hold a sample
-        int nvec = 0, nvec_pad = 0, nslots = 0, nrows = 0, nblk = 0, nwords = 0;
+        int nvec = 0, nvec_pad = 0, nblk = 0, nwords = 0;
         double a = 0.0, a2 = 0.0;
-        std::vector<char> filled;         // nslots: the slot holds an origin
-        std::vector<int64_t> nsamples;    // nrows: the host's count, behind the sum_q2 overflow guard
-        double *ox = nullptr;             // nslots frames of n x dim wrapped coordinates, in particle-id order
-        int32_t *oi = nullptr;            // nslots frames of n x dim image counts
-        double *of = nullptr;             // nslots frames of dim x n fractional coordinates, one array per axis (nvec > 0)
+        SlotRows sr;                      // (sr.nsamples: the host's count, behind the sum_q2 overflow guard)
+        DBuf<double> ox;                  // nslots frames of n x dim wrapped coordinates, in particle-id order
+        DBuf<int32_t> oi;                 // nslots frames of n x dim image counts
+        DBuf<double> of;                  // nslots frames of dim x n fractional coordinates, one array per axis (nvec > 0)
         DBuf<double> nd, cx, part, wlast, s4; // nvec_pad x 3; frame; (vector, comp, block); 2 nvec; nrows x nvec
         DBuf<int32_t> ci;
         DBuf<unsigned long long> mask, qcur; // nwords; 1
         DBuf<long long> qlast, irow;      // 1; nrows x MD_CHI4_NROW
-        void release_slots()
-        {
-            if (ox) (void)hipFree(ox);
-            if (oi) (void)hipFree(oi);
-            if (of) (void)hipFree(of);
-            ox = nullptr;
-            oi = nullptr;
-            of = nullptr;
-        }
-        ~Chi4() { release_slots(); }
     } chi4;
 
     std::string err;
@@ -1630,6 +1688,59 @@ void cluster_zero(md_ctx *c)
     C.nsamples = 0;
 }
 
+// ---- the time-correlation samplers (md_dyn.hpp, md_sq.hpp, md_cage.hpp, md_chi4.hpp) ---------------------------------
+// What setup and reset share: the accumulators and the row counts set to zero, and a wait.
+void dyn_zero(md_ctx *c)
+{
+    md_ctx::Dyn &Y = c->dyn;
+    HIPCHK(hipMemsetAsync(Y.sums.p, 0, sizeof(double) * Y.sr.nrows * (2 + Y.nq), c->stream));
+    HIPCHK(hipMemsetAsync(Y.hist.p, 0, sizeof(unsigned long long) * Y.sr.nrows * std::max(Y.nbins, 1), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    Y.sr.clear_counts();
+}
+
+void sq_zero(md_ctx *c)
+{
+    md_ctx::Sq &S = c->sq;
+    HIPCHK(hipMemsetAsync(S.s2.p, 0, sizeof(double) * S.nvec, c->stream));
+    if (S.sr.nrows) HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * S.sr.nrows * S.nvec, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    S.nstatic = 0;
+    S.sr.clear_counts();
+}
+
+inline int blocks_of(int64_t n, int per) { return (int)((n + per - 1) / per); }
+
+// The DynParams of a sample against the current cell: n, dim, U and nblk; with q, the nq wave numbers and nquant = 2 + nq
+// (0 without: md_chi4's kernels read n and U alone); with nbins > 0, the van Hove bins.
+DynParams dyn_params(const md_ctx *c, const std::vector<double> *q = nullptr, int nbins = 0, double r_max = 0.0)
+{
+    DynParams P{};
+    P.n = (int)c->n;
+    P.dim = c->dim;
+    P.nblk = blocks_of(c->n, MD_DYN_BLOCK * MD_DYN_PPT);
+    for (int k = 0; k < 9; ++k) P.U[k] = c->A[k];
+    if (q) {
+        P.nq = (int)q->size();
+        P.nquant = 2 + P.nq;
+        std::copy(q->begin(), q->end(), P.q);
+    }
+    P.nbins = nbins;
+    P.inv_delta = nbins > 0 ? (float)(nbins / r_max) : 0.0f;
+    return P;
+}
+
+// Entries i0.. of a sample call's (slot, row) pairs, as many as one launch takes
+template <class Batch>
+Batch batch_from(const int32_t *slots, const int32_t *rows, int i0, int count, int max_batch)
+{
+    Batch B{};
+    B.count = std::min(count - i0, max_batch);
+    std::copy(slots + i0, slots + i0 + B.count, B.slot);
+    std::copy(rows + i0, rows + i0 + B.count, B.row);
+    return B;
+}
+
 // ---- cage-relative dynamics (md_cage.hpp): launches ----------------------------------------------------------------
 // The origin walk's own test is the list cutoff (the rows are complete up to it); the bond criterion is the lane's.
 template <int D>
@@ -1643,8 +1754,8 @@ void launch_cage_origin(md_ctx *c, int slot)
     T.scaled = G.scaled;
     T.r_neigh = G.r_neigh;
     T.nnb = G.nnb.p + (size_t)slot * n;
-    T.nid = G.nid + (size_t)slot * mn * n;
-    T.del = G.del + (size_t)slot * mn * D * n;
+    T.nid = G.nid.p + (size_t)slot * mn * n;
+    T.del = G.del.p + (size_t)slot * mn * D * n;
     T.sig = G.sig.p + (size_t)slot * n;
     T.overflow = G.overflow.p;
     launch_rows<D, CageOriginLane<D>>(c, c->rc * c->rc, T, "cage");
@@ -1664,11 +1775,12 @@ void launch_cage_sample(md_ctx *c, const DynParams &P, const DynBatch &B, const 
 void cage_zero(md_ctx *c)
 {
     md_ctx::Cage &G = c->cage;
-    HIPCHK(hipMemsetAsync(G.sums.p, 0, sizeof(double) * G.nrows * (2 + G.nq), c->stream));
-    HIPCHK(hipMemsetAsync(G.counts.p, 0, sizeof(unsigned long long) * G.nrows * MD_CAGE_NCOUNT, c->stream));
-    HIPCHK(hipMemsetAsync(G.hist.p, 0, sizeof(unsigned long long) * G.nrows * MD_CAGE_NHIST, c->stream));
+    const size_t nr = (size_t)G.sr.nrows;
+    HIPCHK(hipMemsetAsync(G.sums.p, 0, sizeof(double) * nr * (2 + G.nq), c->stream));
+    HIPCHK(hipMemsetAsync(G.counts.p, 0, sizeof(unsigned long long) * nr * MD_CAGE_NCOUNT, c->stream));
+    HIPCHK(hipMemsetAsync(G.hist.p, 0, sizeof(unsigned long long) * nr * MD_CAGE_NHIST, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    std::fill(G.nsamples.begin(), G.nsamples.end(), (int64_t)0);
+    G.sr.clear_counts();
 }
 
 // ---- four-point dynamics (md_chi4.hpp): launches ---------------------------------------------------------------------
@@ -1681,11 +1793,11 @@ void launch_chi4_sample(md_ctx *c, const DynParams &P, int slot, int row)
     hipStream_t st = c->stream;
     const size_t frame = (size_t)P.n * D;
     const int oblk = (P.n + MD_CHI4_BLOCK * MD_CHI4_PPT - 1) / (MD_CHI4_BLOCK * MD_CHI4_PPT);
-    k_chi4_overlap<D><<<oblk, MD_CHI4_BLOCK, 0, st>>>(P, X.a2, X.cx.p, X.ci.p, X.ox + (size_t)slot * frame,
-                                                      X.oi + (size_t)slot * frame, X.mask.p, X.qcur.p);
+    k_chi4_overlap<D><<<oblk, MD_CHI4_BLOCK, 0, st>>>(P, X.a2, X.cx.p, X.ci.p, X.ox.p + (size_t)slot * frame,
+                                                      X.oi.p + (size_t)slot * frame, X.mask.p, X.qcur.p);
     if (X.nvec > 0)
         k_chi4_modes<D><<<dim3(X.nblk, X.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(
-            P.n, X.nblk, X.of + (size_t)slot * frame, X.nd.p, X.part.p, X.mask.p, X.nwords);
+            P.n, X.nblk, X.of.p + (size_t)slot * frame, X.nd.p, X.part.p, X.mask.p, X.nwords);
     const int rblk = std::max(1, (X.nvec + MD_SQ_REDUCE_BLOCK / 64 - 1) / (MD_SQ_REDUCE_BLOCK / 64));
     k_chi4_reduce<<<rblk, MD_SQ_REDUCE_BLOCK, 0, st>>>(X.nvec, X.nblk, X.part.p, X.wlast.p,
                                                        X.s4.p + (size_t)row * std::max(X.nvec, 1), X.qcur.p, X.qlast.p,
@@ -1696,10 +1808,10 @@ void launch_chi4_sample(md_ctx *c, const DynParams &P, int slot, int row)
 void chi4_zero(md_ctx *c)
 {
     md_ctx::Chi4 &X = c->chi4;
-    HIPCHK(hipMemsetAsync(X.irow.p, 0, sizeof(long long) * X.nrows * MD_CHI4_NROW, c->stream));
-    HIPCHK(hipMemsetAsync(X.s4.p, 0, sizeof(double) * X.nrows * std::max(X.nvec, 1), c->stream));
+    HIPCHK(hipMemsetAsync(X.irow.p, 0, sizeof(long long) * X.sr.nrows * MD_CHI4_NROW, c->stream));
+    HIPCHK(hipMemsetAsync(X.s4.p, 0, sizeof(double) * X.sr.nrows * std::max(X.nvec, 1), c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    std::fill(X.nsamples.begin(), X.nsamples.end(), (int64_t)0);
+    X.sr.clear_counts();
 }
 
 } // namespace
@@ -2208,7 +2320,9 @@ int md_neighbor_pairs(md_ctx *ctx, int32_t *pairs, int64_t cap, int64_t *count)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Shared by the sampler entry points below (md_rdf_*, md_dyn_*, md_sq_*, md_stress_*), with sampler_of above.
+// Shared by the sampler entry points below, with sampler_of above: the argument checks here; for the four samplers that
+// correlate the current frame with stored origins (md_dyn_*, md_sq_*, md_cage_*, md_chi4_*) also SlotRows and
+// alloc_or_refuse at the top of this file and dyn_zero / sq_zero / cage_zero / chi4_zero, dyn_params and batch_from above.
 static void check_range(const char *who, const char *name, int v, int lo, int hi)
 {
     if (v >= lo && v <= hi) return;
@@ -2233,30 +2347,58 @@ static std::vector<double> squared_edges(double r_max, int nbins)
     return e2;
 }
 
-// The (slot, row) pairs of one md_dyn_sample / md_sq_sample call: every slot holds an origin, every row exists.
-static void check_batch(const char *who, const int32_t *slots, const int32_t *rows, int count, int nslots, int nrows,
-                        const std::vector<char> &filled, const char *empty_hint)
+static void check_nrows(const char *who, int nrows, int lo)
 {
+    if (nrows >= lo) return;
     char b[200];
-    if (count < 0) {
-        snprintf(b, sizeof b, "%s: count must be >= 0, got %d", who, count);
-        throw HipError(b);
+    snprintf(b, sizeof b, "%s: nrows must be >= %d, got %d", who, lo, nrows);
+    throw HipError(b);
+}
+
+// The wave numbers of md_dyn_setup / md_cage_setup
+static void check_q(const char *who, const double *q, int nq)
+{
+    check_range(who, "nq", nq, 0, MD_DYN_MAX_Q);
+    if (nq > 0 && !q) throw HipError(std::string(who) + ": q is null");
+    for (int j = 0; j < nq; ++j)
+        if (!std::isfinite(q[j])) {
+            char b[200];
+            snprintf(b, sizeof b, "%s: q[%d] must be finite", who, j);
+            throw HipError(b);
+        }
+}
+
+// The integer wave vectors of md_sq_setup / md_chi4_setup, nvec x dim: every component in range, none of them n = 0
+// (`zero_hint` says why that one is refused)
+static void check_wave_vectors(const char *who, const int32_t *nvecs, int nvec, int dim, const char *zero_hint)
+{
+    char b[240];
+    for (int v = 0; v < nvec; ++v) {
+        bool zero = true;
+        for (int c = 0; c < dim; ++c) {
+            const int32_t k = nvecs[(size_t)v * dim + c];
+            if (k < -MD_SQ_MAX_N || k > MD_SQ_MAX_N) {
+                snprintf(b, sizeof b, "%s: component %d of vector %d is %d, outside -%d..%d", who, c, v, (int)k, MD_SQ_MAX_N,
+                         MD_SQ_MAX_N);
+                throw HipError(b);
+            }
+            zero = zero && k == 0;
+        }
+        if (zero) {
+            snprintf(b, sizeof b, "%s: vector %d is n = 0 (%s)", who, v, zero_hint);
+            throw HipError(b);
+        }
     }
-    if (count > 0 && (!slots || !rows)) throw HipError(std::string(who) + ": slots / rows is null");
-    for (int i = 0; i < count; ++i) {
-        if (slots[i] < 0 || slots[i] >= nslots) {
-            snprintf(b, sizeof b, "%s: slot %d is out of range 0..%d", who, (int)slots[i], nslots - 1);
-            throw HipError(b);
-        }
-        if (rows[i] < 0 || rows[i] >= nrows) {
-            snprintf(b, sizeof b, "%s: row %d is out of range 0..%d", who, (int)rows[i], nrows - 1);
-            throw HipError(b);
-        }
-        if (!filled[slots[i]]) {
-            snprintf(b, sizeof b, "%s: slot %d is empty (%s)", who, (int)slots[i], empty_hint);
-            throw HipError(b);
-        }
-    }
+}
+
+// ... and the table the mode kernels read: the vectors as doubles, 3 per vector, padded with zero vectors to whole tiles
+static std::vector<double> wave_vector_table(const int32_t *nvecs, int nvec, int dim)
+{
+    const int nvec_pad = (nvec + MD_SQ_TILE - 1) / MD_SQ_TILE * MD_SQ_TILE;
+    std::vector<double> nd((size_t)nvec_pad * 3, 0.0);
+    for (int v = 0; v < nvec; ++v)
+        for (int c = 0; c < dim; ++c) nd[(size_t)v * 3 + c] = (double)nvecs[(size_t)v * dim + c];
+    return nd;
 }
 
 // The gather md_download makes, of the wrapped coordinates and image counts only, into a sampler's own frame buffers.
@@ -2391,11 +2533,9 @@ int md_rdf_read(md_ctx *ctx, int64_t *counts, int64_t *nsamples)
 {
     API_BEGIN
     md_ctx::Rdf &R = sampler_of(ctx, &md_ctx::rdf, "md_rdf_read", "rdf");
-    std::vector<unsigned long long> h(R.nbins);
-    HIPCHK(hipMemcpyAsync(h.data(), R.hist.p, sizeof(unsigned long long) * R.nbins, hipMemcpyDeviceToHost, ctx->stream));
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the device words are read back as int64_t");
+    if (counts) HIPCHK(hipMemcpyAsync(counts, R.hist.p, sizeof(int64_t) * R.nbins, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (counts)
-        for (int k = 0; k < R.nbins; ++k) counts[k] = (int64_t)h[k];
     if (nsamples) *nsamples = R.nsamples;
     API_END
 }
@@ -2420,66 +2560,34 @@ int md_dyn_setup(md_ctx *ctx, int nslots, int nrows, const double *q, int nq, do
     if (ctx->dom.on) throw HipError("md_dyn_setup: not available on a slab-decomposition handle");
     char b[320];
     check_range("md_dyn_setup", "nslots", nslots, 1, MD_DYN_MAX_SLOTS);
-    if (nrows < 1) {
-        snprintf(b, sizeof b, "md_dyn_setup: nrows must be >= 1, got %d", nrows);
-        throw HipError(b);
-    }
-    check_range("md_dyn_setup", "nq", nq, 0, MD_DYN_MAX_Q);
-    if (nq > 0 && !q) throw HipError("md_dyn_setup: q is null");
-    for (int j = 0; j < nq; ++j)
-        if (!std::isfinite(q[j])) {
-            snprintf(b, sizeof b, "md_dyn_setup: q[%d] must be finite", j);
-            throw HipError(b);
-        }
+    check_nrows("md_dyn_setup", nrows, 1);
+    check_q("md_dyn_setup", q, nq);
     check_range("md_dyn_setup", "nbins", nbins, 0, MD_DYN_MAX_BINS);
     if (nbins > 0 && (!(r_max > 0.0) || !std::isfinite(r_max)))
         throw HipError("md_dyn_setup: r_max must be finite and > 0 when nbins > 0");
     md_ctx::Dyn &Y = ctx->dyn;
     Y.on = false;
-    Y.release_slots();
     const int64_t n = ctx->n;
     const size_t frame = (size_t)n * ctx->dim;
-    const size_t bytes = (size_t)nslots * frame * 12;
-    // MDHIP_DYN_ALLOC_LIMIT=bytes: origin slots above this size are refused as if the device had run out of memory (a
-    // debug switch: the message can be checked at a test size)
-    const char *lim = getenv("MDHIP_DYN_ALLOC_LIMIT");
-    hipError_t ea = hipSuccess, eb = hipSuccess;
-    if (lim && bytes > (size_t)strtoull(lim, nullptr, 10))
-        ea = hipErrorOutOfMemory;
-    else {
-        ea = hipMalloc((void **)&Y.ox, (size_t)nslots * frame * sizeof(double));
-        if (ea == hipSuccess) eb = hipMalloc((void **)&Y.oi, (size_t)nslots * frame * sizeof(int32_t));
-    }
-    if (ea != hipSuccess || eb != hipSuccess) {
-        (void)hipGetLastError();
-        Y.release_slots();
-        snprintf(b, sizeof b,
-                 "md_dyn_setup: cannot allocate %zu bytes for %d origin slots (nslots*N*d*12 = %d*%lld*%d*12): %s", bytes,
-                 nslots, nslots, (long long)n, ctx->dim, hipGetErrorString(ea != hipSuccess ? ea : eb));
-        throw HipError(b);
-    }
+    // MDHIP_DYN_ALLOC_LIMIT=bytes refuses origin slots above this size
+    snprintf(b, sizeof b, "%d origin slots (nslots*N*d*12 = %d*%lld*%d*12)", nslots, nslots, (long long)n, ctx->dim);
+    alloc_or_refuse("md_dyn_setup", "MDHIP_DYN_ALLOC_LIMIT", (size_t)nslots * frame * 12, b,
+                    std::make_pair(&Y.ox, (size_t)nslots * frame), std::make_pair(&Y.oi, (size_t)nslots * frame));
     const int nquant = 2 + nq;
-    const int nblk = (int)((n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
     Y.cx.alloc(frame);
     Y.ci.alloc(frame);
-    Y.part.alloc((size_t)MD_DYN_MAX_BATCH * nquant * nblk);
+    Y.part.alloc((size_t)MD_DYN_MAX_BATCH * nquant * blocks_of(n, MD_DYN_BLOCK * MD_DYN_PPT));
     Y.sums.alloc((size_t)nrows * nquant);
     Y.hist.alloc((size_t)nrows * std::max(nbins, 1));
     Y.e2.alloc((size_t)nbins + 1);
     const std::vector<double> e2 = squared_edges(r_max, nbins);
-    hipStream_t st = ctx->stream;
-    HIPCHK(hipMemcpyAsync(Y.e2.p, e2.data(), sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(Y.sums.p, 0, sizeof(double) * nrows * nquant, st));
-    HIPCHK(hipMemsetAsync(Y.hist.p, 0, sizeof(unsigned long long) * nrows * std::max(nbins, 1), st));
-    HIPCHK(hipStreamSynchronize(st)); // (the edge table is a host vector)
-    Y.nslots = nslots;
-    Y.nrows = nrows;
+    HIPCHK(hipMemcpyAsync(Y.e2.p, e2.data(), sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, ctx->stream));
+    Y.sr.init(nslots, nrows);
     Y.nq = nq;
     Y.nbins = nbins;
     Y.r_max = nbins > 0 ? r_max : 0.0;
     Y.q.assign(q, q + nq);
-    Y.filled.assign(nslots, 0);
-    Y.nsamples.assign(nrows, 0);
+    dyn_zero(ctx); // (waits: the edge table is a host vector)
     Y.on = true;
     API_END
 }
@@ -2489,55 +2597,35 @@ int md_dyn_origin(md_ctx *ctx, int slot)
     API_BEGIN
     md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_origin", "dyn");
     require_state(ctx, "md_dyn_origin");
-    if (slot < 0 || slot >= Y.nslots) {
-        char b[160];
-        snprintf(b, sizeof b, "md_dyn_origin: slot %d is out of range 0..%d", slot, Y.nslots - 1);
-        throw HipError(b);
-    }
+    Y.sr.check_slot("md_dyn_origin", slot);
     const size_t frame = (size_t)ctx->n * ctx->dim;
-    export_frame(ctx, Y.ox + (size_t)slot * frame, Y.oi + (size_t)slot * frame);
-    Y.filled[slot] = 1;
+    export_frame(ctx, Y.ox.p + (size_t)slot * frame, Y.oi.p + (size_t)slot * frame);
+    Y.sr.filled[slot] = 1;
     API_END
 }
 
 int md_dyn_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int count)
 {
-#pragma clang fp contract(off)
     API_BEGIN
     md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_sample", "dyn");
     require_state(ctx, "md_dyn_sample");
-    check_batch("md_dyn_sample", slots, rows, count, Y.nslots, Y.nrows, Y.filled,
-                "store an origin with md_dyn_origin first");
+    Y.sr.check_batch("md_dyn_sample", slots, rows, count, "store an origin with md_dyn_origin first");
     if (count == 0) return 0;
     hipStream_t st = ctx->stream;
     export_frame(ctx, Y.cx.p, Y.ci.p);
-    DynParams P{};
-    P.n = (int)ctx->n;
-    P.dim = ctx->dim;
-    P.nq = Y.nq;
-    P.nbins = Y.nbins;
-    P.nblk = (int)((ctx->n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
-    P.nquant = 2 + Y.nq;
-    P.inv_delta = Y.nbins > 0 ? (float)(Y.nbins / Y.r_max) : 0.0f;
-    for (int c = 0; c < 9; ++c) P.U[c] = ctx->A[c];
-    for (int j = 0; j < Y.nq; ++j) P.q[j] = Y.q[j];
+    const DynParams P = dyn_params(ctx, &Y.q, Y.nbins, Y.r_max);
     const size_t lds = sizeof(uint32_t) * Y.nbins;
     for (int i0 = 0; i0 < count; i0 += MD_DYN_MAX_BATCH) {
-        DynBatch B{};
-        B.count = std::min(count - i0, MD_DYN_MAX_BATCH);
-        for (int i = 0; i < B.count; ++i) {
-            B.slot[i] = slots[i0 + i];
-            B.row[i] = rows[i0 + i];
-        }
+        const DynBatch B = batch_from<DynBatch>(slots, rows, i0, count, MD_DYN_MAX_BATCH);
         dim3 grid(P.nblk, B.count);
         if (ctx->dim == 3)
-            k_dyn_sample<3><<<grid, MD_DYN_BLOCK, lds, st>>>(P, B, Y.cx.p, Y.ci.p, Y.ox, Y.oi, Y.e2.p, Y.part.p, Y.hist.p);
+            k_dyn_sample<3><<<grid, MD_DYN_BLOCK, lds, st>>>(P, B, Y.cx.p, Y.ci.p, Y.ox.p, Y.oi.p, Y.e2.p, Y.part.p, Y.hist.p);
         else
-            k_dyn_sample<2><<<grid, MD_DYN_BLOCK, lds, st>>>(P, B, Y.cx.p, Y.ci.p, Y.ox, Y.oi, Y.e2.p, Y.part.p, Y.hist.p);
+            k_dyn_sample<2><<<grid, MD_DYN_BLOCK, lds, st>>>(P, B, Y.cx.p, Y.ci.p, Y.ox.p, Y.oi.p, Y.e2.p, Y.part.p, Y.hist.p);
         HIPCHK(hipGetLastError());
         k_dyn_reduce<<<1, MD_DYN_REDUCE_BLOCK, 0, st>>>(P, B, Y.part.p, Y.sums.p);
         HIPCHK(hipGetLastError());
-        for (int i = 0; i < B.count; ++i) ++Y.nsamples[B.row[i]];
+        Y.sr.count_rows(B.row, B.count);
     }
     API_END
 }
@@ -2546,28 +2634,21 @@ int md_dyn_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *hist)
 {
     API_BEGIN
     md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_read", "dyn");
-    const size_t ns = (size_t)Y.nrows * (2 + Y.nq), nh = (size_t)Y.nrows * Y.nbins;
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the device words are read back as int64_t");
+    const size_t ns = (size_t)Y.sr.nrows * (2 + Y.nq), nh = (size_t)Y.sr.nrows * Y.nbins;
     hipStream_t st = ctx->stream;
-    std::vector<unsigned long long> h(nh);
     if (sums) HIPCHK(hipMemcpyAsync(sums, Y.sums.p, sizeof(double) * ns, hipMemcpyDeviceToHost, st));
-    if (hist && nh) HIPCHK(hipMemcpyAsync(h.data(), Y.hist.p, sizeof(unsigned long long) * nh, hipMemcpyDeviceToHost, st));
+    if (hist && nh) HIPCHK(hipMemcpyAsync(hist, Y.hist.p, sizeof(int64_t) * nh, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (hist)
-        for (size_t k = 0; k < nh; ++k) hist[k] = (int64_t)h[k];
-    if (nsamples)
-        for (int r = 0; r < Y.nrows; ++r) nsamples[r] = Y.nsamples[r];
+    Y.sr.read_counts(nsamples);
     API_END
 }
 
 int md_dyn_reset(md_ctx *ctx)
 {
     API_BEGIN
-    md_ctx::Dyn &Y = sampler_of(ctx, &md_ctx::dyn, "md_dyn_reset", "dyn");
-    hipStream_t st = ctx->stream;
-    HIPCHK(hipMemsetAsync(Y.sums.p, 0, sizeof(double) * Y.nrows * (2 + Y.nq), st));
-    HIPCHK(hipMemsetAsync(Y.hist.p, 0, sizeof(unsigned long long) * Y.nrows * std::max(Y.nbins, 1), st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::fill(Y.nsamples.begin(), Y.nsamples.end(), (int64_t)0);
+    sampler_of(ctx, &md_ctx::dyn, "md_dyn_reset", "dyn");
+    dyn_zero(ctx);
     API_END
 }
 
@@ -2578,40 +2659,19 @@ int md_sq_setup(md_ctx *ctx, const int32_t *nvecs, int nvec, int nslots, int nro
 {
     API_BEGIN
     if (ctx->dom.on) throw HipError("md_sq_setup: not available on a slab-decomposition handle");
-    char b[240];
     check_range("md_sq_setup", "nvec", nvec, 1, MD_SQ_MAX_VEC);
     if (!nvecs) throw HipError("md_sq_setup: n is null");
     check_range("md_sq_setup", "nslots", nslots, 0, MD_SQ_MAX_SLOTS);
-    if (nrows < 0) {
-        snprintf(b, sizeof b, "md_sq_setup: nrows must be >= 0, got %d", nrows);
-        throw HipError(b);
-    }
+    check_nrows("md_sq_setup", nrows, 0);
     const int dim = ctx->dim;
-    for (int v = 0; v < nvec; ++v) {
-        bool zero = true;
-        for (int c = 0; c < dim; ++c) {
-            const int32_t k = nvecs[(size_t)v * dim + c];
-            if (k < -MD_SQ_MAX_N || k > MD_SQ_MAX_N) {
-                snprintf(b, sizeof b, "md_sq_setup: component %d of vector %d is %d, outside -%d..%d", c, v, (int)k,
-                         MD_SQ_MAX_N, MD_SQ_MAX_N);
-                throw HipError(b);
-            }
-            zero = zero && k == 0;
-        }
-        if (zero) {
-            snprintf(b, sizeof b, "md_sq_setup: vector %d is n = 0 (rho(0) = N carries no information)", v);
-            throw HipError(b);
-        }
-    }
+    check_wave_vectors("md_sq_setup", nvecs, nvec, dim, "rho(0) = N carries no information");
     md_ctx::Sq &S = ctx->sq;
     S.on = false;
     const int64_t n = ctx->n;
     const size_t frame = (size_t)n * dim;
-    const int nblk = (int)((n + MD_SQ_BLOCK * MD_SQ_PPT - 1) / (MD_SQ_BLOCK * MD_SQ_PPT));
-    const int nvec_pad = (nvec + MD_SQ_TILE - 1) / MD_SQ_TILE * MD_SQ_TILE;
-    std::vector<double> nd((size_t)nvec_pad * 3, 0.0);
-    for (int v = 0; v < nvec; ++v)
-        for (int c = 0; c < dim; ++c) nd[(size_t)v * 3 + c] = (double)nvecs[(size_t)v * dim + c];
+    const int nblk = blocks_of(n, MD_SQ_BLOCK * MD_SQ_PPT);
+    const std::vector<double> nd = wave_vector_table(nvecs, nvec, dim);
+    const int nvec_pad = (int)(nd.size() / 3);
     S.nd.alloc(nd.size());
     S.cx.alloc(frame);
     S.ci.alloc(frame);
@@ -2624,19 +2684,13 @@ int md_sq_setup(md_ctx *ctx, const int32_t *nvecs, int nvec, int nslots, int nro
     hipStream_t st = ctx->stream;
     HIPCHK(hipMemcpyAsync(S.nd.p, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(S.rho.p, 0, sizeof(double) * nvec * 2, st));
-    HIPCHK(hipMemsetAsync(S.s2.p, 0, sizeof(double) * nvec, st));
-    if (nrows) HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * nrows * nvec, st));
     if (nslots) HIPCHK(hipMemsetAsync(S.org.p, 0, sizeof(double) * nslots * nvec * 2, st));
-    HIPCHK(hipStreamSynchronize(st)); // (the vector table is a host vector)
     S.nvec = nvec;
     S.nvec_pad = nvec_pad;
-    S.nslots = nslots;
-    S.nrows = nrows;
+    S.sr.init(nslots, nrows);
     S.nblk = nblk;
     S.sampled = false;
-    S.nstatic = 0;
-    S.filled.assign(nslots, 0);
-    S.nsamples.assign(nrows, 0);
+    sq_zero(ctx); // (waits: the vector table is a host vector)
     S.on = true;
     API_END
 }
@@ -2646,11 +2700,10 @@ int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_
     API_BEGIN
     md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_sample", "sq");
     require_state(ctx, "md_sq_sample");
-    check_batch("md_sq_sample", slots, rows, count, S.nslots, S.nrows, S.filled,
-                "store an origin with origin_slot first");
-    if (origin_slot < -1 || origin_slot >= S.nslots) {
+    S.sr.check_batch("md_sq_sample", slots, rows, count, "store an origin with origin_slot first");
+    if (origin_slot < -1 || origin_slot >= S.sr.nslots) {
         char b[200];
-        snprintf(b, sizeof b, "md_sq_sample: origin slot %d is out of range -1..%d", origin_slot, S.nslots - 1);
+        snprintf(b, sizeof b, "md_sq_sample: origin slot %d is out of range -1..%d", origin_slot, S.sr.nslots - 1);
         throw HipError(b);
     }
     hipStream_t st = ctx->stream;
@@ -2667,12 +2720,7 @@ int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_
     const int rblk = (S.nvec + MD_SQ_REDUCE_BLOCK / 64 - 1) / (MD_SQ_REDUCE_BLOCK / 64);
     int i0 = 0;
     do {
-        SqBatch B{};
-        B.count = std::min(count - i0, MD_SQ_MAX_BATCH);
-        for (int i = 0; i < B.count; ++i) {
-            B.slot[i] = slots[i0 + i];
-            B.row[i] = rows[i0 + i];
-        }
+        const SqBatch B = batch_from<SqBatch>(slots, rows, i0, count, MD_SQ_MAX_BATCH);
         const bool last = i0 + B.count >= count;
         k_sq_reduce<<<rblk, MD_SQ_REDUCE_BLOCK, 0, st>>>(S.nvec, S.nblk, i0 == 0, add_static != 0, B, last ? origin_slot : -1,
                                                         S.part.p, S.rho.p, S.s2.p, S.corr.p, S.org.p);
@@ -2681,8 +2729,8 @@ int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_
     } while (i0 < count);
     S.sampled = true;
     if (add_static) ++S.nstatic;
-    for (int i = 0; i < count; ++i) ++S.nsamples[rows[i]];
-    if (origin_slot >= 0) S.filled[origin_slot] = 1;
+    S.sr.count_rows(rows, count);
+    if (origin_slot >= 0) S.sr.filled[origin_slot] = 1;
     API_END
 }
 
@@ -2703,25 +2751,19 @@ int md_sq_read(md_ctx *ctx, int64_t *nstatic, double *s2, int64_t *nsamples, dou
     md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_read", "sq");
     hipStream_t st = ctx->stream;
     if (s2) HIPCHK(hipMemcpyAsync(s2, S.s2.p, sizeof(double) * S.nvec, hipMemcpyDeviceToHost, st));
-    if (corr && S.nrows)
-        HIPCHK(hipMemcpyAsync(corr, S.corr.p, sizeof(double) * S.nrows * S.nvec, hipMemcpyDeviceToHost, st));
+    if (corr && S.sr.nrows)
+        HIPCHK(hipMemcpyAsync(corr, S.corr.p, sizeof(double) * S.sr.nrows * S.nvec, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (nstatic) *nstatic = S.nstatic;
-    if (nsamples)
-        for (int r = 0; r < S.nrows; ++r) nsamples[r] = S.nsamples[r];
+    S.sr.read_counts(nsamples);
     API_END
 }
 
 int md_sq_reset(md_ctx *ctx)
 {
     API_BEGIN
-    md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_reset", "sq");
-    hipStream_t st = ctx->stream;
-    HIPCHK(hipMemsetAsync(S.s2.p, 0, sizeof(double) * S.nvec, st));
-    if (S.nrows) HIPCHK(hipMemsetAsync(S.corr.p, 0, sizeof(double) * S.nrows * S.nvec, st));
-    HIPCHK(hipStreamSynchronize(st));
-    S.nstatic = 0;
-    std::fill(S.nsamples.begin(), S.nsamples.end(), (int64_t)0);
+    sampler_of(ctx, &md_ctx::sq, "md_sq_reset", "sq");
+    sq_zero(ctx);
     API_END
 }
 
@@ -3090,10 +3132,7 @@ int md_cage_setup(md_ctx *ctx, int nslots, int nrows, double r_neigh, double r_b
     if (ctx->dom.on) throw HipError("md_cage_setup: not available on a slab-decomposition handle");
     char b[360];
     check_range("md_cage_setup", "nslots", nslots, 1, MD_DYN_MAX_SLOTS);
-    if (nrows < 1) {
-        snprintf(b, sizeof b, "md_cage_setup: nrows must be >= 1, got %d", nrows);
-        throw HipError(b);
-    }
+    check_nrows("md_cage_setup", nrows, 1);
     if (!(r_neigh > 0.0) || !std::isfinite(r_neigh)) throw HipError("md_cage_setup: r_neigh must be finite and > 0");
     if (!std::isfinite(r_break) || !(r_break >= r_neigh)) {
         snprintf(b, sizeof b, "md_cage_setup: r_break must be finite and >= r_neigh = %.17g, got %.17g", r_neigh, r_break);
@@ -3101,43 +3140,21 @@ int md_cage_setup(md_ctx *ctx, int nslots, int nrows, double r_neigh, double r_b
     }
     check_range("md_cage_setup", "scaled", scaled, 0, 1);
     check_range("md_cage_setup", "max_neigh", max_neigh, 1, MD_CAGE_MAX_NEIGH);
-    check_range("md_cage_setup", "nq", nq, 0, MD_DYN_MAX_Q);
-    if (nq > 0 && !q) throw HipError("md_cage_setup: q is null");
-    for (int j = 0; j < nq; ++j)
-        if (!std::isfinite(q[j])) {
-            snprintf(b, sizeof b, "md_cage_setup: q[%d] must be finite", j);
-            throw HipError(b);
-        }
+    check_q("md_cage_setup", q, nq);
     md_ctx::Cage &G = ctx->cage;
     G.on = false;
     G.sampled = false;
-    G.release_table();
     const int64_t n = ctx->n;
     const int d = ctx->dim;
     const size_t entries = (size_t)nslots * (size_t)n * (size_t)max_neigh;
-    const size_t bytes = entries * (4 + 8 * (size_t)d);
-    // MDHIP_CAGE_ALLOC_LIMIT=bytes: a table above this size is refused as if the device had run out of memory (a debug
-    // switch: the message can be checked at a test size)
-    const char *lim = getenv("MDHIP_CAGE_ALLOC_LIMIT");
-    hipError_t ea = hipSuccess, eb = hipSuccess;
-    if (lim && bytes > (size_t)strtoull(lim, nullptr, 10))
-        ea = hipErrorOutOfMemory;
-    else {
-        ea = hipMalloc((void **)&G.nid, entries * sizeof(int32_t));
-        if (ea == hipSuccess) eb = hipMalloc((void **)&G.del, entries * d * sizeof(double));
-    }
-    if (ea != hipSuccess || eb != hipSuccess) {
-        (void)hipGetLastError();
-        G.release_table();
-        snprintf(b, sizeof b,
-                 "md_cage_setup: cannot allocate %zu bytes for the neighbour table (nslots*N*max_neigh*(4+8*d) = "
-                 "%d*%lld*%d*(4+8*%d)): %s",
-                 bytes, nslots, (long long)n, max_neigh, d, hipGetErrorString(ea != hipSuccess ? ea : eb));
-        throw HipError(b);
-    }
+    // MDHIP_CAGE_ALLOC_LIMIT=bytes refuses a table above this size
+    snprintf(b, sizeof b, "the neighbour table (nslots*N*max_neigh*(4+8*d) = %d*%lld*%d*(4+8*%d))", nslots, (long long)n,
+             max_neigh, d);
+    alloc_or_refuse("md_cage_setup", "MDHIP_CAGE_ALLOC_LIMIT", entries * (4 + 8 * (size_t)d), b,
+                    std::make_pair(&G.nid, entries), std::make_pair(&G.del, entries * d));
     const size_t frame = (size_t)n * d;
     const int nquant = 2 + nq;
-    const int nblk = (int)((n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
+    const int nblk = blocks_of(n, MD_DYN_BLOCK * MD_DYN_PPT);
     G.ox.alloc((size_t)nslots * frame);
     G.oi.alloc((size_t)nslots * frame);
     G.nnb.alloc((size_t)nslots * n);
@@ -3152,16 +3169,13 @@ int md_cage_setup(md_ctx *ctx, int nslots, int nrows, double r_neigh, double r_b
     G.l_nnb.alloc((size_t)n);
     G.l_broken.alloc((size_t)n);
     G.l_d2.alloc((size_t)n);
-    G.nslots = nslots;
-    G.nrows = nrows;
+    G.sr.init(nslots, nrows);
     G.nq = nq;
     G.max_neigh = max_neigh;
     G.scaled = scaled;
     G.r_neigh = r_neigh;
     G.r_break = r_break;
     G.q.assign(q, q + nq);
-    G.filled.assign(nslots, 0);
-    G.nsamples.assign(nrows, 0);
     HIPCHK(hipMemsetAsync(G.overflow.p, 0, sizeof(unsigned long long), ctx->stream));
     cage_zero(ctx);
     G.on = true;
@@ -3173,13 +3187,10 @@ int md_cage_origin(md_ctx *ctx, int slot)
     API_BEGIN
     md_ctx::Cage &G = sampler_of(ctx, &md_ctx::cage, "md_cage_origin", "cage");
     require_state(ctx, "md_cage_origin");
-    char b[320];
-    if (slot < 0 || slot >= G.nslots) {
-        snprintf(b, sizeof b, "md_cage_origin: slot %d is out of range 0..%d", slot, G.nslots - 1);
-        throw HipError(b);
-    }
+    G.sr.check_slot("md_cage_origin", slot);
     const double reach = G.r_neigh * (G.scaled ? ctx->sigma_max : 1.0);
     if (reach > ctx->rc) {
+        char b[320];
         snprintf(b, sizeof b,
                  "md_cage_origin: the neighbour radius %.17g (r_neigh%s) exceeds the list cutoff %.17g (the rows are "
                  "complete only up to it)",
@@ -3194,7 +3205,7 @@ int md_cage_origin(md_ctx *ctx, int slot)
     else
         launch_cage_origin<2>(ctx, slot);
     HIPCHK(hipGetLastError());
-    G.filled[slot] = 1;
+    G.sr.filled[slot] = 1;
     API_END
 }
 
@@ -3203,27 +3214,19 @@ int md_cage_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int c
     API_BEGIN
     md_ctx::Cage &G = sampler_of(ctx, &md_ctx::cage, "md_cage_sample", "cage");
     require_state(ctx, "md_cage_sample");
-    check_batch("md_cage_sample", slots, rows, count, G.nslots, G.nrows, G.filled,
-                "store an origin with md_cage_origin first");
+    G.sr.check_batch("md_cage_sample", slots, rows, count, "store an origin with md_cage_origin first");
     if (count == 0) return 0;
     const size_t n = (size_t)ctx->n;
     G.disp.ensure((size_t)std::min(count, MD_CAGE_MAX_BATCH) * ctx->dim * n);
     export_frame(ctx, G.cx.p, G.ci.p);
-    DynParams P{};
-    P.n = (int)ctx->n;
-    P.dim = ctx->dim;
-    P.nq = G.nq;
-    P.nblk = (int)((ctx->n + MD_DYN_BLOCK * MD_DYN_PPT - 1) / (MD_DYN_BLOCK * MD_DYN_PPT));
-    P.nquant = 2 + G.nq;
-    for (int c = 0; c < 9; ++c) P.U[c] = ctx->A[c];
-    for (int j = 0; j < G.nq; ++j) P.q[j] = G.q[j];
+    const DynParams P = dyn_params(ctx, &G.q);
     CageSample A{};
     A.max_neigh = G.max_neigh;
     A.scaled = G.scaled;
     A.r_break = G.r_break;
     A.nnb = G.nnb.p;
-    A.nid = G.nid;
-    A.del = G.del;
+    A.nid = G.nid.p;
+    A.del = G.del.p;
     A.sig = G.sig.p;
     A.disp = G.disp.p;
     A.part = G.part.p;
@@ -3233,19 +3236,14 @@ int md_cage_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int c
     A.o_broken = G.l_broken.p;
     A.o_d2 = G.l_d2.p;
     for (int i0 = 0; i0 < count; i0 += MD_CAGE_MAX_BATCH) {
-        DynBatch B{};
-        B.count = std::min(count - i0, MD_CAGE_MAX_BATCH);
-        for (int i = 0; i < B.count; ++i) {
-            B.slot[i] = slots[i0 + i];
-            B.row[i] = rows[i0 + i];
-        }
+        const DynBatch B = batch_from<DynBatch>(slots, rows, i0, count, MD_CAGE_MAX_BATCH);
         A.keep = (i0 + B.count == count) ? B.count - 1 : -1; // the call's last entry stays readable (md_cage_particles)
         if (ctx->dim == 3)
             launch_cage_sample<3>(ctx, P, B, A);
         else
             launch_cage_sample<2>(ctx, P, B, A);
         HIPCHK(hipGetLastError());
-        for (int i = 0; i < B.count; ++i) ++G.nsamples[B.row[i]];
+        G.sr.count_rows(B.row, B.count);
     }
     G.sampled = true;
     API_END
@@ -3271,15 +3269,14 @@ int md_cage_read(md_ctx *ctx, int64_t *nsamples, double *sums, int64_t *counts, 
     md_ctx::Cage &G = sampler_of(ctx, &md_ctx::cage, "md_cage_read", "cage");
     static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the device words are read back as int64_t");
     hipStream_t st = ctx->stream;
-    const size_t nr = (size_t)G.nrows;
+    const size_t nr = (size_t)G.sr.nrows;
     if (sums) HIPCHK(hipMemcpyAsync(sums, G.sums.p, sizeof(double) * nr * (2 + G.nq), hipMemcpyDeviceToHost, st));
     if (counts) HIPCHK(hipMemcpyAsync(counts, G.counts.p, sizeof(int64_t) * nr * MD_CAGE_NCOUNT, hipMemcpyDeviceToHost, st));
     if (hist_broken)
         HIPCHK(hipMemcpyAsync(hist_broken, G.hist.p, sizeof(int64_t) * nr * MD_CAGE_NHIST, hipMemcpyDeviceToHost, st));
     if (overflow) HIPCHK(hipMemcpyAsync(overflow, G.overflow.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (nsamples)
-        for (int r = 0; r < G.nrows; ++r) nsamples[r] = G.nsamples[r];
+    G.sr.read_counts(nsamples);
     API_END
 }
 
@@ -3305,60 +3302,22 @@ int md_chi4_setup(md_ctx *ctx, double a, const int32_t *nvecs, int nvec, int nsl
     check_range("md_chi4_setup", "nvec", nvec, 0, MD_CHI4_MAX_VEC);
     if (nvec > 0 && !nvecs) throw HipError("md_chi4_setup: n is null");
     check_range("md_chi4_setup", "nslots", nslots, 1, MD_CHI4_MAX_SLOTS);
-    if (nrows < 1) {
-        snprintf(b, sizeof b, "md_chi4_setup: nrows must be >= 1, got %d", nrows);
-        throw HipError(b);
-    }
+    check_nrows("md_chi4_setup", nrows, 1);
     const int dim = ctx->dim;
-    for (int v = 0; v < nvec; ++v) {
-        bool zero = true;
-        for (int c = 0; c < dim; ++c) {
-            const int32_t k = nvecs[(size_t)v * dim + c];
-            if (k < -MD_SQ_MAX_N || k > MD_SQ_MAX_N) {
-                snprintf(b, sizeof b, "md_chi4_setup: component %d of vector %d is %d, outside -%d..%d", c, v, (int)k,
-                         MD_SQ_MAX_N, MD_SQ_MAX_N);
-                throw HipError(b);
-            }
-            zero = zero && k == 0;
-        }
-        if (zero) {
-            snprintf(b, sizeof b, "md_chi4_setup: vector %d is n = 0 (W(0) = Q carries no information)", v);
-            throw HipError(b);
-        }
-    }
+    check_wave_vectors("md_chi4_setup", nvecs, nvec, dim, "W(0) = Q carries no information");
     md_ctx::Chi4 &X = ctx->chi4;
     X.on = false;
-    X.release_slots();
     const int64_t n = ctx->n;
-    const size_t frame = (size_t)n * dim;
-    const size_t bytes = (size_t)nslots * frame * (nvec > 0 ? 20 : 12);
-    // MDHIP_CHI4_ALLOC_LIMIT=bytes: origin slots above this size are refused as if the device had run out of memory (a
-    // debug switch: the message can be checked at a test size)
-    const char *lim = getenv("MDHIP_CHI4_ALLOC_LIMIT");
-    hipError_t ea = hipSuccess, eb = hipSuccess, ec = hipSuccess;
-    if (lim && bytes > (size_t)strtoull(lim, nullptr, 10))
-        ea = hipErrorOutOfMemory;
-    else {
-        ea = hipMalloc((void **)&X.ox, (size_t)nslots * frame * sizeof(double));
-        if (ea == hipSuccess) eb = hipMalloc((void **)&X.oi, (size_t)nslots * frame * sizeof(int32_t));
-        if (ea == hipSuccess && eb == hipSuccess && nvec > 0)
-            ec = hipMalloc((void **)&X.of, (size_t)nslots * frame * sizeof(double));
-    }
-    if (ea != hipSuccess || eb != hipSuccess || ec != hipSuccess) {
-        (void)hipGetLastError();
-        X.release_slots();
-        snprintf(b, sizeof b,
-                 "md_chi4_setup: cannot allocate %zu bytes for %d origin slots (nslots*N*d*%d = %d*%lld*%d*%d): %s", bytes,
-                 nslots, nvec > 0 ? 20 : 12, nslots, (long long)n, dim, nvec > 0 ? 20 : 12,
-                 hipGetErrorString(ea != hipSuccess ? ea : (eb != hipSuccess ? eb : ec)));
-        throw HipError(b);
-    }
-    const int nblk = (int)((n + MD_SQ_BLOCK * MD_SQ_PPT - 1) / (MD_SQ_BLOCK * MD_SQ_PPT));
-    const int nvec_pad = (nvec + MD_SQ_TILE - 1) / MD_SQ_TILE * MD_SQ_TILE;
+    const size_t frame = (size_t)n * dim, slots_size = (size_t)nslots * frame;
+    const int per = nvec > 0 ? 20 : 12; // bytes per coordinate: x, n and -- with vectors -- the fractional coordinate
+    // MDHIP_CHI4_ALLOC_LIMIT=bytes refuses origin slots above this size
+    snprintf(b, sizeof b, "%d origin slots (nslots*N*d*%d = %d*%lld*%d*%d)", nslots, per, nslots, (long long)n, dim, per);
+    alloc_or_refuse("md_chi4_setup", "MDHIP_CHI4_ALLOC_LIMIT", slots_size * per, b, std::make_pair(&X.ox, slots_size),
+                    std::make_pair(&X.oi, slots_size), std::make_pair(&X.of, nvec > 0 ? slots_size : (size_t)0));
+    const int nblk = blocks_of(n, MD_SQ_BLOCK * MD_SQ_PPT);
     const int nwords = (int)((n + 63) / 64);
-    std::vector<double> nd((size_t)nvec_pad * 3, 0.0);
-    for (int v = 0; v < nvec; ++v)
-        for (int c = 0; c < dim; ++c) nd[(size_t)v * 3 + c] = (double)nvecs[(size_t)v * dim + c];
+    const std::vector<double> nd = wave_vector_table(nvecs, nvec, dim);
+    const int nvec_pad = (int)(nd.size() / 3);
     X.nd.alloc(nd.size());
     X.cx.alloc(frame);
     X.ci.alloc(frame);
@@ -3375,15 +3334,12 @@ int md_chi4_setup(md_ctx *ctx, double a, const int32_t *nvecs, int nvec, int nsl
     HIPCHK(hipMemsetAsync(X.qlast.p, 0, sizeof(long long), st));
     X.nvec = nvec;
     X.nvec_pad = nvec_pad;
-    X.nslots = nslots;
-    X.nrows = nrows;
+    X.sr.init(nslots, nrows);
     X.nblk = nblk;
     X.nwords = nwords;
     X.a = a;
     X.a2 = a * a;
     X.sampled = false;
-    X.filled.assign(nslots, 0);
-    X.nsamples.assign(nrows, 0);
     chi4_zero(ctx); // (waits: the vector table is a host vector)
     X.on = true;
     API_END
@@ -3394,24 +3350,20 @@ int md_chi4_origin(md_ctx *ctx, int slot)
     API_BEGIN
     md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_origin", "chi4");
     require_state(ctx, "md_chi4_origin");
-    if (slot < 0 || slot >= X.nslots) {
-        char b[160];
-        snprintf(b, sizeof b, "md_chi4_origin: slot %d is out of range 0..%d", slot, X.nslots - 1);
-        throw HipError(b);
-    }
+    X.sr.check_slot("md_chi4_origin", slot);
     const int n = (int)ctx->n;
     const size_t frame = (size_t)n * ctx->dim;
-    double *ox = X.ox + (size_t)slot * frame;
-    export_frame(ctx, ox, X.oi + (size_t)slot * frame);
+    double *ox = X.ox.p + (size_t)slot * frame;
+    export_frame(ctx, ox, X.oi.p + (size_t)slot * frame);
     if (X.nvec > 0) {
-        double *of = X.of + (size_t)slot * frame;
+        double *of = X.of.p + (size_t)slot * frame;
         if (ctx->dim == 3)
             k_sq_frac<3><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, ox, of);
         else
             k_sq_frac<2><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, ox, of);
         HIPCHK(hipGetLastError());
     }
-    X.filled[slot] = 1;
+    X.sr.filled[slot] = 1;
     API_END
 }
 
@@ -3420,8 +3372,7 @@ int md_chi4_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int c
     API_BEGIN
     md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_sample", "chi4");
     require_state(ctx, "md_chi4_sample");
-    check_batch("md_chi4_sample", slots, rows, count, X.nslots, X.nrows, X.filled,
-                "store an origin with md_chi4_origin first");
+    X.sr.check_batch("md_chi4_sample", slots, rows, count, "store an origin with md_chi4_origin first");
     if (count == 0) return 0;
     // sum_q2 gains at most N^2 per sample: refuse the call before anything is launched if a row could pass the limit
     // (MDHIP_CHI4_SUMQ2_LIMIT=value lowers it from 2^63 - 1: a debug switch, the refusal can be checked at a test size)
@@ -3429,7 +3380,7 @@ int md_chi4_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int c
         const char *lim = getenv("MDHIP_CHI4_SUMQ2_LIMIT");
         const __int128 limit = lim ? (__int128)strtoull(lim, nullptr, 10) : (__int128)INT64_MAX;
         const __int128 n2 = (__int128)ctx->n * (__int128)ctx->n;
-        std::vector<int64_t> ns(X.nsamples);
+        std::vector<int64_t> ns(X.sr.nsamples);
         for (int i = 0; i < count; ++i) {
             if ((__int128)(ns[rows[i]] + 1) * n2 > limit) {
                 char b[240];
@@ -3443,16 +3394,13 @@ int md_chi4_sample(md_ctx *ctx, const int32_t *slots, const int32_t *rows, int c
         }
     }
     export_frame(ctx, X.cx.p, X.ci.p);
-    DynParams P{};
-    P.n = (int)ctx->n;
-    P.dim = ctx->dim;
-    for (int c = 0; c < 9; ++c) P.U[c] = ctx->A[c];
+    const DynParams P = dyn_params(ctx);
     for (int i = 0; i < count; ++i) {
         if (ctx->dim == 3)
             launch_chi4_sample<3>(ctx, P, slots[i], rows[i]);
         else
             launch_chi4_sample<2>(ctx, P, slots[i], rows[i]);
-        ++X.nsamples[rows[i]];
+        X.sr.count_rows(rows + i, 1);
         X.sampled = true;
     }
     API_END
@@ -3482,11 +3430,11 @@ int md_chi4_read(md_ctx *ctx, int64_t *nsamples, int64_t *sum_q, int64_t *sum_q2
     API_BEGIN
     md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_read", "chi4");
     hipStream_t st = ctx->stream;
-    std::vector<long long> r((size_t)X.nrows * MD_CHI4_NROW);
+    std::vector<long long> r((size_t)X.sr.nrows * MD_CHI4_NROW);
     HIPCHK(hipMemcpyAsync(r.data(), X.irow.p, sizeof(long long) * r.size(), hipMemcpyDeviceToHost, st));
-    if (s4 && X.nvec) HIPCHK(hipMemcpyAsync(s4, X.s4.p, sizeof(double) * X.nrows * X.nvec, hipMemcpyDeviceToHost, st));
+    if (s4 && X.nvec) HIPCHK(hipMemcpyAsync(s4, X.s4.p, sizeof(double) * X.sr.nrows * X.nvec, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    for (int k = 0; k < X.nrows; ++k) {
+    for (int k = 0; k < X.sr.nrows; ++k) {
         if (sum_q) sum_q[k] = r[(size_t)k * MD_CHI4_NROW];
         if (sum_q2) sum_q2[k] = r[(size_t)k * MD_CHI4_NROW + 1];
         if (nsamples) nsamples[k] = r[(size_t)k * MD_CHI4_NROW + 2];

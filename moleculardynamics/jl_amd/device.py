@@ -19,6 +19,15 @@ def _ip(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _pairs(slots, rows):
+    """The (slot, row) pairs of a *_sample call as two flat int32 arrays of one length."""
+    s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+    r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    if s.shape != r.shape:
+        raise ValueError("slots and rows must have the same length")
+    return s, r
+
+
 def _f64(a, shape=None):
     if a is None:
         return None
@@ -205,10 +214,7 @@ class MDDevice:
     def dyn_sample(self, slots, rows):
         """Export the current frame once and add one sample per (slots[i], rows[i]): this frame against the origin in
         slots[i], accumulated into rows[i] (does not wait, changes no state)."""
-        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
-        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
-        if s.shape != r.shape:
-            raise ValueError("slots and rows must have the same length")
+        s, r = _pairs(slots, rows)
         self._chk(self._L.md_dyn_sample(self._h, _ip(s), _ip(r), int(s.size)))
 
     def dyn_read(self):
@@ -238,10 +244,7 @@ class MDDevice:
         """Evaluate rho(q) of the current frame once; then add |rho|^2 to the static accumulator if `static`, one
         correlation per (slots[i], rows[i]) -- this frame against the origin in slots[i], into rows[i] -- and store rho in
         slot `origin` unless it is None, in that order (does not wait, changes no state)."""
-        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
-        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
-        if s.shape != r.shape:
-            raise ValueError("slots and rows must have the same length")
+        s, r = _pairs(slots, rows)
         self._chk(self._L.md_sq_sample(self._h, 1 if static else 0, _ip(s) if s.size else None, _ip(r) if r.size else None,
                                        int(s.size), -1 if origin is None else int(origin)))
 
@@ -399,10 +402,7 @@ class MDDevice:
     def cage_sample(self, slots, rows):
         """Export the current frame once and add one sample per (slots[i], rows[i]): this frame against the origin and the
         neighbours stored in slots[i], accumulated into rows[i] (does not wait, changes no state)."""
-        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
-        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
-        if s.shape != r.shape:
-            raise ValueError("slots and rows must have the same length")
+        s, r = _pairs(slots, rows)
         self._chk(self._L.md_cage_sample(self._h, _ip(s), _ip(r), int(s.size)))
 
     def cage_particles(self):
@@ -450,10 +450,7 @@ class MDDevice:
         """Export the current frame once and add one sample per (slots[i], rows[i]), in order: the overlap of this frame
         with the origin in slots[i] and W on the slow particles, accumulated into rows[i] (does not wait, changes no
         state)."""
-        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
-        r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
-        if s.shape != r.shape:
-            raise ValueError("slots and rows must have the same length")
+        s, r = _pairs(slots, rows)
         self._chk(self._L.md_chi4_sample(self._h, _ip(s), _ip(r), int(s.size)))
 
     def chi4_last(self):

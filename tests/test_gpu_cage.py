@@ -659,3 +659,37 @@ def test_run_simulation_writes_cage_txt_and_nothing_else_changes(tmp_path):
     assert np.all(cage.counts[:, 0] <= cage.nsamples * n) and np.all(cage.counts[:, 0] > 0.99 * cage.nsamples * n)
     for st in (sa, sb):
         st.system.device.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the split of a call's pairs into launches of MD_CAGE_MAX_BATCH = 8
+
+@pytest.mark.parametrize("dim", [3, 2])
+@pytest.mark.parametrize("npairs", [9, 16])
+def test_one_call_with_more_pairs_than_a_batch_equals_one_call_per_pair(dim, npairs):
+    """9 pairs (a ragged second launch) and 16 (two full ones) on three origins and five rows, at N = 257: handle A samples
+    them in one call, handle B in calls of one pair, in order.  k_dyn_reduce adds a batch's entries to their rows in call
+    order and the counts are integers, so every read-back is equal bit for bit -- the per-particle arrays included: `keep`
+    marks the call's last entry alone, in a ragged last launch and in a full one."""
+    from tests.test_gpu_dynamics import _assert_identical, _ragged_frames, _ragged_handle
+    frames, box = _ragged_frames(dim)
+    zi = np.zeros((257, dim), dtype=np.int32)
+    slots, rows = [i % 3 for i in range(npairs)], [(2 * i) % 5 for i in range(npairs)]
+    out = []
+    for one_call in (True, False):
+        with _ragged_handle(dim, box, frames[0]) as dev:
+            dev.cage_setup(3, 5, 1.3, 1.3, False, 32, Q2)
+            for s in range(3):
+                dev.upload(frames[s], None, None, zi)
+                dev.cage_origin(s)
+            dev.upload(frames[3], None, None, zi)
+            if one_call:
+                dev.cage_sample(slots, rows)
+            else:
+                for a, b in zip(slots, rows):
+                    dev.cage_sample([a], [b])
+            out.append(list(dev.cage_read()) + list(dev.cage_particles()))
+    _assert_identical(out[0], out[1])
+    cnt, sums, counts, hist, overflow, nnb, d2cr, broken = out[0]
+    assert list(cnt) == list(np.bincount(rows, minlength=5)) and overflow == 0
+    assert np.all(sums[cnt > 0, 0] > 0.0) and nnb.sum() > 257 and d2cr.max() > 0.0

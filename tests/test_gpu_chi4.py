@@ -618,3 +618,36 @@ def test_refusals(monkeypatch):
             assert b"slab" in lib.md_last_error(h)
     finally:
         lib.md_destroy(h)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# a call of several pairs: one launch triple per pair, in call order
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_one_call_of_several_pairs_equals_one_call_per_pair(dim):
+    """3 pairs on three origins, two of them into one row, at N = 257 with 19 wave vectors: handle A samples them in one
+    call, handle B in three calls, in order.  The sampler does not batch, so this pins the order of a call's pairs: every
+    read-back, and Q, W and the slow particles of the last pair, are equal bit for bit."""
+    from tests.test_gpu_dynamics import _assert_identical, _ragged_frames, _ragged_handle
+    from tests.test_gpu_sq import _ragged_vectors
+    frames, box = _ragged_frames(dim)
+    zi = np.zeros((257, dim), dtype=np.int32)
+    slots, rows = [0, 1, 2], [1, 0, 1]
+    out = []
+    for one_call in (True, False):
+        with _ragged_handle(dim, box, frames[0]) as dev:
+            dev.chi4_setup(0.12, _ragged_vectors(dim), 3, 2)
+            for s in range(3):
+                dev.upload(frames[s], None, None, zi)
+                dev.chi4_origin(s)
+            dev.upload(frames[3], None, None, zi)
+            if one_call:
+                dev.chi4_sample(slots, rows)
+            else:
+                for a, b in zip(slots, rows):
+                    dev.chi4_sample([a], [b])
+            out.append(list(dev.chi4_read()) + list(dev.chi4_last()))
+    _assert_identical(out[0], out[1])
+    cnt, sum_q, sum_q2, s4, q, w, slow = out[0]
+    assert list(cnt) == [1, 2] and q == slow.sum() and 0 < q < 257      # (some particles moved 0.12 in one step, not all)
+    assert np.all(sum_q > 0) and np.all(s4 > 0.0)

@@ -395,3 +395,62 @@ def test_errors(monkeypatch):
         assert lib.md_dyn_reset(h) != 0
     finally:
         lib.md_destroy(h)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the split of a call's pairs into launches of MD_DYN_MAX_BATCH = 32
+
+def _ragged_frames(dim, nframes=4):
+    """(frames, box) of N = 257 -- one full 256-lane block and one lane: a simple lattice of spacing 1.1 with vacancies and
+    a jitter of 0.04, then every further frame the one before it moved by a normal step of 0.08 per particle."""
+    rng = np.random.default_rng(257 + dim)
+    m = 7 if dim == 3 else 17
+    sites = np.stack(np.meshgrid(*([np.arange(m)] * dim), indexing="ij"), -1).reshape(-1, dim).astype(np.float64)
+    frames = [1.1 * (rng.permutation(sites)[:257] + 0.5) + rng.normal(0.0, 0.04, (257, dim))]
+    for _ in range(nframes - 1):
+        frames.append(frames[-1] + rng.normal(0.0, 0.08, (257, dim)))
+    return frames, np.full(dim, 1.1 * m)
+
+
+def _ragged_handle(dim, box, x):
+    from moleculardynamics.jl_amd import MDDevice
+    dev = MDDevice(dim, 257, box, 1.5)
+    dev.set_potential(0, [1.0, 1.0, 1.5])
+    dev.upload(x, np.zeros_like(x), np.zeros_like(x), np.zeros(x.shape, dtype=np.int32), np.ones(257))
+    return dev
+
+
+def _assert_identical(a, b):
+    """Every array of two read-backs: the same dtype, the same shape, the same values (no tolerance)."""
+    assert len(a) == len(b)
+    for u, v in zip(a, b):
+        u, v = np.asarray(u), np.asarray(v)
+        assert u.dtype == v.dtype and u.shape == v.shape and np.array_equal(u, v)
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_one_call_with_more_pairs_than_a_batch_equals_one_call_per_pair(dim):
+    """33 pairs, one more than a launch takes, on three origins and five rows (so rows receive entries of both launches):
+    handle A samples them in one call, handle B in 33 calls of one pair, in order.  k_dyn_reduce adds a batch's entries
+    to their rows in call order and the histogram counts are integers, so every read-back is equal bit for bit."""
+    frames, box = _ragged_frames(dim)
+    zi = np.zeros((257, dim), dtype=np.int32)
+    slots, rows = [i % 3 for i in range(33)], [(2 * i) % 5 for i in range(33)]
+    out = []
+    for one_call in (True, False):
+        with _ragged_handle(dim, box, frames[0]) as dev:
+            dev.dyn_setup(3, 5, Q4, 1.0, 64)
+            for s in range(3):
+                dev.upload(frames[s], None, None, zi)
+                dev.dyn_origin(s)
+            dev.upload(frames[3], None, None, zi)
+            if one_call:
+                dev.dyn_sample(slots, rows)
+            else:
+                for a, b in zip(slots, rows):
+                    dev.dyn_sample([a], [b])
+            out.append(dev.dyn_read())
+    _assert_identical(out[0], out[1])
+    cnt, sums, hist = out[0]
+    assert list(cnt) == list(np.bincount(rows, minlength=5)) and np.all(sums[:, 0] > 0.0)
+    assert np.array_equal(hist.sum(axis=1), 257 * cnt)         # (no displacement reaches r_max = 1)

@@ -500,3 +500,45 @@ def test_errors():
         assert lib.md_sq_reset(h) != 0
     finally:
         lib.md_destroy(h)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the split of a call's pairs into launches of MD_SQ_MAX_BATCH = 64
+
+def _ragged_vectors(dim):
+    """19 integer wave vectors with components in -2..2, none of them zero: two tiles of 8 and a ragged third."""
+    g = np.arange(-2, 3)
+    n = np.stack(np.meshgrid(*([g] * dim), indexing="ij"), -1).reshape(-1, dim)
+    return np.ascontiguousarray(n[np.any(n != 0, axis=1)][::(5 if dim == 3 else 1)][:19], dtype=np.int32)
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_one_call_with_more_pairs_than_a_batch_equals_one_call_per_pair(dim):
+    """65 pairs, one more than a launch takes, on three origins and five rows, at N = 257: handle A samples them in one
+    call together with the static sample and a new origin; handle B in 65 calls of one pair, in order, the static sample
+    with the first and the origin with the last.  k_sq_reduce adds a batch's entries to their rows in call order, so
+    every read-back, rho and the stored origin (read through one more correlation) are equal bit for bit."""
+    from tests.test_gpu_dynamics import _assert_identical, _ragged_frames, _ragged_handle
+    frames, box = _ragged_frames(dim)
+    zi = np.zeros((257, dim), dtype=np.int32)
+    slots, rows = [i % 3 for i in range(65)], [(2 * i) % 5 for i in range(65)]
+    out = []
+    for one_call in (True, False):
+        with _ragged_handle(dim, box, frames[0]) as dev:
+            dev.sq_setup(_ragged_vectors(dim), 4, 6)
+            for s in range(3):
+                dev.upload(frames[s], None, None, zi)
+                dev.sq_sample(False, origin=s)
+            dev.upload(frames[3], None, None, zi)
+            if one_call:
+                dev.sq_sample(True, slots, rows, origin=3)
+            else:
+                for i, (a, b) in enumerate(zip(slots, rows)):
+                    dev.sq_sample(i == 0, [a], [b], origin=3 if i == 64 else None)
+            res = list(dev.sq_read()) + [dev.sq_rho()]
+            dev.sq_sample(False, [3], [5])                      # row 5: this frame against the origin stored last
+            out.append(res + list(dev.sq_read()))
+    _assert_identical(out[0], out[1])
+    nst, s2, cnt, corr, rho = out[0][:5]
+    assert nst == 1 and list(cnt) == list(np.bincount(rows, minlength=6)) and np.all(s2 > 0.0) and np.all(corr[:5] != 0.0)
+    assert np.all(np.abs(rho) > 0.0) and np.all(out[0][8][5] > 0.0)
