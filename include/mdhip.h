@@ -457,6 +457,50 @@ int md_chi4_last(md_ctx *ctx, int64_t *q, double *w, void *slow /* uint8_t[N] */
 int md_chi4_read(md_ctx *ctx, int64_t *nsamples, int64_t *sum_q, int64_t *sum_q2, double *s4);
 int md_chi4_reset(md_ctx *ctx);
 
+/* Current correlations and the velocity autocorrelation, sampled on the device (new relative to the reference, whose
+ * users dump positions and velocities and redo the sums on the host).  A frame is what md_download returns at that
+ * moment: wrapped x and v in particle-id order, written by the same gather into buffers the sampler owns.  On
+ * md_sq_setup's integer wave vectors n (the same limits), the particle current is
+ *   j_a(n) = sum over particles of v_a exp(+i q_n.x),  a = 0..d-1,
+ * with md_sq_sample's phase, operation for operation (f, t = (n_0*f_0 + n_1*f_1) + n_2*f_2, r = t - rint(t), then the
+ * same cos 2*pi*r, sin 2*pi*r); the particle adds fma(v_a, cos, Re j_a) and fma(v_a, sin, Im j_a), all in fp64.  The sum
+ * over particles is md_sq_sample's tree, fixed by N alone, without floating-point atomics: j is a function of the frame
+ * only (the same bits on any handle), and per vector, component a and part
+ *   |j_a - j_a,true| <= V_a * (32*kappa*|n|_1 + 128) * 2^-53,   V_a = sum_i |v_i,a|,  kappa as for md_sq_sample.
+ * Accumulators, fp64, no fma, added in stream order, with the caller's direction e[v*d + a] per vector (finite, not all
+ * zero; the unit vector q_n/|q_n| for the longitudinal / transverse split) and pL = (e_0*j_0 + e_1*j_1) + e_2*j_2 formed
+ * for Re and Im separately (2-D: no third term):
+ *   static                 s_tot[v]  += sum over a, in order, of (Re_a*Re_a + Im_a*Im_a);  s_long[v] += pL_re^2 + pL_im^2
+ *   frame vs slot s, row k c_tot[k][v] += sum over a, in order, of (Re_a*oRe_a + Im_a*oIm_a)
+ *                          c_long[k][v] += pL_re*oL_re + pL_im*oL_im   (oL: the same expression of the stored origin j)
+ * so C_L = c_long/(ns*N) and C_T = (c_tot - c_long)/((d-1)*ns*N).  An origin is the frame's j, 2*d*nvec doubles.
+ *
+ * With vacf != 0 an origin also stores the frame's velocities (N*d doubles per slot), and every (slot, row) pair adds
+ *   Z = sum over particles of (v_0*o_0 + v_1*o_1) + v_2*o_2     (no fma; 2-D: no third term)
+ * to z[row], reduced in a tree fixed by N alone (thread: 4 ids in order; shuffle tree; the 4 waves in order; one reduce
+ * block: thread t sums the blocks t, t + 1024, ..., a shuffle tree per wave and one over the 16 waves), no atomics, the
+ * totals added in call order; |Z - Z_true| <= A*64*2^-53, A = sum_i sum_a |v_i,a(t)*v_i,a(t0)|.  A static sample adds
+ * the same sum of the frame against itself (the equal-time Z) to z[nrows], the row after the lag rows.
+ *
+ * md_cur_setup: nvec vectors n[nvec*d] and directions e[nvec*d] under md_sq_setup's rules (1 <= nvec <= 16384; nvec = 0
+ * is allowed with vacf != 0 and samples Z only), 0 <= nslots <= 64, nrows >= 0, vacf 0 or 1; everything zeroed; calling
+ * it again starts over.  MDHIP_CUR_ALLOC_LIMIT=bytes in the environment refuses a larger velocity-slot allocation as a
+ * failed allocation is refused.  md_cur_sample exports the frame once, evaluates j once, then, in this order: adds the
+ * static sample if add_static != 0, adds the `count` correlations (frame vs slots[i] into rows[i]) in call order, and
+ * stores the origin (j and, with vacf, the velocities) in origin_slot unless that is -1 -- a slot may be read and
+ * overwritten in one call.  It does not wait and changes nothing the handle computes afterwards.  md_cur_last waits and
+ * returns j of the last sampled frame, j[(v*d + a)*2 + {Re, Im}].  md_cur_read waits and returns the number of static
+ * samples, s_tot[nvec], s_long[nvec], nsamples[nrows], c_tot[nrows*nvec], c_long[nrows*nvec] and z[nrows + 1] (any may be
+ * NULL; z != NULL without vacf is refused); md_cur_reset zeroes the accumulators and the counts and keeps the setup and
+ * the stored origins.  Refused: a slab-decomposition handle, a vector, slot or row out of range, an empty origin slot,
+ * any call before md_cur_setup, md_cur_last before the first sample.                                              */
+int md_cur_setup(md_ctx *ctx, const int32_t *n, const double *e, int nvec, int nslots, int nrows, int vacf);
+int md_cur_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_t *rows, int count, int origin_slot);
+int md_cur_last(md_ctx *ctx, double *j);
+int md_cur_read(md_ctx *ctx, int64_t *nstatic, double *s_tot, double *s_long, int64_t *nsamples, double *c_tot,
+                double *c_long, double *z);
+int md_cur_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

@@ -19,7 +19,9 @@ export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, Pseudo
        gofr, write_rdf, SelfDynamics, msd, alpha2, fs, van_hove, write_dynamics, write_van_hove,
        CageDynamics, bond_correlation, broken_distribution, write_cage, cage_particles,
        FourPoint, overlap, chi4, s4, s4_vectors, write_chi4, write_s4, chi4_last,
-       StructureFactor, select_wave_vectors, compute_sq, sofq, fqt, fqt_normalised, write_sq, write_fqt
+       StructureFactor, select_wave_vectors, compute_sq, sofq, fqt, fqt_normalised, write_sq, write_fqt,
+       CurrentCorrelations, current_cl, current_ct, current_cl0, current_ct0, vacf, vacf0, write_currents, write_vacf,
+       cur_last
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -778,6 +780,178 @@ function compute_sq(state::SimulationState, params::Parameters, q_max; dq=nothin
     return sq_collect!(dev, sq, params.dt)
 end
 
+# ---- currents, C_L / C_T(q,t) and the VACF, sampled on the device (md_cur_*; normalisation and file formats as analysis.py's
+# CurrentCorrelations)
+"""
+CurrentCorrelations(q_max; dq, max_per_bin=16, seed=0, lags, origin_every, vacf=true): the longitudinal and transverse
+current correlations C_L(q,t), C_T(q,t) of j_a(q) = sum_i v_i,a exp(+i q.x_i) on select_wave_vectors' vectors (directions
+e = q_n / |q_n|) and, with vacf, Z(t) = <v_i(t0+t).v_i(t0)>, on SelfDynamics' schedule (default: the log-time schedule;
+explicit lags need origin_every, at most 64 slots; samples before the new origin); the equal-time sample is taken at the
+stops that store an origin.  q_max=nothing samples the VACF only.  Not available with Brownian dynamics.
+"""
+mutable struct CurrentCorrelations
+    q_max::Union{Nothing,Float64}
+    dq::Union{Nothing,Float64}
+    max_per_bin::Int
+    seed::Int
+    with_vacf::Bool
+    sched::SelfDynamics                  # the schedule (lags, origin_every, nslots) is SelfDynamics' own
+    lags::Vector{Int}
+    nslots::Int
+    unitcell::Union{Nothing,Matrix{Float64}}
+    n::Matrix{Int32}                     # d x nvec
+    e::Matrix{Float64}                   # d x nvec
+    qvec::Vector{Float64}
+    bin::Vector{Int}                     # per vector: index into q
+    q::Vector{Float64}                   # mean |q| of a bin
+    nvectors::Vector{Int}
+    nstatic::Int64
+    s_tot::Vector{Float64}
+    s_long::Vector{Float64}
+    nsamples::Vector{Int64}
+    c_tot::Matrix{Float64}               # nvec x nlags
+    c_long::Matrix{Float64}              # nvec x nlags
+    z::Vector{Float64}                   # per lag
+    z0::Float64
+    n_particles::Int
+    dimension::Int
+    dt::Float64
+end
+function CurrentCorrelations(q_max; dq=nothing, max_per_bin::Int=16, seed::Int=0, lags=nothing, origin_every=nothing,
+                             vacf::Bool=true)
+    (q_max === nothing || (q_max > 0 && isfinite(q_max))) || error("q_max must be finite and > 0 (or nothing for the VACF only)")
+    (q_max !== nothing || dq === nothing) || error("dq needs q_max")
+    (q_max !== nothing || vacf) || error("q_max=nothing with vacf=false leaves nothing to sample")
+    (dq === nothing || (dq > 0 && isfinite(dq))) || error("dq must be finite and > 0")
+    max_per_bin >= 1 || error("max_per_bin must be >= 1")
+    sched = SelfDynamics(; q=Float64[], lags=lags, origin_every=origin_every)
+    lv = copy(sched.lags)
+    return CurrentCorrelations(q_max === nothing ? nothing : Float64(q_max), dq === nothing ? nothing : Float64(dq),
+                               max_per_bin, seed, vacf, sched, lv, sched.nslots, nothing, zeros(Int32, 0, 0), zeros(0, 0),
+                               Float64[], Int[], Float64[], Int[], 0, Float64[], Float64[], zeros(Int64, length(lv)),
+                               zeros(0, length(lv)), zeros(0, length(lv)), zeros(length(lv)), 0.0, 0, 3, 1.0)
+end
+function reset!(cc::CurrentCorrelations)
+    cc.unitcell = nothing; cc.nstatic = 0; cc.nsamples .= 0; cc.z .= 0.0; cc.z0 = 0.0
+    cc.n = zeros(Int32, 0, 0); cc.e = zeros(0, 0); cc.qvec = Float64[]; cc.s_tot = Float64[]; cc.s_long = Float64[]
+    cc.c_tot = zeros(0, length(cc.lags)); cc.c_long = zeros(0, length(cc.lags))
+    return cc
+end
+cur_schedule(cc::CurrentCorrelations, T::Int) = dyn_schedule(cc.sched, T)
+
+function cur_setup!(dev::Device, cc::CurrentCorrelations, unitcell)
+    U = Matrix{Float64}(unitcell)
+    if cc.q_max !== nothing
+        if cc.unitcell === nothing
+            n, q, b = select_wave_vectors(U, cc.q_max; dq=cc.dq, max_per_bin=cc.max_per_bin, seed=cc.seed)
+            ub = sort(unique(b))
+            qc = 2π .* (inv(U)' * Float64.(n))                                     # the Cartesian q_n, d x nvec
+            cc.unitcell = U; cc.n = n; cc.qvec = q; cc.bin = [searchsortedfirst(ub, x) for x in b]
+            cc.e = qc ./ [norm(qc[:, v]) for v in 1:size(qc, 2)]'
+            cc.nvectors = [count(==(k), cc.bin) for k in eachindex(ub)]
+            cc.q = [sum(q[cc.bin .== k]) / cc.nvectors[k] for k in eachindex(ub)]
+            cc.s_tot = zeros(length(q)); cc.s_long = zeros(length(q))
+            cc.c_tot = zeros(length(q), length(cc.lags)); cc.c_long = zeros(length(q), length(cc.lags))
+        else
+            cc.unitcell == U || error("the unit cell differs from the one the wave vectors were selected for; reset! first")
+        end
+    end
+    nvec = size(cc.n, 2)
+    check(dev, ccall((:md_cur_setup, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Cint, Cint, Cint, Cint),
+                     dev.h, nvec > 0 ? cc.n : C_NULL, nvec > 0 ? cc.e : C_NULL, nvec, cc.nslots, length(cc.lags),
+                     cc.with_vacf ? 1 : 0))
+end
+"j of the current frame once; then the static sample, the correlations (slot, row), the origin store (-1: none)"
+function cur_sample!(dev::Device, static::Bool, slots::Vector{Int32}, rows::Vector{Int32}, origin::Integer)
+    check(dev, ccall((:md_cur_sample, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Int32}, Ptr{Int32}, Cint, Cint),
+                     dev.h, static ? 1 : 0, slots, rows, length(slots), origin))
+end
+"the work at one stop: the static sample exactly where an origin is stored"
+function cur_act!(dev::Device, ev)
+    smp, org = ev
+    cur_sample!(dev, org >= 0, Int32[a for (a, _) in smp], Int32[b for (_, b) in smp], org)
+end
+"j_a(q) of the last sampled frame, nvec x d (j = sum v exp(+i q.x)); waits"
+function cur_last(dev::Device, nvec::Int, d::Int)
+    out = zeros(2, d, max(nvec, 1))
+    check(dev, ccall((:md_cur_last, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), dev.h, out))
+    return [complex(out[1, a, v], out[2, a, v]) for v in 1:nvec, a in 1:d]
+end
+cur_reset!(dev::Device) = check(dev, ccall((:md_cur_reset, LIB), Cint, (Ptr{Cvoid},), dev.h))
+function cur_collect!(dev::Device, cc::CurrentCorrelations, d, dt)
+    nvec = length(cc.qvec); nl = length(cc.lags)
+    nst = Ref{Int64}(0); s_tot = zeros(max(nvec, 1)); s_long = zeros(max(nvec, 1)); ns = zeros(Int64, max(nl, 1))
+    c_tot = zeros(max(nvec, 1), max(nl, 1)); c_long = zeros(max(nvec, 1), max(nl, 1)); z = zeros(nl + 1)
+    check(dev, ccall((:md_cur_read, LIB), Cint,
+                     (Ptr{Cvoid}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     dev.h, nst, s_tot, s_long, ns, c_tot, c_long, cc.with_vacf ? z : C_NULL))
+    cc.nstatic += nst[]; cc.nsamples .+= ns[1:nl]
+    if nvec > 0
+        cc.s_tot .+= s_tot; cc.s_long .+= s_long; cc.c_tot .+= c_tot[:, 1:nl]; cc.c_long .+= c_long[:, 1:nl]
+    end
+    if cc.with_vacf
+        cc.z .+= z[1:nl]; cc.z0 += z[nl + 1]
+    end
+    cc.n_particles = dev.n; cc.dimension = d; cc.dt = dt
+    return cc
+end
+
+_cur_binned(cc::CurrentCorrelations, v) = [sum(v[cc.bin .== k]) / cc.nvectors[k] for k in eachindex(cc.q)]
+function _cur_lags(cc::CurrentCorrelations, per_vector)
+    out = fill(NaN, length(cc.lags), length(cc.q))
+    for k in eachindex(cc.lags)
+        cc.nsamples[k] > 0 && (out[k, :] = _cur_binned(cc, per_vector(k) ./ (cc.nsamples[k] * cc.n_particles)))
+    end
+    return out
+end
+"C_L(q,t): nlags x nbins, the bin mean of c_long / (ns N); NaN where a lag has no sample"
+current_cl(cc::CurrentCorrelations) = _cur_lags(cc, k -> cc.c_long[:, k])
+"C_T(q,t): nlags x nbins, the bin mean of (c_tot - c_long) / ((d-1) ns N)"
+current_ct(cc::CurrentCorrelations) = _cur_lags(cc, k -> (cc.c_tot[:, k] .- cc.c_long[:, k]) ./ (cc.dimension - 1))
+"C_L(q,0) per |q| bin from the static sums"
+current_cl0(cc::CurrentCorrelations) = cc.nstatic == 0 ? fill(NaN, length(cc.q)) :
+    _cur_binned(cc, cc.s_long ./ (cc.nstatic * cc.n_particles))
+"C_T(q,0) per |q| bin from the static sums"
+current_ct0(cc::CurrentCorrelations) = cc.nstatic == 0 ? fill(NaN, length(cc.q)) :
+    _cur_binned(cc, (cc.s_tot .- cc.s_long) ./ ((cc.dimension - 1) * cc.nstatic * cc.n_particles))
+"Z(t) per lag: z / (ns N); NaN where a lag has no sample"
+vacf(cc::CurrentCorrelations) = [cc.nsamples[k] > 0 ? cc.z[k] / (cc.nsamples[k] * cc.n_particles) : NaN for k in eachindex(cc.lags)]
+"Z(0) from the static samples"
+vacf0(cc::CurrentCorrelations) = cc.nstatic > 0 ? cc.z0 / (cc.nstatic * cc.n_particles) : NaN
+
+function write_currents(path, cc::CurrentCorrelations; dt=cc.dt)
+    cl = current_cl(cc); ct = current_ct(cc); cl0 = current_cl0(cc); ct0 = current_ct0(cc)
+    open(path, "w") do io
+        println(io, "# lag time q C_L C_T nsamples")
+        first = true
+        if cc.nstatic > 0
+            first = false
+            for b in eachindex(cc.q)
+                @printf(io, "%d %.6e %.6f %.6e %.6e %d\n", 0, 0.0, cc.q[b], cl0[b], ct0[b], cc.nstatic)
+            end
+        end
+        for (k, l) in enumerate(cc.lags)
+            cc.nsamples[k] > 0 || continue
+            first || println(io)
+            first = false
+            for b in eachindex(cc.q)
+                @printf(io, "%d %.6e %.6f %.6e %.6e %d\n", l, l * dt, cc.q[b], cl[k, b], ct[k, b], cc.nsamples[k])
+            end
+        end
+    end
+end
+
+function write_vacf(path, cc::CurrentCorrelations; dt=cc.dt)
+    z = vacf(cc); z0 = vacf0(cc)
+    open(path, "w") do io
+        println(io, "# lag time Z Z/Z(0) nsamples")
+        cc.nstatic > 0 && @printf(io, "%d %.6e %.6e %.6e %d\n", 0, 0.0, z0, 1.0, cc.nstatic)
+        for (k, l) in enumerate(cc.lags)
+            cc.nsamples[k] > 0 && @printf(io, "%d %.6e %.6e %.6e %d\n", l, l * dt, z[k], z[k] / z0, cc.nsamples[k])
+        end
+    end
+end
+
 # ---- four-point dynamics, sampled on the device (md_chi4_*; normalisation and file formats as analysis.py's FourPoint) --
 """
 FourPoint(a; q_max=nothing, dq=nothing, max_per_bin=16, seed=0, lags=nothing, origin_every=nothing): the self overlap
@@ -1011,6 +1185,8 @@ With sq a StructureFactor, S(q) is sampled the same way (pathname/sq.txt) and, i
 schedule (pathname/fqt.txt).  With cage a CageDynamics, the cage-relative MSD, alpha2, F_s(q,t) and the bond-breaking
 correlation are sampled on SelfDynamics' schedule (pathname/cage.txt).  With four_point a FourPoint, the self overlap,
 chi4(t) and -- if it has wave vectors -- S4(q,t) are sampled on SelfDynamics' schedule (pathname/chi4.txt, pathname/s4.txt).
+With currents a CurrentCorrelations, C_L(q,t), C_T(q,t) and -- with vacf -- Z(t) are sampled on SelfDynamics' schedule
+(pathname/currents.txt, pathname/vacf.txt); not with Brownian dynamics.
 """
 function run_simulation!(state::SimulationState, params::Parameters, ensemble::Ensemble, total_steps::Int,
                          frequency::Int, pathname::String; traj_name::String="trajectory.xyz",
@@ -1018,10 +1194,12 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
                          rdf::Union{Nothing,RadialDistribution}=nothing,
                          dynamics::Union{Nothing,SelfDynamics}=nothing,
                          sq::Union{Nothing,StructureFactor}=nothing,
+                         currents::Union{Nothing,CurrentCorrelations}=nothing,
                          cage::Union{Nothing,CageDynamics}=nothing,
                          four_point::Union{Nothing,FourPoint}=nothing)
     dev = state.system.device; d = state.dimension; n = params.n_particles
     brownian = ensemble isa Brownian
+    (currents === nothing || !brownian) || error("currents is not available with Brownian dynamics (no velocities)")
     configure!(dev, params.potential)
     upload!(dev, state; velocities=!brownian)
     rdf === nothing || rdf_setup!(dev, rdf)
@@ -1033,6 +1211,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
     sq_stops, sq_events = sq === nothing ? (Int[], nothing) : sq_schedule(sq, total_steps)
     sq === nothing || sq_setup!(dev, sq, state.unitcell)
     sq_i = 1
+    # the currents: SelfDynamics' stops; their device calls come after sq's at a shared step
+    cur_stops, cur_events = currents === nothing ? (Int[], nothing) : cur_schedule(currents, total_steps)
+    currents === nothing || cur_setup!(dev, currents, state.unitcell)
+    cur_i = 1
     # cage-relative dynamics: SelfDynamics' stops; its device calls come after every other sampler's at a shared step
     cage_stops, cage_events = cage === nothing ? (Int[], nothing) : cage_schedule(cage, total_steps)
     cage === nothing || cage_setup!(dev, cage)
@@ -1074,6 +1256,8 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         dyn_i <= length(dyn_stops) && (next_out = min(next_out, dyn_stops[dyn_i]))
         while sq_i <= length(sq_stops) && sq_stops[sq_i] < step; sq_i += 1; end
         sq_i <= length(sq_stops) && (next_out = min(next_out, sq_stops[sq_i]))
+        while cur_i <= length(cur_stops) && cur_stops[cur_i] < step; cur_i += 1; end
+        cur_i <= length(cur_stops) && (next_out = min(next_out, cur_stops[cur_i]))
         while cage_i <= length(cage_stops) && cage_stops[cage_i] < step; cage_i += 1; end
         cage_i <= length(cage_stops) && (next_out = min(next_out, cage_stops[cage_i]))
         while fp_i <= length(fp_stops) && fp_stops[fp_i] < step; fp_i += 1; end
@@ -1133,6 +1317,10 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
             end
             (sq_static || sq_ev !== nothing) && sq_act!(dev, sq_static, sq_ev)   # rho once: static, samples, origin
         end
+        if cur_i <= length(cur_stops) && cur_stops[cur_i] == last
+            cur_act!(dev, cur_events[last])          # j once: static (at an origin stop), samples, origin
+            cur_i += 1
+        end
         if cage_i <= length(cage_stops) && cage_stops[cage_i] == last
             cage_act!(dev, cage_events[last])        # the samples, then the new origin and its neighbour table
             cage_i += 1
@@ -1167,6 +1355,11 @@ function run_simulation!(state::SimulationState, params::Parameters, ensemble::E
         sq_collect!(dev, sq, params.dt)
         write_sq(joinpath(pathname, "sq.txt"), sq)
         sq.dynamic && write_fqt(joinpath(pathname, "fqt.txt"), sq)
+    end
+    if currents !== nothing
+        cur_collect!(dev, currents, d, params.dt)
+        isempty(currents.qvec) || write_currents(joinpath(pathname, "currents.txt"), currents)
+        currents.with_vacf && write_vacf(joinpath(pathname, "vacf.txt"), currents)
     end
     if cage !== nothing
         cage_collect!(dev, cage, d, params.dt)

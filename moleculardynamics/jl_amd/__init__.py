@@ -10,7 +10,7 @@ from .initialization import (initialize_state, initialize_velocities, lattice_po
 from .simulation import run_simulation
 from .analysis import (RadialDistribution, compute_rdf, SelfDynamics, StructureFactor, compute_sq, select_wave_vectors,
                        StressTensor, compute_stress, BondOrder, compute_bond_order, ClusterAnalysis,
-                       compute_clusters, CageDynamics, FourPoint)
+                       compute_clusters, CageDynamics, FourPoint, CurrentCorrelations)
 from .minimize import fire_minimize, minimize
 from .device import MDDevice
 from ._lib import MdhipError
@@ -22,5 +22,5 @@ __all__ = [
     "fire_minimize", "minimize", "LennardJonesShifted", "LennardJonesForceShifted", "LennardJonesXPLOR",
     "RadialDistribution", "compute_rdf", "SelfDynamics", "StructureFactor", "compute_sq", "select_wave_vectors",
     "StressTensor", "compute_stress", "BondOrder", "compute_bond_order", "ClusterAnalysis", "compute_clusters", "CageDynamics",
-    "FourPoint",
+    "FourPoint", "CurrentCorrelations",
 ]

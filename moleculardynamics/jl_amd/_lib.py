@@ -33,6 +33,7 @@ EXPORTS = [
     "md_cluster_setup", "md_cluster_sample", "md_cluster_particles", "md_cluster_read", "md_cluster_reset",
     "md_cage_setup", "md_cage_origin", "md_cage_sample", "md_cage_particles", "md_cage_read", "md_cage_reset",
     "md_chi4_setup", "md_chi4_origin", "md_chi4_sample", "md_chi4_last", "md_chi4_read", "md_chi4_reset",
+    "md_cur_setup", "md_cur_sample", "md_cur_last", "md_cur_read", "md_cur_reset",
 ]
 
 
@@ -225,6 +226,16 @@ def load():
     L.md_chi4_read.restype = C.c_int
     L.md_chi4_reset.argtypes = [vp]
     L.md_chi4_reset.restype = C.c_int
+    L.md_cur_setup.argtypes = [vp, ip, dp, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.md_cur_setup.restype = C.c_int
+    L.md_cur_sample.argtypes = [vp, C.c_int, ip, ip, C.c_int, C.c_int]
+    L.md_cur_sample.restype = C.c_int
+    L.md_cur_last.argtypes = [vp, dp]
+    L.md_cur_last.restype = C.c_int
+    L.md_cur_read.argtypes = [vp, i64p, dp, dp, i64p, dp, dp, dp]
+    L.md_cur_read.restype = C.c_int
+    L.md_cur_reset.argtypes = [vp]
+    L.md_cur_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -3,8 +3,8 @@ the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes
 (pressure tensor, stress autocorrelations, Green-Kubo viscosity), the bond-orientational order (Steinhardt q_l, the
 neighbour-averaged qbar_l, psi_k in 2-D, the solid-particle count) and the clusters (connected components of the bond
 graph: sizes, the size distribution, the largest -- solid -- cluster), the cage-relative dynamics (displacements
-relative to the origin neighbours' mean, the bond-breaking correlation C_B) and the four-point functions of the self
-overlap (chi4(t), S4(q, t)).
+relative to the origin neighbours' mean, the bond-breaking correlation C_B), the four-point functions of the self
+overlap (chi4(t), S4(q, t)) and the currents (C_L(q, t), C_T(q, t), the velocity autocorrelation).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -644,6 +644,198 @@ def compute_sq(state, params, q_max, dq=None, max_per_bin=16, seed=0):
     nst, s2, ns, corr = dev.sq_read()
     sq._accumulate(nst, s2, ns, corr, dev.n, params.dt)
     return sq
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Currents: j_a(q) = sum_i v_i,a exp(i q.x_i), its longitudinal part e.j (e = q / |q|) and the rest, the transverse part;
+# C_L(q, t) = <e.j(t0 + t) (e.j)*(t0)> / N, C_T(q, t) = <j_T(t0 + t) . j_T*(t0)> / ((d - 1) N), and the velocity
+# autocorrelation Z(t) = <v_i(t0 + t) . v_i(t0)>, sampled on the device (md_cur_*) on wave vectors commensurate with the cell.
+
+class CurrentCorrelations(_Scheduled, _WaveVectors):
+    """Longitudinal and transverse current correlations C_L(q, t), C_T(q, t) and, with vacf=True, the velocity
+    autocorrelation Z(t), accumulated on the device over the samples of a schedule until reset().
+
+    The wave vectors are select_wave_vectors(unitcell, q_max, dq, max_per_bin, seed) of the cell the sampler is first used
+    on, their directions e = q_n / |q_n| from the same Cartesian q_n that wave_vector_lengths forms; q_max=None samples
+    the VACF only.  The schedule (lags, origin_every) is SelfDynamics': log-time by default, explicit lags need
+    origin_every (at most 64 origin slots), samples before the new origin at a shared step.  The equal-time (static)
+    sample -- C_L(q, 0), C_T(q, 0), Z(0) -- is taken exactly at the stops that store an origin.  An origin costs
+    2 d nvec doubles on the device and, with vacf, the frame's N d velocities.  Unit mass throughout: C_L(q, 0) =
+    C_T(q, 0) = Z(0) / d = kT in equilibrium; -d^2 F(q, t) / dt^2 = q^2 C_L(q, t).
+
+    Fields: n (nvec, d), e (nvec, d), qvec (|q| per vector), bin (per vector: index into q), q (mean |q| of a bin),
+    nvectors (per bin), nstatic, s_tot, s_long (per vector: sum |j|^2, sum |e.j|^2), lags, nsamples (per lag), c_tot,
+    c_long (nlags, nvec), z (per lag: sum Z), z0 (sum of the equal-time Z)."""
+    _prefix = "cur"
+
+    def __init__(self, q_max, dq=None, max_per_bin=16, seed=0, lags=None, origin_every=None, vacf=True):
+        if q_max is not None:
+            q_max = float(q_max)
+            if not (q_max > 0.0 and math.isfinite(q_max)):
+                raise ValueError("q_max must be finite and > 0 (or None for the VACF only)")
+        elif dq is not None:
+            raise ValueError("dq needs q_max")
+        elif not vacf:
+            raise ValueError("q_max=None with vacf=False leaves nothing to sample")
+        if dq is not None and not (float(dq) > 0.0 and math.isfinite(float(dq))):
+            raise ValueError("dq must be finite and > 0")
+        if int(max_per_bin) < 1:
+            raise ValueError("max_per_bin must be >= 1")
+        nl = self._set_schedule(lags, origin_every)
+        self.q_max, self.dq, self.max_per_bin, self.seed = q_max, dq, int(max_per_bin), seed
+        self.with_vacf = bool(vacf)
+        self.nstatic = 0
+        self.z, self.z0 = np.zeros(nl), 0.0
+        self.unitcell = None
+        self.n = self.e = self.qvec = self.bin = self.q = self.nvectors = None
+        self.s_tot = self.s_long = self.c_tot = self.c_long = None
+        self.n_particles = 0
+        self.dimension = 3
+        self.dt = 1.0
+
+    def _zero_vector_sums(self, nvec):
+        u = self.unitcell if self.unitcell.ndim == 2 else np.diag(self.unitcell)
+        qc = 2.0 * math.pi * (np.asarray(self.n, dtype=np.float64) @ np.linalg.inv(u))
+        self.e = np.ascontiguousarray(qc / np.linalg.norm(qc, axis=1)[:, None])
+        self.s_tot, self.s_long = np.zeros(nvec), np.zeros(nvec)
+        self.c_tot, self.c_long = np.zeros((len(self.lags), nvec)), np.zeros((len(self.lags), nvec))
+
+    def reset(self):
+        """Forget the samples and the wave vectors (the next use selects them again, for the cell it meets)."""
+        self.nsamples[:] = 0
+        self.nstatic = 0
+        self.z[:] = 0.0
+        self.z0 = 0.0
+        self.unitcell = None
+        self.n = self.e = self.qvec = self.bin = self.q = self.nvectors = None
+        self.s_tot = self.s_long = self.c_tot = self.c_long = None
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    def _accumulate(self, nstatic, s_tot, s_long, nsamples, c_tot, c_long, z, n_particles, dimension, dt):
+        self.nstatic += int(nstatic)
+        self.nsamples += np.asarray(nsamples, dtype=np.int64)
+        if self.s_tot is not None:
+            self.s_tot += np.asarray(s_tot, dtype=np.float64)
+            self.s_long += np.asarray(s_long, dtype=np.float64)
+            self.c_tot += np.asarray(c_tot, dtype=np.float64)
+            self.c_long += np.asarray(c_long, dtype=np.float64)
+        if self.with_vacf:
+            z = np.asarray(z, dtype=np.float64)
+            self.z += z[:-1]
+            self.z0 += float(z[-1])
+        self.n_particles, self.dimension, self.dt = int(n_particles), int(dimension), float(dt)
+
+    def _need_vectors(self):
+        if self.s_tot is None:
+            raise ValueError("no wave vectors: give q_max (and use the sampler once) for C_L and C_T")
+
+    def _lag_norm(self):
+        ns = self.nsamples.astype(np.float64)[:, None]
+        return ns, ns * self.n_particles
+
+    def cl_vectors(self):
+        """C_L(q_v, t), (nlags, nvec): c_long / (ns N); nan where a lag has no sample."""
+        self._need_vectors()
+        ns, norm = self._lag_norm()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ns > 0, self.c_long / norm, np.nan)
+
+    def ct_vectors(self):
+        """C_T(q_v, t), (nlags, nvec): (c_tot - c_long) / ((d - 1) ns N); nan where a lag has no sample."""
+        self._need_vectors()
+        ns, norm = self._lag_norm()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ns > 0, (self.c_tot - self.c_long) / ((self.dimension - 1) * norm), np.nan)
+
+    def _binned_rows(self, per_vector):
+        return np.array([self._binned(row) for row in per_vector]).reshape(per_vector.shape[0], self.q.size)
+
+    def cl(self):
+        """C_L(q, t), (nlags, nbins): the mean of cl_vectors() over a |q| bin's vectors."""
+        return self._binned_rows(self.cl_vectors())
+
+    def ct(self):
+        """C_T(q, t), (nlags, nbins): the mean of ct_vectors() over a |q| bin's vectors."""
+        return self._binned_rows(self.ct_vectors())
+
+    def cl0(self):
+        """C_L(q, 0) per |q| bin from the static sums: s_long / (nstatic N); nan before the first static sample."""
+        self._need_vectors()
+        if self.nstatic == 0:
+            return np.full(self.q.size, np.nan)
+        return self._binned(self.s_long / (self.nstatic * self.n_particles))
+
+    def ct0(self):
+        """C_T(q, 0) per |q| bin from the static sums: (s_tot - s_long) / ((d - 1) nstatic N)."""
+        self._need_vectors()
+        if self.nstatic == 0:
+            return np.full(self.q.size, np.nan)
+        return self._binned((self.s_tot - self.s_long) / ((self.dimension - 1) * self.nstatic * self.n_particles))
+
+    def _need_vacf(self):
+        if not self.with_vacf:
+            raise ValueError("the VACF was not sampled: construct with vacf=True")
+
+    def vacf(self):
+        """Z(t) = <v_i(t0 + t) . v_i(t0)> per lag: z / (ns N); nan where a lag has no sample."""
+        self._need_vacf()
+        ns = self.nsamples.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ns > 0, self.z / (ns * self.n_particles), np.nan)
+
+    def vacf0(self):
+        """Z(0) = <v_i . v_i> from the static samples: z0 / (nstatic N); nan before the first."""
+        self._need_vacf()
+        return self.z0 / (self.nstatic * self.n_particles) if self.nstatic > 0 else float("nan")
+
+    def write(self, path, dt=None):
+        """One block per lag, lines `lag time q C_L C_T nsamples`, a blank line between blocks: first lag 0 from the
+        static sums (nsamples = nstatic), then every lag that has a sample."""
+        dt = self.dt if dt is None else float(dt)
+        cl, ct, cl0, ct0 = self.cl(), self.ct(), self.cl0(), self.ct0()
+        lags = [0] + [int(l) for l in self.lags]
+        ns = [self.nstatic] + [int(v) for v in self.nsamples]
+
+        def lines(k, l):
+            a, b = (cl0, ct0) if k == 0 else (cl[k - 1], ct[k - 1])
+            return ("%d %.6e %.6f %.6e %.6e %d\n" % (l, l * dt, self.q[i], a[i], b[i], ns[k]) for i in range(self.q.size))
+
+        _write_blocks(path, "# lag time q C_L C_T nsamples\n", lags, ns, lines)
+
+    def write_vacf(self, path, dt=None):
+        """# lag time Z Z/Z(0) nsamples: lag 0 from the static samples, then one row per lag that has a sample."""
+        dt = self.dt if dt is None else float(dt)
+        z, z0 = self.vacf(), self.vacf0()
+        with open(path, "w") as io:
+            io.write("# lag time Z Z/Z(0) nsamples\n")
+            if self.nstatic > 0:
+                io.write("%d %.6e %.6e %.6e %d\n" % (0, 0.0, z0, 1.0, self.nstatic))
+            for k, l in enumerate(self.lags):
+                if self.nsamples[k] > 0:
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        io.write("%d %.6e %.6e %.6e %d\n" % (int(l), l * dt, z[k], z[k] / z0, int(self.nsamples[k])))
+
+    # -- run_simulation's sampler protocol: the stops of schedule(); the static sample where an origin is stored ---------
+    def _begin(self, dev, run):
+        if run.brownian:
+            raise ValueError("currents= is not available with Brownian dynamics (no velocities)")
+        self._stops, self._events = self.schedule(run.total_steps)
+        self._select(run.unitcell)
+        dev.cur_setup(self.n, self.e, self.nslots, len(self.lags), vacf=self.with_vacf)
+
+    def _act(self, dev, step):
+        """The work at one stop: j of the frame once, then the static sample (at an origin stop), the correlations, the
+        origin."""
+        smp, org = self._events[step]
+        dev.cur_sample(org is not None, [a for a, _ in smp], [b for _, b in smp], org)
+
+    def _finish(self, dev, run, pathname):
+        nst, s_tot, s_long, ns, c_tot, c_long, z = dev.cur_read()
+        self._accumulate(nst, s_tot, s_long, ns, c_tot, c_long, z, run.n, run.dim, run.dt)
+        if self.s_tot is not None:
+            self.write(os.path.join(pathname, "currents.txt"))
+        if self.with_vacf:
+            self.write_vacf(os.path.join(pathname, "vacf.txt"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "md_cluster.hpp"
 #include "md_cage.hpp"
 #include "md_chi4.hpp"
+#include "md_cur.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -487,6 +488,24 @@ struct md_ctx {
         DBuf<unsigned long long> mask, qcur; // nwords; 1
         DBuf<long long> qlast, irow;      // 1; nrows x MD_CHI4_NROW
     } chi4;
+
+    // currents and the VACF (md_cur_*): the slot / row bookkeeping (both may be empty); the wave vectors and their unit
+    // directions; the current frame, its f and v per axis; block partials, j of the last sampled frame, the static and
+    // the correlation accumulators, j of the stored origins; with vacf the origins' velocity frames, the pair partials
+    // and z (nrows lag rows, then the equal-time row)
+    struct Cur {
+        bool on = false;
+        bool vacf = false;
+        int nvec = 0, nvec_pad = 0, nblk = 0, zblk = 0;
+        bool sampled = false;             // jl holds a frame
+        int64_t nstatic = 0;
+        SlotRows sr;
+        DBuf<double> nd, e;               // nvec_pad x 3 wave vectors as doubles; nvec x dim unit directions
+        DBuf<double> cx, cv, fr, va;      // frame x, v (n x dim); f and v per axis
+        DBuf<int32_t> ci;
+        DBuf<double> part, jl, s_tot, s_long, c_tot, c_long, org; // (vector, a, part, block); nvec x dim x 2; nvec; nvec; nrows x nvec (2); nslots x nvec x dim x 2
+        DBuf<double> ov, zpart, z;        // nslots frames of n x dim velocities; batch x zblk; nrows + 1
+    } current;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1814,6 +1833,47 @@ void chi4_zero(md_ctx *c)
     X.sr.clear_counts();
 }
 
+// ---- currents (md_cur.hpp): launches ---------------------------------------------------------------------------------
+template <int D>
+void launch_cur_modes(md_ctx *c, hipStream_t st)
+{
+    md_ctx::Cur &S = c->current;
+    const int n = (int)c->n;
+    k_sq_frac<D><<<nblocks(n), MD_BLOCK, 0, st>>>(n, c->grid, S.cx.p, S.fr.p);
+    k_cur_vaxis<D><<<nblocks(n), MD_BLOCK, 0, st>>>(n, S.cv.p, S.va.p);
+    const int ntiles = S.nvec_pad / MD_CUR_TILE;
+    k_cur_modes<D><<<(unsigned)S.nblk * (unsigned)ntiles, MD_CUR_BLOCK, 0, st>>>(n, S.nblk, ntiles, S.fr.p, S.va.p, S.nd.p,
+                                                                              S.part.p);
+    HIPCHK(hipGetLastError());
+}
+
+template <int D>
+void launch_cur_reduce(md_ctx *c, hipStream_t st, bool first, bool add_static, const CurBatch &B, int origin_slot)
+{
+    md_ctx::Cur &S = c->current;
+    const int rblk = (S.nvec + MD_CUR_REDUCE_BLOCK / 64 - 1) / (MD_CUR_REDUCE_BLOCK / 64);
+    k_cur_reduce<D><<<rblk, MD_CUR_REDUCE_BLOCK, 0, st>>>(S.nvec, S.nblk, first, add_static, B, origin_slot, S.part.p,
+                                                        S.e.p, S.jl.p, S.s_tot.p, S.s_long.p, S.c_tot.p, S.c_long.p,
+                                                        S.org.p);
+    HIPCHK(hipGetLastError());
+}
+
+void cur_zero(md_ctx *c)
+{
+    md_ctx::Cur &S = c->current;
+    const size_t nr = (size_t)S.sr.nrows;
+    if (S.nvec) {
+        HIPCHK(hipMemsetAsync(S.s_tot.p, 0, sizeof(double) * S.nvec, c->stream));
+        HIPCHK(hipMemsetAsync(S.s_long.p, 0, sizeof(double) * S.nvec, c->stream));
+        if (nr) HIPCHK(hipMemsetAsync(S.c_tot.p, 0, sizeof(double) * nr * S.nvec, c->stream));
+        if (nr) HIPCHK(hipMemsetAsync(S.c_long.p, 0, sizeof(double) * nr * S.nvec, c->stream));
+    }
+    if (S.vacf) HIPCHK(hipMemsetAsync(S.z.p, 0, sizeof(double) * (nr + 1), c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    S.nstatic = 0;
+    S.sr.clear_counts();
+}
+
 } // namespace
 
 struct FusedScope { // md_run / slab windows: marks the handle's state invalid when the fused loop is left by an exception
@@ -2321,8 +2381,9 @@ int md_neighbor_pairs(md_ctx *ctx, int32_t *pairs, int64_t cap, int64_t *count)
 
 // ---------------------------------------------------------------------------------------------
 // Shared by the sampler entry points below, with sampler_of above: the argument checks here; for the four samplers that
-// correlate the current frame with stored origins (md_dyn_*, md_sq_*, md_cage_*, md_chi4_*) also SlotRows and
-// alloc_or_refuse at the top of this file and dyn_zero / sq_zero / cage_zero / chi4_zero, dyn_params and batch_from above.
+// correlate the current frame with stored origins (md_dyn_*, md_sq_*, md_cage_*, md_chi4_*, md_cur_*) also SlotRows and
+// alloc_or_refuse at the top of this file and dyn_zero / sq_zero / cage_zero / chi4_zero / cur_zero, dyn_params and
+// batch_from above.
 static void check_range(const char *who, const char *name, int v, int lo, int hi)
 {
     if (v >= lo && v <= hi) return;
@@ -2401,14 +2462,15 @@ static std::vector<double> wave_vector_table(const int32_t *nvecs, int nvec, int
     return nd;
 }
 
-// The gather md_download makes, of the wrapped coordinates and image counts only, into a sampler's own frame buffers.
-static void export_frame(md_ctx *ctx, double *x, int32_t *im)
+// The gather md_download makes, of the wrapped coordinates and image counts -- and, with v, the velocities -- into a
+// sampler's own frame buffers.
+static void export_frame(md_ctx *ctx, double *x, int32_t *im, double *v = nullptr)
 {
     DevState s = ctx->dev(ctx->cur);
     if (ctx->dim == 3)
-        k_export<3><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
+        k_export<3><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, v, nullptr, im);
     else
-        k_export<2><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, nullptr, nullptr, im);
+        k_export<2><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->grid, x, v, nullptr, im);
     HIPCHK(hipGetLastError());
 }
 
@@ -3447,6 +3509,187 @@ int md_chi4_reset(md_ctx *ctx)
     API_BEGIN
     sampler_of(ctx, &md_ctx::chi4, "md_chi4_reset", "chi4");
     chi4_zero(ctx);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Currents, C_L / C_T(q, t) and the VACF (md_cur.hpp): a sample launches k_export into the sampler's own frame buffers
+// (x and v) and reads nothing else of the state, so the step loop, the list and the cell order are what they would have
+// been without it.
+int md_cur_setup(md_ctx *ctx, const int32_t *nvecs, const double *e, int nvec, int nslots, int nrows, int vacf)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_cur_setup: not available on a slab-decomposition handle");
+    char b[320];
+    check_range("md_cur_setup", "vacf", vacf, 0, 1);
+    check_range("md_cur_setup", "nvec", nvec, vacf ? 0 : 1, MD_SQ_MAX_VEC);
+    if (nvec > 0 && !nvecs) throw HipError("md_cur_setup: n is null");
+    if (nvec > 0 && !e) throw HipError("md_cur_setup: e is null");
+    check_range("md_cur_setup", "nslots", nslots, 0, MD_SQ_MAX_SLOTS);
+    check_nrows("md_cur_setup", nrows, 0);
+    const int dim = ctx->dim;
+    check_wave_vectors("md_cur_setup", nvecs, nvec, dim, "j(0) = the total momentum, a constant of the motion");
+    for (int v = 0; v < nvec; ++v) {
+        bool finite = true, zero = true;
+        for (int c = 0; c < dim; ++c) {
+            finite = finite && std::isfinite(e[(size_t)v * dim + c]);
+            zero = zero && e[(size_t)v * dim + c] == 0.0;
+        }
+        if (!finite || zero) {
+            snprintf(b, sizeof b, "md_cur_setup: direction %d must be finite and not all zero", v);
+            throw HipError(b);
+        }
+    }
+    md_ctx::Cur &S = ctx->current;
+    S.on = false;
+    const int64_t n = ctx->n;
+    const size_t frame = (size_t)n * dim, slots_size = vacf ? (size_t)nslots * frame : (size_t)0;
+    // MDHIP_CUR_ALLOC_LIMIT=bytes refuses velocity origin slots above this size
+    snprintf(b, sizeof b, "%d velocity origin slots (nslots*N*d*8 = %d*%lld*%d*8)", nslots, nslots, (long long)n, dim);
+    alloc_or_refuse("md_cur_setup", "MDHIP_CUR_ALLOC_LIMIT", slots_size * 8, b, std::make_pair(&S.ov, slots_size));
+    const int nblk = blocks_of(n, MD_CUR_BLOCK * MD_CUR_PPT);
+    const int zblk = blocks_of(n, MD_CUR_VACF_BLOCK * MD_CUR_VACF_PPT);
+    const std::vector<double> nd = wave_vector_table(nvecs, nvec, dim);
+    const int nvec_pad = (int)(nd.size() / 3);
+    const size_t nv = (size_t)nvec;
+    S.nd.alloc(nd.size());
+    S.e.alloc(nv * dim);
+    S.cx.alloc(frame);
+    S.cv.alloc(frame);
+    S.ci.alloc(frame);
+    S.fr.alloc(nvec ? frame : 0);
+    S.va.alloc(nvec ? frame : 0);
+    S.part.alloc((size_t)nvec_pad * 2 * dim * std::max(nblk, 1));
+    S.jl.alloc(nv * 2 * dim);
+    S.s_tot.alloc(nv);
+    S.s_long.alloc(nv);
+    S.c_tot.alloc((size_t)nrows * nv);
+    S.c_long.alloc((size_t)nrows * nv);
+    S.org.alloc((size_t)nslots * nv * 2 * dim);
+    S.zpart.alloc(vacf ? (size_t)MD_CUR_MAX_BATCH * std::max(zblk, 1) : 0);
+    S.z.alloc(vacf ? (size_t)nrows + 1 : 0);
+    hipStream_t st = ctx->stream;
+    if (nvec) {
+        HIPCHK(hipMemcpyAsync(S.nd.p, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(S.e.p, e, sizeof(double) * nv * dim, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(S.jl.p, 0, sizeof(double) * nv * 2 * dim, st));
+        if (nslots) HIPCHK(hipMemsetAsync(S.org.p, 0, sizeof(double) * nslots * nv * 2 * dim, st));
+    }
+    S.vacf = vacf != 0;
+    S.nvec = nvec;
+    S.nvec_pad = nvec_pad;
+    S.sr.init(nslots, nrows);
+    S.nblk = nblk;
+    S.zblk = zblk;
+    S.sampled = false;
+    cur_zero(ctx); // (waits: the tables are host memory)
+    S.on = true;
+    API_END
+}
+
+int md_cur_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_t *rows, int count, int origin_slot)
+{
+    API_BEGIN
+    md_ctx::Cur &S = sampler_of(ctx, &md_ctx::current, "md_cur_sample", "cur");
+    require_state(ctx, "md_cur_sample");
+    S.sr.check_batch("md_cur_sample", slots, rows, count, "store an origin with origin_slot first");
+    if (origin_slot < -1 || origin_slot >= S.sr.nslots) {
+        char b[200];
+        snprintf(b, sizeof b, "md_cur_sample: origin slot %d is out of range -1..%d", origin_slot, S.sr.nslots - 1);
+        throw HipError(b);
+    }
+    hipStream_t st = ctx->stream;
+    const int n = (int)ctx->n, dim = ctx->dim;
+    export_frame(ctx, S.cx.p, S.ci.p, S.cv.p);
+    if (S.nvec > 0) {
+        if (dim == 3)
+            launch_cur_modes<3>(ctx, st);
+        else
+            launch_cur_modes<2>(ctx, st);
+        int i0 = 0;
+        do {
+            const CurBatch B = batch_from<CurBatch>(slots, rows, i0, count, MD_CUR_MAX_BATCH);
+            const bool last = i0 + B.count >= count;
+            if (dim == 3)
+                launch_cur_reduce<3>(ctx, st, i0 == 0, add_static != 0, B, last ? origin_slot : -1);
+            else
+                launch_cur_reduce<2>(ctx, st, i0 == 0, add_static != 0, B, last ? origin_slot : -1);
+            i0 += B.count;
+        } while (i0 < count);
+    }
+    if (S.vacf) {
+        // the equal-time pair (the frame against itself, into the row after the lag rows) first, then the call's pairs
+        std::vector<int32_t> zs, zr;
+        if (add_static) {
+            zs.push_back(-1);
+            zr.push_back(S.sr.nrows);
+        }
+        zs.insert(zs.end(), slots, slots + count);
+        zr.insert(zr.end(), rows, rows + count);
+        const int zcount = (int)zs.size();
+        for (int i0 = 0; i0 < zcount; i0 += MD_CUR_MAX_BATCH) {
+            const CurBatch B = batch_from<CurBatch>(zs.data(), zr.data(), i0, zcount, MD_CUR_MAX_BATCH);
+            const dim3 grid(S.zblk, B.count);
+            if (dim == 3)
+                k_cur_vacf<3><<<grid, MD_CUR_VACF_BLOCK, 0, st>>>(n, S.zblk, B, S.cv.p, S.ov.p, S.zpart.p);
+            else
+                k_cur_vacf<2><<<grid, MD_CUR_VACF_BLOCK, 0, st>>>(n, S.zblk, B, S.cv.p, S.ov.p, S.zpart.p);
+            HIPCHK(hipGetLastError());
+            if (dim == 3)
+                k_cur_vacf_reduce<3><<<1, MD_CUR_VACF_REDUCE_BLOCK, 0, st>>>(S.zblk, B, S.zpart.p, S.z.p);
+            else
+                k_cur_vacf_reduce<2><<<1, MD_CUR_VACF_REDUCE_BLOCK, 0, st>>>(S.zblk, B, S.zpart.p, S.z.p);
+            HIPCHK(hipGetLastError());
+        }
+        if (origin_slot >= 0) {
+            const size_t frame = (size_t)n * dim;
+            HIPCHK(hipMemcpyAsync(S.ov.p + (size_t)origin_slot * frame, S.cv.p, sizeof(double) * frame,
+                                  hipMemcpyDeviceToDevice, st));
+        }
+    }
+    S.sampled = true;
+    if (add_static) ++S.nstatic;
+    S.sr.count_rows(rows, count);
+    if (origin_slot >= 0) S.sr.filled[origin_slot] = 1;
+    API_END
+}
+
+int md_cur_last(md_ctx *ctx, double *j)
+{
+    API_BEGIN
+    md_ctx::Cur &S = sampler_of(ctx, &md_ctx::current, "md_cur_last", "cur");
+    if (!S.sampled) throw HipError("md_cur_last: no frame has been sampled since md_cur_setup");
+    if (!j) throw HipError("md_cur_last: j is null");
+    if (S.nvec)
+        HIPCHK(hipMemcpyAsync(j, S.jl.p, sizeof(double) * S.nvec * 2 * ctx->dim, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    API_END
+}
+
+int md_cur_read(md_ctx *ctx, int64_t *nstatic, double *s_tot, double *s_long, int64_t *nsamples, double *c_tot,
+                double *c_long, double *z)
+{
+    API_BEGIN
+    md_ctx::Cur &S = sampler_of(ctx, &md_ctx::current, "md_cur_read", "cur");
+    if (z && !S.vacf) throw HipError("md_cur_read: z needs a setup with vacf != 0");
+    hipStream_t st = ctx->stream;
+    const size_t nv = (size_t)S.nvec, nc = (size_t)S.sr.nrows * nv;
+    if (s_tot && nv) HIPCHK(hipMemcpyAsync(s_tot, S.s_tot.p, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
+    if (s_long && nv) HIPCHK(hipMemcpyAsync(s_long, S.s_long.p, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
+    if (c_tot && nc) HIPCHK(hipMemcpyAsync(c_tot, S.c_tot.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+    if (c_long && nc) HIPCHK(hipMemcpyAsync(c_long, S.c_long.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+    if (z) HIPCHK(hipMemcpyAsync(z, S.z.p, sizeof(double) * ((size_t)S.sr.nrows + 1), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nstatic) *nstatic = S.nstatic;
+    S.sr.read_counts(nsamples);
+    API_END
+}
+
+int md_cur_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    sampler_of(ctx, &md_ctx::current, "md_cur_reset", "cur");
+    cur_zero(ctx);
     API_END
 }
 

@@ -268,6 +268,58 @@ class MDDevice:
     def sq_reset(self):
         self._chk(self._L.md_sq_reset(self._h))
 
+    # -- currents, C_L / C_T(q, t), the VACF ----------------------------------------------
+    def cur_setup(self, n, e, nslots=0, nrows=0, vacf=False):
+        """Allocate the device current sampler (md_cur_setup): the integer wave vectors n (nvec, d), q_n = 2 pi U^-T n,
+        their unit directions e (nvec, d) for the longitudinal / transverse split, nslots origin slots and nrows
+        correlation rows, all zeroed; vacf=True adds Z = sum v(t).v(t0) per (slot, row) and an origin's velocity frame.
+        n = None (with vacf) samples Z only."""
+        na = np.zeros((0, self.dim), dtype=np.int32) if n is None else np.ascontiguousarray(n, dtype=np.int32)
+        ea = np.zeros((0, self.dim)) if e is None else np.ascontiguousarray(e, dtype=np.float64)
+        if na.ndim != 2 or na.shape[1] != self.dim:
+            raise ValueError(f"n must have shape (nvec, {self.dim})")
+        if ea.shape != na.shape:
+            raise ValueError(f"e must have n's shape {na.shape}")
+        self._chk(self._L.md_cur_setup(self._h, _ip(na) if na.size else None, _dp(ea) if ea.size else None,
+                                       int(na.shape[0]), int(nslots), int(nrows), 1 if vacf else 0))
+        self._cur_shape = (int(na.shape[0]), int(nrows), bool(vacf))
+
+    def cur_sample(self, static=True, slots=(), rows=(), origin=None):
+        """Evaluate j(q) of the current frame once; then add the static sample if `static`, one correlation per
+        (slots[i], rows[i]) -- this frame against the origin in slots[i], into rows[i] -- and store the origin (j and,
+        with vacf, the velocities) in slot `origin` unless it is None, in that order (does not wait, changes no state)."""
+        s, r = _pairs(slots, rows)
+        self._chk(self._L.md_cur_sample(self._h, 1 if static else 0, _ip(s) if s.size else None, _ip(r) if r.size else None,
+                                        int(s.size), -1 if origin is None else int(origin)))
+
+    def cur_last(self):
+        """j(q) of the last sampled frame, complex128[nvec, d] (j_a = sum v_a exp(+i q.x)); waits."""
+        nvec, _, _ = getattr(self, "_cur_shape", (0, 0, False))
+        out = np.zeros((max(nvec, 1), self.dim, 2))
+        self._chk(self._L.md_cur_last(self._h, _dp(out)))
+        return out[:nvec].copy().view(np.complex128).reshape(nvec, self.dim)
+
+    def cur_read(self):
+        """(nstatic, s_tot float64[nvec], s_long float64[nvec], nsamples int64[nrows], c_tot float64[nrows, nvec],
+        c_long float64[nrows, nvec], z), summed since setup / reset; z is float64[nrows + 1] -- the lag rows, then the
+        equal-time sum of the static samples -- with vacf and None without."""
+        nvec, nrows, vacf = getattr(self, "_cur_shape", (0, 0, False))
+        nst = C.c_int64()
+        s_tot, s_long = np.zeros(max(nvec, 1)), np.zeros(max(nvec, 1))
+        ns = np.zeros(max(nrows, 1), dtype=np.int64)
+        c_tot, c_long = np.zeros((max(nrows, 1), max(nvec, 1))), np.zeros((max(nrows, 1), max(nvec, 1)))
+        z = np.zeros(nrows + 1) if vacf else None
+        self._chk(self._L.md_cur_read(self._h, C.byref(nst), _dp(s_tot), _dp(s_long),
+                                      ns.ctypes.data_as(C.POINTER(C.c_int64)), _dp(c_tot), _dp(c_long), _dp(z)))
+        if nvec == 0:
+            c_tot, c_long = np.zeros((nrows, 0)), np.zeros((nrows, 0))
+        else:
+            c_tot, c_long = c_tot.reshape(-1)[:nrows * nvec].reshape(nrows, nvec), c_long.reshape(-1)[:nrows * nvec].reshape(nrows, nvec)
+        return nst.value, s_tot[:nvec], s_long[:nvec], ns[:nrows], c_tot, c_long, z
+
+    def cur_reset(self):
+        self._chk(self._L.md_cur_reset(self._h))
+
     # -- pressure tensor and its lag correlations -----------------------------------------
     def stress_setup(self, nlags=0):
         """Allocate the device pressure-tensor sampler (md_stress_setup): running sums of the kinetic and virial tensors

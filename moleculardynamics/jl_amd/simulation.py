@@ -36,7 +36,7 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, sq=None, stress=None, four_point=None, clusters=None, cage=None, bond_order=None):
+                   dynamics=None, sq=None, currents=None, stress=None, four_point=None, clusters=None, cage=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -53,6 +53,13 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     dynamic=True, the coherent F(q, t) at the steps of its schedule (SelfDynamics' rules: the stops are added to the
     loop's output steps, the schedule restarts at step 0 in every call).  Written to pathname/sq.txt and, if dynamic,
     pathname/fqt.txt.  Nothing else the run produces changes.
+
+    currents: a CurrentCorrelations (analysis.py) to sample the longitudinal and transverse current correlations
+    C_L(q, t), C_T(q, t) and, with vacf=True, the velocity autocorrelation into, on the device, at the steps of its
+    schedule (SelfDynamics' rules: the stops are added to the loop's output steps, the schedule restarts at step 0 in
+    every call, the samples accumulate in the object); the equal-time sample is taken at the stops that store an origin.
+    Written to pathname/currents.txt (with wave vectors) and pathname/vacf.txt (with vacf).  Not available with Brownian
+    dynamics (no velocities).  Nothing else the run produces changes.
 
     stress: a StressTensor (analysis.py) to sample the pressure tensor and, with nlags > 0, its lag correlations into, on
     the device, at every step that is a multiple of stress.every (the stops are added to the loop's output steps; the step
@@ -113,8 +120,10 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
     # the samplers (analysis.py's protocol), in the order their device calls are made at a step they share
     # (clusters after bond_order: with members="solid" it reads the bond-order frame of the same step; then cage;
-    # four_point last)
+    # four_point last; currents right after sq)
     samplers = [s for s in (rdf, dynamics, sq, stress, bond_order) + (clusters, cage, four_point) if s is not None]
+    if currents is not None:
+        samplers.insert(sum(s is not None for s in (rdf, dynamics, sq)), currents)
     run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
                                 unitcell=state.unitcell, brownian=brownian)
     for s in samplers:
