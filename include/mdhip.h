@@ -135,7 +135,8 @@ int md_fire_minimize(md_ctx *ctx, int64_t max_steps, double tol, double dt_initi
  * counter-based stream -- Philox4x32-10, key = seed, counter = (0-based particle index, first_step + s) --
  * so a trajectory depends on neither thread layout nor particle order and a host can reproduce it.
  * out = {U, W of the last step's force evaluation, sum of the virial over the steps with
- * (first_step + s) % virial_every == 0 (the reference samples every 10th step), number of such steps}.     */
+ * (first_step + s) % virial_every == 0 (the reference samples every 10th step), number of such steps}.
+ * nsteps == 0 evaluates nothing: out = {0, 0, 0, 0} and the state is left as it is.                         */
 int md_run_brownian(md_ctx *ctx, int64_t nsteps, double dt, double ktemp, uint64_t seed, int64_t first_step,
                     int64_t virial_every, double *out /* [4] */);
 

@@ -4077,6 +4077,8 @@ int md_fire_minimize(md_ctx *ctx, int64_t max_steps, double tol, double dt_initi
             k_fire_b<3><<<nb, MD_BLOCK, 0, st>>>(n, s, ctx->fire_state.p, 0.5 * ctx->skin, ctx->scal.p, t);
         else
             k_fire_b<2><<<nb, MD_BLOCK, 0, st>>>(n, s, ctx->fire_state.p, 0.5 * ctx->skin, ctx->scal.p, t);
+        // ghost copies (rows without tiles, or 2^26 slots and more) follow their owners, as after md_run's drift
+        launch_ghost_update(ctx, t);
     };
     auto read_fire = [&]() {
         HIPCHK(hipMemcpyAsync(&hf, ctx->fire_state.p, sizeof hf, hipMemcpyDeviceToHost, st));
@@ -4136,6 +4138,11 @@ int md_run_brownian(md_ctx *ctx, int64_t nsteps, double dt, double ktemp, uint64
     if (ctx->dom.on) throw HipError("md_run_brownian: not available on a slab-decomposition handle");
     if (nsteps < 0 || nsteps > 0x3ffffff0) throw HipError("md_run_brownian: bad nsteps");
     if (!(dt > 0.0) || !(ktemp > 0.0)) throw HipError("md_run_brownian: need dt > 0 and kT > 0");
+    if (nsteps == 0) {
+        // no force evaluation ran: nothing to report (the scalars still hold an earlier call's U / W) and no state to touch
+        if (out) out[0] = out[1] = out[2] = out[3] = 0.0;
+        return 0;
+    }
     if (virial_every < 1) virial_every = 10;
     hipStream_t st = ctx->stream;
     ctx->brown_acc.ensure(2);
@@ -4161,6 +4168,7 @@ int md_run_brownian(md_ctx *ctx, int64_t nsteps, double dt, double ktemp, uint64
             else
                 k_brownian_move<2><<<ctx->nblk, MD_BLOCK, 0, st>>>((int)ctx->n, sd, dt, ktemp, sigma, seed, g,
                                                                    0.5 * ctx->skin, ctx->scal.p, (int)t);
+            launch_ghost_update(ctx, (int)t); // (ghost copies follow their owners, as after md_run's drift)
         }
         HIPCHK(hipGetLastError());
         Scalars h = read_scalars(ctx);

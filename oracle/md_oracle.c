@@ -713,7 +713,7 @@ int oracle_run(int dim, int n, double *x, int32_t *img, double *v, double *f, co
  *   if |v| > 0 and |f| > 0: v = (1-alpha) v + alpha (|v|/|f|) f (:95-102) -- mixed BEFORE the sign test, with
  *   the alpha of this step; P > 0: ++steps_since_neg, and past Nmin dt = min(dt*f_inc, dt_max), alpha *= 0.99
  *   (:104-109); else dt = max(dt*f_dec, dt_initial), v = 0, alpha = alpha0, counter = 0 (:110-115);
- *   x += dt*v with the NEW dt, wrap + images (:117-123).
+ *   x += dt*v with the NEW dt, wrap + images (:117-123; per particle through U^-1 under oracle_set_cell).
  * v is internal (starts at zero, :57); ndof = dimension*(N-1) (:61).  Not converged after max_steps: forces
  * are evaluated once more (:126-129) and the reference returns nothing.
  * Returns the number of steps whose force evaluation ran (the converging step included); *converged,
@@ -778,12 +778,14 @@ int oracle_fire_minimize(int dim, int n, double *x, int32_t *img, double *f, con
             alpha = alpha0;
             since_neg = 0;
         }
-        for (int i = 0; i < n; ++i)
+        for (int i = 0; i < n; ++i) {
             for (int c = 0; c < dim; ++c) {
                 size_t k = (size_t)i * dim + c;
                 x[k] += dt * v[k];
-                x[k] = wrap1(x[k], &img[k], L[c], invL[c]);
+                if (!g_tric) x[k] = wrap1(x[k], &img[k], L[c], invL[c]);
             }
+            if (g_tric) wrap_tric(dim, x + (size_t)i * dim, img + (size_t)i * dim);
+        }
     }
     free(v);
     *energy = U;
@@ -821,9 +823,9 @@ void oracle_philox(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t 
 /* The Brownian step loop, src/simulation.jl:181-308 with integrate_brownian! src/integrate.jl:66-82 (broken in
  * the reference, SURVEY.md D9: undefined names, one RNG and one noise buffer shared across threads).  Per step
  * s = 0..nsteps-1: forces at x (:233-240); x_i += f_i*dt/kT + noise_i*sigma, sigma = sqrt(2 dt) (:213),
- * noise = (2u-1)*sqrt(3) per component (src/integrate.jl:55-59), then wrap + images; the virial is sampled on
- * steps with step % virial_every == 0 (:253-256, every 10th).  u: Philox4x32-10, key = seed, counter =
- * (particle index, first_step + s): u_c = (word_c + 1/2) / 2^32.
+ * noise = (2u-1)*sqrt(3) per component (src/integrate.jl:55-59), then wrap + images (per particle through U^-1 under
+ * oracle_set_cell); the virial is sampled on steps with step % virial_every == 0 (:253-256, every 10th).
+ * u: Philox4x32-10, key = seed, counter = (particle index, first_step + s): u_c = (word_c + 1/2) / 2^32.
  * out = {U, W of the last step's force evaluation, virial sum, samples}. */
 int oracle_run_brownian(int dim, int n, double *x, int32_t *img, double *f, const double *diam, const double *L,
                         double cutoff, const oracle_pot *pot, double dt, double ktemp, uint64_t seed,
@@ -852,8 +854,9 @@ int oracle_run_brownian(int dim, int n, double *x, int32_t *img, double *f, cons
                 double u = ((double)w[c] + 0.5) * 2.3283064365386963e-10;
                 double noise = (2.0 * u - 1.0) * 1.7320508075688772;
                 x[k] = x[k] + (f[k] * dt / ktemp) + (noise * sigma); /* src/integrate.jl:75: (f*dt)/kT */
-                x[k] = wrap1(x[k], &img[k], L[c], invL[c]);
+                if (!g_tric) x[k] = wrap1(x[k], &img[k], L[c], invL[c]);
             }
+            if (g_tric) wrap_tric(dim, x + (size_t)i * dim, img + (size_t)i * dim);
         }
     }
     if (out) {

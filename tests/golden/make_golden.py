@@ -63,10 +63,22 @@ def fire_case(n, nsteps):
     return dict(x_end=r["x"], img_end=r["img"], f_end=r["f"], energy=r["energy"], f_rms=r["f_rms"], nsteps=nsteps)
 
 
+def brownian_case(n, nsteps, dt, ktemp, seed):
+    """The Brownian loop (Philox noise keyed by particle id and global step) from the permuted thermal lattice start."""
+    s = lj_system(n, kT=1.0, permute=777)
+    pot = orc.make_pot(orc.POT_LJ, [1.0, 1.0, 2.5])
+    r = orc.run_brownian(s["x"], s["img"], s["diam"], s["box"], 2.5, pot, dt, ktemp, seed, nsteps, use_cells=False,
+                         nthreads=1)
+    return dict(x_end=r["x"], img_end=r["img"], f_end=r["f"], U=r["U"], W=r["W"], virial_sum=r["virial_sum"],
+                virial_count=r["virial_count"], nsteps=nsteps, dt=dt, ktemp=ktemp, seed=np.uint64(seed))
+
+
 if __name__ == "__main__":
     np.savez_compressed(os.path.join(HERE, "lj_n512_rc2p5.npz"), **lj_case(512, 2.5, 10, 0.001))
     np.savez_compressed(os.path.join(HERE, "lj_n500_rc1p5.npz"), **lj_case(500, 1.5, 10, 0.001))
     np.savez_compressed(os.path.join(HERE, "lj_n512_nvt.npz"), **nvt_case(512, 12, 0.001))
     np.savez_compressed(os.path.join(HERE, "poly2d_n1200.npz"), **poly_case(20, 0.005))
     np.savez_compressed(os.path.join(HERE, "fire_lj_n512.npz"), **fire_case(512, 120))
+    np.savez_compressed(os.path.join(HERE, "brownian_lj_n512.npz"),
+                        **brownian_case(512, 60, 2e-4, 1.5, 0xC0FFEE1234ABCDEF))
     print("golden vectors written to", HERE)

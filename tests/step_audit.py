@@ -33,6 +33,9 @@ whole run is a failure.
 Every segment is also classified from the stats() delta: a one-step segment's step followed a list build ("after_rebuild"),
 was a prune step ("prune") or walked the rows it found ("ordinary"); a longer segment's last step is known to be "ordinary"
 only if the whole segment saw neither a prune nor a build ("unknown" otherwise).
+
+The Brownian loop and the FIRE minimiser have modes of their own, audit_brownian and audit_fire (with
+audit_fire_convergence), on the same ledger, knife edges and image exceptions: see the comment block above BD_MIXED.
 """
 import contextlib
 
@@ -151,6 +154,52 @@ def face_distance(x, box, cell=None):
     return (np.minimum(np.abs(fr), np.abs(1.0 - fr)) * perp).min(axis=1)
 
 
+class Ledger:
+    """What every mode of the audit keeps: the worst error of each quantity as a fraction of its bound, the misses, the
+    particles the knife-edge precondition left out and the image exceptions, with their caps."""
+
+    def __init__(self, keys, box, cell, thresholds):
+        self.worst = {k: 0.0 for k in keys}
+        self.failures, self.excluded, self.image_exc = [], set(), set()
+        self.box, self.cell, self.thresholds = box, cell, thresholds
+
+    def miss(self, check, what, msg):
+        self.failures.append(AuditFailure(check, what, msg))
+
+    def note(self, key, err, bound):
+        """Records err / bound; True if the bound is missed."""
+        with np.errstate(over="ignore"):
+            self.worst[key] = max(self.worst[key], float(err) / bound if np.isfinite(err) else np.inf)
+        return not (err <= bound)
+
+    def knife(self, x):
+        """(knife-edge particles at x, mask of the others); the particles join the excluded set."""
+        knife = knife_edge_particles(x, self.box, self.cell, self.thresholds)
+        self.excluded.update(int(i) for i in knife)
+        keep = np.ones(len(x), dtype=bool)
+        keep[knife] = False
+        return knife, keep
+
+    def images(self, where, img, ref_x, ref_img, xb, check="B"):
+        """Image counters must be equal, except for a particle whose oracle coordinate lies within xb of a face."""
+        differ = np.flatnonzero((img != ref_img).any(axis=1))
+        if differ.size:
+            near = face_distance(ref_x, self.box, self.cell)[differ] <= xb
+            self.image_exc.update(int(i) for i in differ[near])
+            if not near.all() or len(self.image_exc) > MAX_IMAGE_EXCEPTIONS:
+                self.miss(check, "img", "%s: image counters differ for particles %s" % (where, differ[:8].tolist()))
+
+    def close_segment(self, where, raise_on_failure):
+        if len(self.excluded) > MAX_EXCLUDED:
+            self.miss("precondition", "knife", "%s: %d particles on a knife edge so far" % (where, len(self.excluded)))
+        if self.failures and raise_on_failure:
+            raise self.failures[0]
+
+    def result(self, segments, stats):
+        return dict(worst=self.worst, segments=segments, excluded=sorted(self.excluded),
+                    image_exceptions=sorted(self.image_exc), failures=self.failures, stats=stats)
+
+
 def audit_run(stepper, oracle, system, pot, cutoff, dt, schedule, ensemble=NVE, tau=0.1, ktemp=None, r1=None, r2=None,
               cell=None, raise_on_failure=True):
     """Runs `schedule` (segment lengths) on `stepper` from `system` and audits every segment as the module docstring says.
@@ -175,16 +224,9 @@ def audit_run(stepper, oracle, system, pot, cutoff, dt, schedule, ensemble=NVE, 
     if nvt:
         ktemp, r1, r2 = (np.ascontiguousarray(a, dtype=np.float64) for a in (ktemp, r1, r2))
         assert min(ktemp.size, r1.size, r2.size) >= total
-    worst = dict(F=0.0, U=0.0, W=0.0, K=0.0, x1=0.0, v1=0.0, x=0.0, v=0.0)
-    segments, failures = [], []
-    excluded, image_exc = set(), set()
-
-    def miss(check, what, msg):
-        failures.append(AuditFailure(check, what, msg))
-
-    def note(key, err, bound):
-        worst[key] = max(worst[key], float(err) / bound if np.isfinite(err) else np.inf)
-        return not (err <= bound)
+    led = Ledger(("F", "U", "W", "K", "x1", "v1", "x", "v"), box, cell, thresholds)
+    segments = []
+    note, miss = led.note, led.miss
 
     with (oracle.set_cell(cell) if cell is not None else contextlib.nullcontext()):
         f0 = oracle.forces_brute(system["x"], box, cutoff, pot, diam)[0]
@@ -207,10 +249,7 @@ def audit_run(stepper, oracle, system, pot, cutoff, dt, schedule, ensemble=NVE, 
 
             # ---- (A) force completeness at the stepper's own positions
             f_ref, u_ref, w_ref, _ = oracle.forces_brute(x, box, cutoff, pot, diam)
-            knife = knife_edge_particles(x, box, cell, thresholds)
-            excluded.update(int(i) for i in knife)
-            keep = np.ones(n, dtype=bool)
-            keep[knife] = False
+            knife, keep = led.knife(x)
             tol_f = ftol * max(1.0, float(np.abs(f_ref).max()))
             err = np.abs(f - f_ref)[keep].max() if keep.any() else 0.0
             if note("F", err, tol_f):
@@ -250,21 +289,12 @@ def audit_run(stepper, oracle, system, pot, cutoff, dt, schedule, ensemble=NVE, 
                     miss("B", "x", "%s: |dx|inf = %.3e > %.3e (particle %d)" % (where, dx.max(), xb, int(dx.max(axis=1).argmax())))
                 if note(vkey, dv.max(), vb):
                     miss("B", "v", "%s: |dv|inf = %.3e > %.3e (particle %d)" % (where, dv.max(), vb, int(dv.max(axis=1).argmax())))
-                differ = np.flatnonzero((img != ref["img"]).any(axis=1))
-                if differ.size:
-                    near = face_distance(ref["x"], box, cell)[differ] <= xb
-                    image_exc.update(int(i) for i in differ[near])
-                    if not near.all() or len(image_exc) > MAX_IMAGE_EXCEPTIONS:
-                        miss("B", "img", "%s: image counters differ for particles %s" % (where, differ[:8].tolist()))
-            if len(excluded) > MAX_EXCLUDED:
-                miss("precondition", "knife", "%s: %d particles on a knife edge so far" % (where, len(excluded)))
-            if failures and raise_on_failure:
-                raise failures[0]
+                led.images(where, img, ref["x"], ref["img"], xb)
+            led.close_segment(where, raise_on_failure)
             start = end
             a += k
         stats = stepper.stats()
-    return dict(worst=worst, segments=segments, excluded=sorted(excluded), image_exceptions=sorted(image_exc),
-                failures=failures, stats=stats)
+    return led.result(segments, stats)
 
 
 def coverage(result):
@@ -320,3 +350,487 @@ class OracleStepper:
                 self.o.bussi(self.v, float(ktemp[t]), nf, dt, tau, float(r1[t]), float(r2[t]))
             self.step += 1
         return (u, w, self.o.kinetic(self.v)) if thermo else None
+
+
+# =================================================================================================================
+# The other two device loops: Brownian dynamics (md_run_brownian) and the FIRE minimiser (md_fire_minimize).
+#
+# Both are audited the same way, with two differences in what a segment leaves behind.
+#
+# Brownian.  A step evaluates the forces at x and then moves, so the forces a run of k steps leaves are those of its LAST
+# evaluation, at the positions BEFORE the last move.  (A) for k == 1 is therefore forces_brute at the segment's start (no
+# trajectory enters), and for k > 1 the shadow's last evaluation, whose positions carry the segment's trajectory error:
+# bound tol_F + 1e-10 |F|inf for k <= 10 (the x bound through a force gradient of order |F|inf per unit length), and the
+# project's long-run bound 1e-8 max(1, |F|inf) beyond.  U and W of that evaluation: the energy tolerance plus the x bound
+# through sum_i |f_i| (dU = -sum f_i dx_i), for W with the factor 64 >= 1 + the steepest exponent of the suite's potentials
+# (r dF/dr = -(m + 1) F for a power law r^-m; pseudo hard spheres m = 50).  The knife-edge precondition is evaluated where
+# that evaluation took place (k > 1: the shadow's positions after k - 1 steps).
+# (B) one step, diagonal cell: |dx| <= 8 spacing(Lmax) + (dt / kT) tol_F -- the eight roundings of the MD bound, and the
+# force now enters x, with weight dt / kT.  1 < k <= 10 and every segment in a general cell: 1e-10.  k > 10: 1e-9
+# (tests/test_brownian.py).  Segments chain through first_step, so the noise counter is the global step throughout.
+# The virial: virial_count is the number of global steps g of the segment with g % virial_every == 0, virial_sum the
+# shadow's to 1e-12 relative (pseudo hard spheres: the energy tolerance, relative).
+#
+# FIRE.  Every call restarts the minimiser's own state (v = 0, dt = dt_initial, alpha = alpha0), so a segment is a run
+# of max_steps = k that cannot converge (tol = 1e-300).  Its closing evaluation is at the positions it leaves: (A) is
+# exact at the held positions, f_rms included.  (B): a numpy restatement of the algorithm (FireRestated) from the
+# segment's start; one step in a diagonal cell |dx| <= 8 spacing(Lmax) + dt_initial^2 tol_F (x += dt (dt f)), <= 10
+# steps 1e-10, beyond 1e-9.  Convergence is audited apart (audit_fire_convergence).
+# =================================================================================================================
+BD_MIXED = (1, 1, 2, 1, 5, 1, 9, 1, 3, 1, 10, 1, 7, 1, 10, 1, 6, 1, 8, 1)
+BD_CHUNKS = (31, 32, 33, 64, 65)      # across the 32-step host chunk, with and without a remainder
+FIRE_MIXED = (0, 1, 1, 2, 5, 9, 14, 10, 3, 33, 7)
+LONG_X_TOL = 1e-9                     # x after > 10 steps (tests/test_brownian.py, tests/test_fire.py)
+LONG_F_TOL = 1e-8                     # f after > 10 steps, times max(1, |F|inf)
+W_SLOPE = 64.0                        # |dW| <= W_SLOPE sum_i |f_i| |dx|: see above
+NEVER = 1e-300                        # a FIRE tolerance no force meets
+
+
+def wrap_np(x, img, box, cell=None, cell_inv=None):
+    """oracle/md_oracle.c wrap1 / wrap_tric restated, operation for operation: (wrapped x, images) as new arrays."""
+    img = img.copy()
+    if cell is None:
+        L = np.asarray(box, dtype=np.float64)
+        frac = (1.0 / L) * x
+        nn = np.floor(frac)
+        img += nn.astype(np.int32)
+        return L * (frac - nn), img
+    d = x.shape[1]
+    U, Ui = np.asarray(cell, dtype=np.float64), np.asarray(cell_inv, dtype=np.float64)
+
+    def rows(M, y):
+        out = np.empty_like(y)
+        for r in range(d):
+            a = M[r, 0] * y[:, 0] + M[r, 1] * y[:, 1]
+            out[:, r] = a + M[r, 2] * y[:, 2] if d == 3 else a
+        return out
+    frac = rows(Ui, x)
+    nn = np.floor(frac)
+    img += nn.astype(np.int32)
+    return rows(U, frac - nn), img
+
+
+def philox_np(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 on arrays (or scalars) of counter and key words; returns the four output words as uint64 arrays."""
+    m = np.uint64(0xFFFFFFFF)
+    s32 = np.uint64(32)
+    c0, c1, c2, c3, k0, k1 = (np.asarray(a, dtype=np.uint64) & m for a in np.broadcast_arrays(c0, c1, c2, c3, k0, k1))
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ k0, p1 & m, (p0 >> s32) ^ c3 ^ k1, p0 & m
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m, (k1 + np.uint64(0xBB67AE85)) & m
+    return c0, c1, c2, c3
+
+
+def _unwrapped_diff(x, img, ref_x, ref_img, U):
+    return np.abs((x - ref_x) + (img - ref_img) @ U.T)
+
+
+def _x_bound(k, cell, one_step):
+    """(bound, key of `worst`) of the unwrapped positions after k moves."""
+    if k == 1 and cell is None:
+        return one_step, "x1"
+    if k <= SHORT_STEPS or cell is not None:
+        return SHORT_TOL, "x"
+    return LONG_X_TOL, "xl"
+
+
+class _Setup:
+    """The quantities all modes derive from (system, pot, cutoff, cell)."""
+
+    def __init__(self, system, pot, cutoff, cell):
+        self.n, self.dim = system["x"].shape
+        self.box = np.asarray(system["box"], dtype=np.float64)
+        self.diam = np.asarray(system["diam"], dtype=np.float64)
+        self.cell = cell
+        self.U = cell_matrix(self.box, cell)
+        self.Lmax = float(np.abs(self.U).sum(axis=1).max()) if cell is not None else float(self.box.max())
+        self.ftol, self.etol = force_tolerance(pot), energy_tolerance(pot)
+        self.thresholds = pair_thresholds(pot, cutoff, self.diam)
+
+    def ledger(self, keys):
+        return Ledger(keys, self.box, self.cell, self.thresholds)
+
+
+def audit_brownian(stepper, oracle, system, pot, cutoff, dt, ktemp, seed, schedule, first_step=0, virial_every=10,
+                   cell=None, raise_on_failure=True):
+    """The Brownian mode: `stepper` has upload / download / stats and run_brownian(nsteps, dt, ktemp, seed, first_step,
+    virial_every) -> dict(U, W, virial_sum, virial_count), the shape of MDDevice.  Checks as the comment block above says.
+    worst: F U W (k <= 10), Fl (k > 10), V (virial sum), x1 (one step), x (<= 10 steps, general cell), xl (> 10 steps);
+    segments: dict(k, g0, rebuilds, violations)."""
+    su = _Setup(system, pot, cutoff, cell)
+    box, diam, n = su.box, su.diam, su.n
+    led = su.ledger(("F", "U", "W", "Fl", "V", "x1", "x", "xl"))
+    note, miss = led.note, led.miss
+    segments = []
+    kw = dict(use_cells=False, nthreads=1, virial_every=virial_every)
+    with (oracle.set_cell(cell) if cell is not None else contextlib.nullcontext()):
+        f0 = oracle.forces_brute(system["x"], box, cutoff, pot, diam)[0]
+        stepper.upload(system["x"], system["v"], f0, system["img"], diam)
+        start = stepper.download()
+        g0 = int(first_step)
+        for seg, k in enumerate(schedule):
+            where = "segment %d (global steps %d..%d)" % (seg, g0, g0 + k - 1)
+            before = stepper.stats()
+            got = stepper.run_brownian(k, dt, ktemp, seed, first_step=g0, virial_every=virial_every)
+            x, v, f, img = end = stepper.download()
+            after = stepper.stats()
+            segments.append(dict(k=k, g0=g0, **{key: int(after[key] - before[key]) for key in ("rebuilds", "violations")}))
+
+            # ---- the shadow: k - 1 steps, then the last one (the same arithmetic as k steps in one call)
+            x0, _, _, img0 = start
+            head = oracle.run_brownian(x0, img0, diam, box, cutoff, pot, dt, ktemp, seed, k - 1, first_step=g0, **kw)
+            ref = oracle.run_brownian(head["x"], head["img"], diam, box, cutoff, pot, dt, ktemp, seed, 1,
+                                      first_step=g0 + k - 1, **kw)
+            finf = float(np.abs(ref["f"]).max())
+            tol_f = su.ftol * max(1.0, finf)
+            xb, xkey = _x_bound(k, cell, 8.0 * float(np.spacing(su.Lmax)) + (dt / ktemp) * tol_f)
+
+            # ---- (A) the forces of the last evaluation, at the positions before the last move
+            knife, keep = led.knife(head["x"])
+            if k == 1:
+                fb, fkey, slope = tol_f, "F", 0.0
+            elif k <= SHORT_STEPS:
+                fb, fkey, slope = tol_f + SHORT_TOL * finf, "F", SHORT_TOL
+            else:
+                fb, fkey, slope = LONG_F_TOL * max(1.0, finf), "Fl", LONG_X_TOL
+            err = np.abs(f - ref["f"])[keep].max() if keep.any() else 0.0
+            if note(fkey, err, fb):
+                i = int(np.argmax(np.abs(f - ref["f"]).max(axis=1) * keep))
+                miss("A", "F", "%s: |dF|inf = %.3e > %.3e (particle %d)" % (where, err, fb, i))
+            if len(knife) == 0:
+                f1 = float(np.abs(ref["f"]).sum())
+                for key, mult in (("U", 1.0), ("W", W_SLOPE)):
+                    bound = su.etol * max(1.0, abs(ref[key])) + mult * slope * f1
+                    if note(key, abs(got[key] - ref[key]), bound):
+                        miss("A", key, "%s: %s = %.17g, oracle %.17g, |d| = %.3e > %.3e"
+                             % (where, key, got[key], ref[key], abs(got[key] - ref[key]), bound))
+
+            # ---- (B) the end state
+            dx = _unwrapped_diff(x, img, ref["x"], ref["img"], su.U)
+            if note(xkey, dx.max(), xb):
+                miss("B", "x", "%s: |dx|inf = %.3e > %.3e (particle %d)" % (where, dx.max(), xb, int(dx.max(axis=1).argmax())))
+            led.images(where, img, ref["x"], ref["img"], xb)
+            if not np.array_equal(v, system["v"]):
+                miss("B", "v", "%s: the velocities are not the uploaded ones" % where)
+
+            # ---- the virial bookkeeping, on the global step
+            count = sum(1 for g in range(g0, g0 + k) if g % virial_every == 0)
+            vsum = head["virial_sum"] + ref["virial_sum"]
+            assert count == head["virial_count"] + ref["virial_count"]
+            if got["virial_count"] != count:
+                miss("V", "count", "%s: virial_count = %g, %d steps sampled" % (where, got["virial_count"], count))
+            bound = su.etol * max(abs(vsum), np.finfo(float).tiny)
+            if note("V", abs(got["virial_sum"] - vsum), bound):
+                miss("V", "sum", "%s: virial_sum = %.17g, oracle %.17g" % (where, got["virial_sum"], vsum))
+
+            led.close_segment(where, raise_on_failure)
+            start = end
+            g0 += k
+        stats = stepper.stats()
+    return led.result(segments, stats)
+
+
+class FireRestated:
+    """fire_minimize! restated in numpy over oracle.forces_brute (oracle/md_oracle.c oracle_fire_minimize, statement for
+    statement; the sums are numpy's, so P, |v| and |f| differ from the C loop's in the last bits).  run() also returns
+    `trace`, one dict(P, branch, f_rms, energy, dt, finf) per executed step -- branch 'accelerate' (P > 0 past nmin: dt
+    and alpha change), 'hold' (P > 0), 'reset' (P <= 0) or 'converged' -- and `hist`, the (x, img) every evaluation,
+    the closing one included, took place at.  The three pieces a sabotaged copy overrides are methods."""
+
+    def __init__(self, oracle, box, cutoff, pot, diam, cell=None):
+        self.o, self.box, self.cutoff, self.pot, self.diam, self.cell = oracle, box, cutoff, pot, diam, cell
+        self.cell_inv = oracle.set_cell.inverse() if cell is not None else None
+
+    mix_first = True      # the mix comes before the sign test of P, with the alpha of this step
+
+    def mix(self, v, f, alpha, vn, fn):
+        return (1.0 - alpha) * v + (alpha * (vn / fn)) * f
+
+    def update(self, P, dt, alpha, since_neg, kw):
+        """-> (dt, alpha, since_neg, branch)"""
+        if P > 0.0:
+            since_neg += 1
+            if since_neg > kw["nmin"]:
+                return min(dt * kw["f_inc"], kw["dt_max"]), alpha * 0.99, since_neg, "accelerate"
+            return dt, alpha, since_neg, "hold"
+        return max(dt * kw["f_dec"], kw["dt_initial"]), kw["alpha0"], 0, "reset"
+
+    def drift(self, x, img, v, dt_new, dt_old):
+        return wrap_np(x + dt_new * v, img, self.box, self.cell, self.cell_inv)
+
+    def converging_step(self, x, img, v, f, dt):
+        return x, img
+
+    def run(self, x, img, max_steps, tol, dt_initial=0.01, dt_max=0.1, alpha0=0.1, f_inc=1.2, f_dec=0.2, nmin=5):
+        kw = dict(dt_initial=dt_initial, dt_max=dt_max, alpha0=alpha0, f_inc=f_inc, f_dec=f_dec, nmin=nmin)
+        x, img = np.array(x, dtype=np.float64), np.array(img, dtype=np.int32)
+        n, dim = x.shape
+        v = np.zeros_like(x)
+        alpha, dt, ndof, since_neg, steps, converged = alpha0, dt_initial, dim * (n - 1.0), 0, 0, False
+        trace, hist = [], []
+        for step in range(1, max_steps + 2):
+            f, u, _, _ = self.o.forces_brute(x, self.box, self.cutoff, self.pot, self.diam)
+            hist.append((x.copy(), img.copy()))
+            fn = float(np.sqrt((f * f).sum(axis=1).sum()))
+            f_rms = fn / np.sqrt(ndof)
+            if step == max_steps + 1:
+                break
+            steps += 1
+            rec = dict(f_rms=f_rms, energy=u, dt=dt, finf=float(np.abs(f).max()), P=0.0, branch="converged")
+            trace.append(rec)
+            if f_rms < tol:
+                converged = True
+                x, img = self.converging_step(x, img, v, f, dt)
+                break
+            v = v + dt * f
+            P = float((v * f).sum(axis=1).sum())
+            vn = float(np.sqrt((v * v).sum(axis=1).sum()))
+            dt_old, alpha_old = dt, alpha
+            if self.mix_first and vn > 0.0 and fn > 0.0:
+                v = self.mix(v, f, alpha_old, vn, fn)
+            dt, alpha, since_neg, branch = self.update(P, dt, alpha, since_neg, kw)
+            if not self.mix_first and vn > 0.0 and fn > 0.0:
+                v = self.mix(v, f, alpha, vn, fn)
+            if branch == "reset":
+                v = np.zeros_like(x)
+            rec.update(P=P, branch=branch)
+            x, img = self.drift(x, img, v, dt, dt_old)
+        return dict(x=x, img=img, f=f, steps=steps, converged=converged, energy=u, f_rms=f_rms, trace=trace, hist=hist)
+
+
+def audit_fire(stepper, oracle, system, pot, cutoff, fire_kw, schedule, cell=None, raise_on_failure=True):
+    """The FIRE mode: `stepper` has upload / download / stats and fire_minimize(max_steps, tol, **fire_kw) ->
+    dict(steps, converged, energy, f_rms).  worst: F U R (f_rms) of check (A); x1, x, xl as in the Brownian mode.
+    segments: dict(k, rebuilds, violations, branches) with the shadow's branches of that segment."""
+    su = _Setup(system, pot, cutoff, cell)
+    box, diam, n = su.box, su.diam, su.n
+    led = su.ledger(("F", "U", "R", "x1", "x", "xl"))
+    note, miss = led.note, led.miss
+    segments = []
+    dt0 = float(fire_kw.get("dt_initial", 0.01))
+    with (oracle.set_cell(cell) if cell is not None else contextlib.nullcontext()):
+        shadow = FireRestated(oracle, box, cutoff, pot, diam, cell)
+        f0 = oracle.forces_brute(system["x"], box, cutoff, pot, diam)[0]
+        stepper.upload(system["x"], system["v"], f0, system["img"], diam)
+        start = stepper.download()
+        a = 0
+        for seg, k in enumerate(schedule):
+            where = "segment %d (steps %d..%d)" % (seg, a, a + k - 1)
+            before = stepper.stats()
+            got = stepper.fire_minimize(max_steps=k, tol=NEVER, **fire_kw)
+            x, v, f, img = end = stepper.download()
+            after = stepper.stats()
+            x0, _, _, img0 = start
+            ref = shadow.run(x0, img0, k, NEVER, **fire_kw)
+            segments.append(dict(k=k, branches=[t["branch"] for t in ref["trace"]],
+                                 **{key: int(after[key] - before[key]) for key in ("rebuilds", "violations")}))
+            if got["steps"] != k or got["converged"]:
+                miss("B", "steps", "%s: steps = %d, converged = %s" % (where, got["steps"], got["converged"]))
+
+            # ---- (A) the closing evaluation, at the positions the stepper holds
+            f_ref, u_ref, _, _ = oracle.forces_brute(x, box, cutoff, pot, diam)
+            knife, keep = led.knife(x)
+            tol_f = su.ftol * max(1.0, float(np.abs(f_ref).max()))
+            err = np.abs(f - f_ref)[keep].max() if keep.any() else 0.0
+            if note("F", err, tol_f):
+                i = int(np.argmax(np.abs(f - f_ref).max(axis=1) * keep))
+                miss("A", "F", "%s: |dF|inf = %.3e > %.3e (particle %d)" % (where, err, tol_f, i))
+            if len(knife) == 0:
+                bound = su.etol * max(1.0, abs(u_ref))
+                if note("U", abs(got["energy"] - u_ref), bound):
+                    miss("A", "U", "%s: energy = %.17g, oracle %.17g" % (where, got["energy"], u_ref))
+                r_ref = float(np.sqrt((f_ref * f_ref).sum())) / np.sqrt(su.dim * (n - 1.0))
+                if note("R", abs(got["f_rms"] - r_ref), 1e-12 * max(r_ref, np.finfo(float).tiny)):
+                    miss("A", "f_rms", "%s: f_rms = %.17g, oracle %.17g" % (where, got["f_rms"], r_ref))
+
+            # ---- (B) the restated algorithm from the segment's start
+            finf0 = ref["trace"][0]["finf"] if ref["trace"] else 0.0
+            xb, xkey = _x_bound(k, cell, 8.0 * float(np.spacing(su.Lmax)) + dt0 * dt0 * su.ftol * max(1.0, finf0))
+            dx = _unwrapped_diff(x, img, ref["x"], ref["img"], su.U)
+            if note(xkey, dx.max(), xb):
+                miss("B", "x", "%s: |dx|inf = %.3e > %.3e (particle %d)" % (where, dx.max(), xb, int(dx.max(axis=1).argmax())))
+            led.images(where, img, ref["x"], ref["img"], xb)
+            if not np.array_equal(v, system["v"]):
+                miss("B", "v", "%s: the MD velocities are not the uploaded ones" % where)
+            led.close_segment(where, raise_on_failure)
+            start = end
+            a += k
+        stats = stepper.stats()
+    return led.result(segments, stats)
+
+
+def pick_tolerance(f_rms, j):
+    """A tolerance at which evaluation j (1-based) is the first to converge: the midpoint between its f_rms and the
+    smallest earlier one (j == 1: twice its f_rms -- nothing precedes it), or None if the two are closer than 1e-6
+    relative or evaluation j is not the smallest so far."""
+    r = float(f_rms[j - 1])
+    if j == 1:
+        return 2.0 * r
+    prev = float(min(f_rms[:j - 1]))
+    if not (prev - r >= 1e-6 * prev):
+        return None
+    return 0.5 * (prev + r)
+
+
+def audit_fire_convergence(stepper, oracle, system, pot, cutoff, fire_kw, cell=None, wanted=(1, 16, 32), horizon=40,
+                           raise_on_failure=True):
+    """Convergence inside the host loop's 32-step chunk.  From the uploaded start the restated algorithm gives the f_rms of
+    every evaluation; for each j in `wanted` (or the nearest j with a usable gap, see pick_tolerance) the stepper runs
+    from the same start with that tolerance and must report converged, steps == j, the energy of evaluation j, and
+    hold the positions of evaluation j -- the shadow's after j - 1 moves, within the bound of a (j - 1)-step segment;
+    for j == 1 exactly the uploaded state as a download with no run in between returns it.  check 'C'."""
+    su = _Setup(system, pot, cutoff, cell)
+    box, diam = su.box, su.diam
+    led = su.ledger(("U", "x1", "x", "xl"))
+    note, miss = led.note, led.miss
+    segments = []
+    dt0 = float(fire_kw.get("dt_initial", 0.01))
+    with (oracle.set_cell(cell) if cell is not None else contextlib.nullcontext()):
+        shadow = FireRestated(oracle, box, cutoff, pot, diam, cell)
+        f0 = oracle.forces_brute(system["x"], box, cutoff, pot, diam)[0]
+        stepper.upload(system["x"], system["v"], f0, system["img"], diam)
+        x_up, v_up, _, img_up = stepper.download()
+        ref = shadow.run(x_up, img_up, horizon, NEVER, **fire_kw)
+        f_rms = [t["f_rms"] for t in ref["trace"]]
+        for want in wanted:
+            j, tol = None, None
+            for cand in sorted(range(1 if want == 1 else 2, horizon), key=lambda c: (abs(c - want), c)):
+                tol = pick_tolerance(f_rms, cand)
+                if tol is not None:
+                    j = cand
+                    break
+            assert j is not None, "no evaluation with a usable f_rms gap"
+            where = "convergence at evaluation %d (tol %.6e)" % (j, tol)
+            stepper.upload(system["x"], system["v"], f0, system["img"], diam)
+            before = stepper.stats()
+            got = stepper.fire_minimize(max_steps=horizon, tol=tol, **fire_kw)
+            x, v, f, img = stepper.download()
+            after = stepper.stats()
+            segments.append(dict(k=j - 1, j=j, tol=tol, steps=got["steps"], converged=bool(got["converged"]),
+                                 **{key: int(after[key] - before[key]) for key in ("rebuilds", "violations")}))
+            rec, (xr, imr) = ref["trace"][j - 1], ref["hist"][j - 1]
+            if not got["converged"]:
+                miss("C", "converged", "%s: not converged after %d steps" % (where, got["steps"]))
+            if got["steps"] != j:
+                miss("C", "steps", "%s: steps = %d" % (where, got["steps"]))
+            finf0 = ref["trace"][0]["finf"]
+            xb, xkey = _x_bound(j - 1, cell, 8.0 * float(np.spacing(su.Lmax)) + dt0 * dt0 * su.ftol * max(1.0, finf0))
+            if j == 1:
+                if not (np.array_equal(x, x_up) and np.array_equal(img, img_up)):
+                    miss("C", "x", "%s: the positions moved on the converging step" % where)
+            else:
+                dx = _unwrapped_diff(x, img, xr, imr, su.U)
+                if note(xkey, dx.max(), xb):
+                    miss("C", "x", "%s: |dx|inf = %.3e > %.3e" % (where, dx.max(), xb))
+                led.images(where, img, xr, imr, xb, check="C")
+            fr = oracle.forces_brute(xr, box, cutoff, pot, diam)[0]
+            bound = su.etol * max(1.0, abs(rec["energy"])) + (xb if j > 1 else 0.0) * float(np.abs(fr).sum())
+            if note("U", abs(got["energy"] - rec["energy"]), bound):
+                miss("C", "energy", "%s: energy = %.17g, evaluation %d has %.17g" % (where, got["energy"], j, rec["energy"]))
+            if not np.array_equal(v, v_up):
+                miss("C", "v", "%s: the MD velocities are not the uploaded ones" % where)
+            if led.failures and raise_on_failure:
+                raise led.failures[0]
+        stats = stepper.stats()
+    return led.result(segments, stats)
+
+
+def loop_margins_line(name, result):
+    """One line per case for the records of the Brownian and FIRE modes: every entry of `worst` as a fraction of its bound."""
+    w = result["worst"]
+    return "%-30s %s | excl %d  img %d" % (
+        name, "  ".join("%s %.1e" % (k, w[k]) for k in w), len(result["excluded"]), len(result["image_exceptions"]))
+
+
+class OracleBrownianStepper:
+    """The Brownian stepper interface on the oracle's own functions: forces_brute, the Philox block (philox_np, held to
+    oracle.philox by tests/test_loop_audit.py) and the oracle's move and wrap restated operation for operation, so that
+    audit_brownian sees exactly zero error.  The pieces a sabotaged stepper overrides are methods."""
+
+    def __init__(self, oracle, box, cutoff, pot, cell=None):
+        self.o, self.box, self.cutoff, self.pot, self.cell = oracle, np.asarray(box, dtype=np.float64), cutoff, pot, cell
+        self.steps = 0
+
+    def upload(self, x, v, f, images, diameters):
+        self.x, self.v, self.f = (np.array(a, dtype=np.float64) for a in (x, v, f))
+        self.img = np.array(images, dtype=np.int32)
+        self.diam = np.array(diameters, dtype=np.float64)
+        self.cell_inv = self.o.set_cell.inverse() if self.cell is not None else None
+
+    def download(self):
+        return self.x.copy(), self.v.copy(), self.f.copy(), self.img.copy()
+
+    def stats(self):
+        return dict(steps=self.steps, prunes=0, rebuilds=0, violations=0, fused=0)
+
+    def forces(self, x, t):
+        """(f, U, W) at x for local step t"""
+        f, u, w, _ = self.o.forces_brute(x, self.box, self.cutoff, self.pot, self.diam)
+        return f, u, w
+
+    def counter(self, g, first_step, t):
+        """the two counter words of the global step g = first_step + t"""
+        return g & 0xFFFFFFFF, (g >> 32) & 0xFFFFFFFF
+
+    def key(self, seed):
+        return seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+
+    def noise_ids(self):
+        return np.arange(len(self.x))
+
+    def mobility(self, dt, ktemp, f):
+        return f * dt / ktemp
+
+    def wrap(self, x, img):
+        return wrap_np(x, img, self.box, self.cell, self.cell_inv)
+
+    def samples(self, g, t, virial_every):
+        return g % virial_every == 0
+
+    def run_brownian(self, nsteps, dt, ktemp, seed, first_step=0, virial_every=10):
+        sigma = np.sqrt(2.0 * dt)
+        u = w = vsum = vcnt = 0.0
+        for t in range(nsteps):
+            g = int(first_step) + t
+            self.f, u, w = self.forces(self.x, t)
+            if self.samples(g, t, virial_every):
+                vsum += w
+                vcnt += 1.0
+            words = philox_np(self.noise_ids(), *self.counter(g, int(first_step), t), 0, *self.key(int(seed)))
+            un = (np.stack(words[:self.x.shape[1]], axis=1).astype(np.float64) + 0.5) * 2.3283064365386963e-10
+            noise = (2.0 * un - 1.0) * 1.7320508075688772
+            self.x, self.img = self.wrap(self.x + self.mobility(dt, ktemp, self.f) + noise * sigma, self.img)
+            self.steps += 1
+        return dict(U=u, W=w, virial_sum=vsum, virial_count=vcnt)
+
+
+class OracleFireStepper:
+    """The FIRE stepper interface on oracle.fire_minimize (brute force).  `restated`: a FireRestated (sub)class to run
+    instead -- what the sabotaged steppers of tests/test_loop_audit.py are made of."""
+
+    def __init__(self, oracle, box, cutoff, pot, cell=None, restated=None):
+        self.o, self.box, self.cutoff, self.pot, self.cell = oracle, np.asarray(box, dtype=np.float64), cutoff, pot, cell
+        self.restated = restated
+        self.steps = 0
+
+    upload = OracleBrownianStepper.upload
+    download = OracleBrownianStepper.download
+    stats = OracleBrownianStepper.stats
+
+    def restore_velocities(self, v):
+        self.v = v
+
+    def fire_minimize(self, max_steps=10000, tol=1e-6, **kw):
+        v = self.v.copy()
+        self.v = np.zeros_like(v)               # FIRE's own velocities live where the MD ones do
+        if self.restated is None:
+            r = self.o.fire_minimize(self.x, self.img, self.diam, self.box, self.cutoff, self.pot, max_steps=max_steps,
+                                     tol=tol, use_cells=False, nthreads=1, **kw)
+        else:
+            r = self.restated(self.o, self.box, self.cutoff, self.pot, self.diam, self.cell).run(
+                self.x, self.img, max_steps, tol, **kw)
+        self.x, self.img, self.f = r["x"], r["img"], r["f"]
+        self.steps += r["steps"]
+        self.restore_velocities(v)
+        return dict(steps=r["steps"], converged=r["converged"], energy=r["energy"], f_rms=r["f_rms"])

@@ -1,6 +1,11 @@
 """Brownian dynamics (src/simulation.jl:181-308, src/integrate.jl:55-82).  The reference
 method is broken (D9), so this is the restated algorithm with a counter-based noise stream; parity = device vs the
-oracle's restatement with the same Philox stream, plus the statistics free diffusion must obey."""
+oracle's restatement with the same Philox stream, plus the statistics free diffusion must obey.
+
+What this file pins is one shape -- the cubic 3-D monodisperse LJ liquid, over 60 and 120 steps at 1e-9 -- and a golden
+vector of it.  Everything else about md_run_brownian (2-D, diameters, the other potentials and a user potential, general
+cells, systems below and just above a wave, the violation redo and the 32-step host chunk, the high words of the step
+counter and of the seed, the path switches) is audited segment by segment in tests/test_gpu_loop_audit.py."""
 import numpy as np
 import pytest
 
@@ -81,3 +86,66 @@ def test_run_simulation_brownian(tmp_path):
     assert os.path.isfile(os.path.join(path, "final.xyz")) and os.path.isfile(os.path.join(path, "trajectory.xyz"))
     assert np.abs(np.asarray(state.system.positions) - x0).max() > 0
     state.system.device.close()
+
+
+def _golden():
+    import os
+    return np.load(os.path.join(os.path.dirname(__file__), "golden", "brownian_lj_n512.npz"))
+
+
+def test_oracle_brownian_matches_golden(oracle):
+    g = _golden()
+    s = lj_system(512, kT=1.0, permute=777)
+    pot = oracle.make_pot(0, LJ)
+    r = oracle.run_brownian(s["x"], s["img"], s["diam"], s["box"], 2.5, pot, float(g["dt"]), float(g["ktemp"]),
+                            int(g["seed"]), int(g["nsteps"]), use_cells=False, nthreads=1)
+    assert int(g["seed"]) == 0xC0FFEE1234ABCDEF and int(g["nsteps"]) == 60
+    assert np.abs(r["x"] - g["x_end"]).max() <= 1e-10 and np.array_equal(r["img"], g["img_end"])
+    assert np.abs(r["f"] - g["f_end"]).max() <= 1e-10 * max(1.0, np.abs(g["f_end"]).max())
+    for key in ("U", "W", "virial_sum"):
+        assert abs(r[key] - float(g[key])) <= 1e-10 * abs(float(g[key])), key
+    assert r["virial_count"] == float(g["virial_count"]) == 6
+
+
+@pytest.mark.gpu
+def test_device_brownian_matches_golden():
+    from moleculardynamics.jl_amd import MDDevice
+    g = _golden()
+    s = lj_system(512, kT=1.0, permute=777)
+    with MDDevice(3, 512, s["box"], 2.5) as dev:
+        dev.set_potential(0, LJ)
+        dev.upload(s["x"], s["v"], s["f"], s["img"], s["diam"])
+        r = dev.run_brownian(int(g["nsteps"]), float(g["dt"]), float(g["ktemp"]), int(g["seed"]))
+        x, _, f, img = dev.download()
+    assert np.abs(x - g["x_end"]).max() <= 1e-9 and np.array_equal(img, g["img_end"])
+    assert np.abs(f - g["f_end"]).max() <= 1e-8 * max(1.0, np.abs(g["f_end"]).max())
+    for key in ("U", "W", "virial_sum"):
+        assert abs(r[key] - float(g[key])) <= 1e-9 * abs(float(g[key])), key
+    assert r["virial_count"] == float(g["virial_count"])
+
+
+@pytest.mark.gpu
+def test_device_brownian_zero_steps_changes_nothing():
+    """nsteps == 0 evaluates nothing: it returns zeros, as the oracle does (not the U / W an earlier call left in the
+    device scalars), and positions, velocities, forces, images and the counters stay as they were."""
+    from moleculardynamics.jl_amd import MDDevice
+    s = lj_system(512, kT=1.0, permute=777)
+    with MDDevice(3, 512, s["box"], 2.5) as dev:
+        dev.set_potential(0, LJ)
+        dev.upload(s["x"], s["v"], s["f"], s["img"], s["diam"])
+        first = dev.run_brownian(7, 2e-4, 1.5, 99)
+        assert first["U"] != 0.0 and first["W"] != 0.0
+        before, st0 = dev.download(), dev.stats()
+        r = dev.run_brownian(0, 2e-4, 1.5, 99, first_step=7)
+        after, st1 = dev.download(), dev.stats()
+        assert r == dict(U=0.0, W=0.0, virial_sum=0.0, virial_count=0.0)
+        for a, b in zip(before, after):
+            assert np.array_equal(a, b)
+        assert st0 == st1
+        # ... and the run goes on from there as if the empty call had not happened
+        dev.run_brownian(5, 2e-4, 1.5, 99, first_step=7)
+        x12 = dev.download()[0]
+        dev.upload(s["x"], s["v"], s["f"], s["img"], s["diam"])
+        dev.run_brownian(7, 2e-4, 1.5, 99)
+        dev.run_brownian(5, 2e-4, 1.5, 99, first_step=7)
+        assert np.array_equal(dev.download()[0], x12)
