@@ -826,7 +826,11 @@ void rebuild_t(md_ctx *c)
     BoxGrid g = c->grid;
 
     // (k_wrap_count also writes the scan's extra item, nimg[n_src] = 0)
-    k_wrap_count<D><<<nbs, MD_BLOCK, 0, st>>>(n_src, n_own_src, so, g, alive, c->nimg.p);
+    // A slab may own no particle, or have no source at all: a launch with an empty grid is an error, not a no-op.
+    if (nbs > 0)
+        k_wrap_count<D><<<nbs, MD_BLOCK, 0, st>>>(n_src, n_own_src, so, g, alive, c->nimg.p);
+    else
+        HIPCHK(hipMemsetAsync(c->nimg.p, 0, sizeof(int32_t), st));
     // exclusive scan over n_src+1 items -> img_off[n_src] = total number of sort entries
     size_t tmp_bytes = 0;
     HIPCHK(rocprim::exclusive_scan(nullptr, tmp_bytes, c->nimg.p, c->img_off.p, (int32_t)0, (size_t)n_src + 1,
@@ -846,22 +850,25 @@ void rebuild_t(md_ctx *c)
     DevState sn = c->dev(c->cur ^ 1);
 
     // (k_emit also zeroes the cell ranges that k_gather fills in after the sort: nothing reads them in between)
-    k_emit<D><<<nbs, MD_BLOCK, 0, st>>>(n_src, n_own_src, so, g, alive, c->img_off.p, c->keys_in.p, c->vals_in.p,
-                                        c->cell_start.p, c->cell_end.p, c->ncell_ext + 1);
+    if (nbs > 0)
+        k_emit<D><<<nbs, MD_BLOCK, 0, st>>>(n_src, n_own_src, so, g, alive, c->img_off.p, c->keys_in.p, c->vals_in.p,
+                                            c->cell_start.p, c->cell_end.p, c->ncell_ext + 1);
     // Only the (ghost bit, cell) digits are sorted -- three radix passes instead of five.  The sort is stable, so the
     // particles of a cell keep the order they were emitted in (source-slot order), which is as deterministic as the
     // id order the low digits would give.
     unsigned begin_bit = (unsigned)g.id_bits, end_bit = (unsigned)(g.id_bits + g.cell_bits + 1);
     tmp_bytes = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, c->keys_in.p, c->keys_out.p, c->vals_in.p, c->vals_out.p,
-                                     (size_t)next, begin_bit, end_bit, st));
-    c->sort_tmp.ensure(tmp_bytes);
-    HIPCHK(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, c->keys_in.p, c->keys_out.p, c->vals_in.p,
-                                     c->vals_out.p, (size_t)next, begin_bit, end_bit, st));
-    // (k_gather also resets the build's flags for the first attempt below)
-    k_gather<D><<<nblocks(next), MD_BLOCK, 0, st>>>(n, (int)next, so, sn, g, c->keys_out.p, c->vals_out.p,
-                                                     c->newslot.p, c->gsrc.p, c->gcode.p, c->cell_start.p,
-                                                     c->cell_end.p, c->scal.p);
+    if (next > 0) {
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, c->keys_in.p, c->keys_out.p, c->vals_in.p, c->vals_out.p,
+                                         (size_t)next, begin_bit, end_bit, st));
+        c->sort_tmp.ensure(tmp_bytes);
+        HIPCHK(rocprim::radix_sort_pairs(c->sort_tmp.p, tmp_bytes, c->keys_in.p, c->keys_out.p, c->vals_in.p,
+                                         c->vals_out.p, (size_t)next, begin_bit, end_bit, st));
+        // (k_gather also resets the build's flags for the first attempt below)
+        k_gather<D><<<nblocks(next), MD_BLOCK, 0, st>>>(n, (int)next, so, sn, g, c->keys_out.p, c->vals_out.p,
+                                                         c->newslot.p, c->gsrc.p, c->gcode.p, c->cell_start.p,
+                                                         c->cell_end.p, c->scal.p);
+    }
     if (nghost > 0)
         k_ghost_owner<<<nblocks(nghost), MD_BLOCK, 0, st>>>(nghost, c->gsrc.p, c->newslot.p, c->gowner.p);
     c->cur ^= 1;
@@ -902,11 +909,12 @@ void rebuild_t(md_ctx *c)
         float rl2f = (float)(rl2 * (1.0 + 1.0e-4));
         for (int attempt = 0; attempt < 8; ++attempt) {
             if (attempt > 0 || next == 0) k_reset_flags<<<1, 1, 0, st>>>(c->scal.p);
-            k_build_tile<D><<<c->nblk, MD_BT_THREADS, 0, st>>>(n, sn, g, rl2f, c->cell_start.p, c->cell_end.p,
-                                                               c->nlist16.p, c->maxn, c->nneigh.p, c->nmax_tile.p,
-                                                               c->halo.p, c->hcap, c->halo_count.p, c->scal.p,
-                                                               c->dbg_stamps.p, rs, c->allow_own_first ? 1 : 0);
-            if (c->dbg_stamps.p) {
+            if (c->nblk > 0) // (no tile on a slab that owns no particle: the reset flags stand, Hmax = 0)
+                k_build_tile<D><<<c->nblk, MD_BT_THREADS, 0, st>>>(n, sn, g, rl2f, c->cell_start.p, c->cell_end.p,
+                                                                   c->nlist16.p, c->maxn, c->nneigh.p, c->nmax_tile.p,
+                                                                   c->halo.p, c->hcap, c->halo_count.p, c->scal.p,
+                                                                   c->dbg_stamps.p, rs, c->allow_own_first ? 1 : 0);
+            if (c->dbg_stamps.p && c->nblk > 0) {
                 std::vector<long long> hs((size_t)c->nblk * 10);
                 HIPCHK(hipMemcpyAsync(hs.data(), c->dbg_stamps.p, hs.size() * 8, hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
@@ -936,9 +944,10 @@ void rebuild_t(md_ctx *c)
     if (!tile_ok) {
         for (int attempt = 0; attempt < 8; ++attempt) {
             k_reset_flags<<<1, 1, 0, st>>>(c->scal.p);
-            k_build_list<D><<<nb, MD_BLOCK, 0, st>>>(n, sn, g, rl2, c->cell_start.p, c->cell_end.p, c->nlist.p,
-                                                     c->maxn, c->nneigh.p, c->nmax_tile.p, (uint32_t)c->cap,
-                                                     c->scal.p);
+            if (nb > 0)
+                k_build_list<D><<<nb, MD_BLOCK, 0, st>>>(n, sn, g, rl2, c->cell_start.p, c->cell_end.p, c->nlist.p,
+                                                         c->maxn, c->nneigh.p, c->nmax_tile.p, (uint32_t)c->cap,
+                                                         c->scal.p);
             Scalars h;
             HIPCHK(hipMemcpyAsync(&h, c->scal.p, sizeof(Scalars), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
@@ -954,9 +963,10 @@ void rebuild_t(md_ctx *c)
                 HIPCHK(hipFuncSetAttribute((const void *)k_tile_localize, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
                 attr_dev_mask2 |= 1 << (c->device & 31);
             }
-            k_tile_localize<<<c->nblk, MD_TILE, lds, st>>>(c->nlist.p, c->nlist16.p, c->maxn, c->nmax_tile.p,
-                                                           (uint32_t)c->cap, c->halo.p, c->hcap, c->halo_count.p,
-                                                           c->scal.p, rs);
+            if (c->nblk > 0)
+                k_tile_localize<<<c->nblk, MD_TILE, lds, st>>>(c->nlist.p, c->nlist16.p, c->maxn, c->nmax_tile.p,
+                                                               (uint32_t)c->cap, c->halo.p, c->hcap, c->halo_count.p,
+                                                               c->scal.p, rs);
             Scalars h;
             HIPCHK(hipMemcpyAsync(&h, c->scal.p, sizeof(Scalars), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
@@ -967,7 +977,7 @@ void rebuild_t(md_ctx *c)
     // and the per-step ghost refresh disappears.  (Under slab decomposition the owner may itself be a received
     // x-halo record: those are real records, refreshed by message, and reference themselves with shift 0.)
     c->virtual_ghosts = c->use_tiles && c->cap < (1ll << 26);
-    if (c->virtual_ghosts && nghost > 0)
+    if (c->virtual_ghosts && nghost > 0 && c->nblk > 0)
         k_halo_virtualize<<<c->nblk, MD_BLOCK, 0, st>>>(n, c->halo.p, c->hcap, c->halo_count.p, c->gowner.p, c->gcode.p);
     if (getenv("MDHIP_ROWSTATS")) {
         std::vector<int32_t> nn((size_t)n), nm((size_t)c->ntiles);
@@ -4219,7 +4229,9 @@ int md_scale_velocities(md_ctx *ctx, double sfac)
     API_BEGIN
     require_state(ctx, "md_scale_velocities");
     DevState s = ctx->dev(ctx->cur);
-    if (ctx->dim == 3)
+    if (ctx->nblk <= 0) {
+        // (a slab that owns no particle)
+    } else if (ctx->dim == 3)
         k_scale_v<3><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->scal.p, sfac, 0);
     else
         k_scale_v<2><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, ctx->scal.p, sfac, 0);

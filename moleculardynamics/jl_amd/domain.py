@@ -437,7 +437,7 @@ class DomainDevice:
             self._kuw = torch.zeros(3, dtype=torch.float64, device=ex.device)
         self._stream.synchronize()
 
-    def run_async(self, nsteps, dt, ensemble=_lib.MD_NVE, tau=0.0, nf=None, ktemp=None, r1=None, r2=None):
+    def run_async(self, nsteps, dt, ensemble=_lib.MD_NVE, tau=0.0, nf=None, ktemp=None, r1=None, r2=None, thermo=True):
         """run() without a host wait per step.  A window of steps (up to the next scheduled list build) is
         enqueued on one stream: kernels of the library, the all-reduce (MIN) of the displacement flag, the
         neighbour exchange of the halo coordinates and the all-reduce (SUM) of K/U/W alternate in stream order.
@@ -445,7 +445,7 @@ class DomainDevice:
         evaluation, so all later kernels of the window skip themselves everywhere; the host reads the flag
         once per window, refreshes the rows at the drifted positions and resumes -- the single-GPU scheme,
         globally.  Collectives go through torch.distributed (RCCL: stream-ordered; gloo: staged, for tests).
-        Returns global (U, W, K) of the last step."""
+        Returns global (U, W, K) of the last step; thermo=False: the last step is no energy step either, returns None."""
         self._async_setup()
         torch = self.ex.torch
         L, h = self._L, self._h
@@ -458,19 +458,19 @@ class DomainDevice:
             sl, sr = sl[: ns[0] * POS_REC], sr[: ns[1] * POS_REC]
             rl, rr = rl[: nr[0] * POS_REC], rr[: nr[1] * POS_REC]
             for t in range(wlen):
-                last = ends_run and t == wlen - 1
+                want = thermo and ends_run and t == wlen - 1
                 self._chk(L.md_dom_step_a(h, float(dt), t))
                 self.ex.allreduce_dev(self._flag, "min")
                 self.ex.sendrecv_dev(sl, sr, rl, rr)
-                self._chk(L.md_dom_step_b(h, float(dt), t, 1 if last else 0))
-                if nvt or last:
+                self._chk(L.md_dom_step_b(h, float(dt), t, 1 if want else 0))
+                if nvt or want:
                     self.ex.allreduce_dev(self._kuw, "sum")
-                    if last or t == wlen - 1:       # (in between, the next kick-drift forms the scale itself)
-                        self._chk(L.md_dom_step_c(h, t, 1 if last else 0))
+                    if want or t == wlen - 1:       # (in between, the next kick-drift forms the scale itself)
+                        self._chk(L.md_dom_step_c(h, t, 1 if want else 0))
             self._chk(L.md_dom_async_end(h, 1 if ends_run else 0, C.byref(fv), uwk, info))
 
         with torch.cuda.stream(self._stream):
-            return self._run_planned(window, nsteps, dt, ensemble, tau, nf, ktemp, r1, r2)
+            return self._run_planned(window, nsteps, dt, ensemble, tau, nf, ktemp, r1, r2, thermo=thermo)
 
     # -- native transport: the window loop inside the library, RCCL issued by the library ----------------
     def _native_setup(self):
@@ -524,25 +524,25 @@ class DomainDevice:
         self._chk(self._L.md_dom_max_disp0(self._h, C.byref(d0)))
         return self.ex.allreduce([d0.value], op="max")[0]
 
-    def run_native(self, nsteps, dt, ensemble=_lib.MD_NVE, tau=0.0, nf=None, ktemp=None, r1=None, r2=None):
+    def run_native(self, nsteps, dt, ensemble=_lib.MD_NVE, tau=0.0, nf=None, ktemp=None, r1=None, r2=None, thermo=True):
         """run_async() with the window loop inside the library (md_dom_run_window): one C call per window,
         RCCL issued by the library on its own stream.  List builds still go through torch.distributed.
-        Returns global (U, W, K) of the last step."""
+        Returns global (U, W, K) of the last step; thermo=False: the last step is no energy step either, returns None."""
         self._native_setup()
         L, h = self._L, self._h
 
         def window(wlen, dt, ensemble, tau, nf, arrs, nvt, ends_run, prune_interval, fv, uwk, info):
             try:
                 self._chk(L.md_dom_run_window(h, wlen, float(dt), int(ensemble), float(tau), nf, *arrs,
-                                              1 if ends_run else 0, 1 if ends_run else 0, int(prune_interval), C.byref(fv),
-                                              uwk, info))
+                                              1 if ends_run and thermo else 0, 1 if ends_run else 0, int(prune_interval),
+                                              C.byref(fv), uwk, info))
             except Exception:
                 self._native_ready = False      # (the library aborted its communicator: md_dom_comm_init again)
                 raise
 
-        return self._run_planned(window, nsteps, dt, ensemble, tau, nf, ktemp, r1, r2)
+        return self._run_planned(window, nsteps, dt, ensemble, tau, nf, ktemp, r1, r2, thermo=thermo)
 
-    def _run_planned(self, window, nsteps, dt, ensemble, tau, nf, ktemp, r1, r2):
+    def _run_planned(self, window, nsteps, dt, ensemble, tau, nf, ktemp, r1, r2, thermo=True):
         """The window planner shared by run_async and run_native.  Without inner rows a window runs up to the
         next scheduled list build.  With enable_pruning() it spans a whole rebuild interval with prune steps
         inside; rebuild and prune intervals are planned from all-reduced displacement measurements, so every
@@ -629,14 +629,18 @@ class DomainDevice:
                     s = g
                     self._pruning = pruning
                     continue
-                self._chk(L.md_dom_forces(h, float(dt), 1, 1 if last else 0, uwk))
-                if nvt or last:
+                want = last and thermo
+                self._chk(L.md_dom_forces(h, float(dt), 1, 1 if want else 0, uwk))
+                if nvt or want:
                     U, W, K = self.ex.allreduce([uwk[0], uwk[1], uwk[2]])
                 if nvt:
                     scale = float(bussi_scale(K, ktemp[g], nf, dt, tau, r1[g], r2[g]))
                     K = K * scale * scale
                     if last:
+                        # (the window's scale word still holds the scale step m's drift consumed: nothing is pending
+                        # after this call, or the next run's first step would apply that stale scale once more)
                         self._chk(L.md_scale_velocities(h, scale))
+                        self._chk(L.md_dom_set_scale(h, 1.0))
                     else:
                         self._chk(L.md_dom_set_scale(h, scale))
                 s = g + 1
@@ -661,11 +665,12 @@ class DomainDevice:
                     self.build()
                     self.target_interval += 1
             self._pruning = pruning
-        return U, W, K
+        return (U, W, K) if thermo else None
 
-    def run(self, nsteps, dt, ensemble=_lib.MD_NVE, tau=0.0, nf=None, ktemp=None, r1=None, r2=None):
+    def run(self, nsteps, dt, ensemble=_lib.MD_NVE, tau=0.0, nf=None, ktemp=None, r1=None, r2=None, thermo=True):
         """The step loop of run_simulation! across the slabs; returns global (U, W, K) of the last step.
-        r1, r2, ktemp must be identical on every rank (draw them from one seeded stream)."""
+        r1, r2, ktemp must be identical on every rank (draw them from one seeded stream).  thermo=False: the last step
+        is no energy step either (the no-energy kernels; K is still all-reduced under NVT) and None is returned."""
         nf = float(self.dim * (self.n_global - 1.0)) if nf is None else float(nf)
         nvt = ensemble == _lib.MD_NVT
         uwk = (C.c_double * 3)()
@@ -676,6 +681,7 @@ class DomainDevice:
             self.build()
         for s in range(nsteps):
             last = s == nsteps - 1
+            want = last and thermo
             self._chk(self._L.md_dom_step_begin(self._h, float(dt), C.byref(viol)))
             # the violation flag is all-reduced while the halo coordinates travel (the exchange is harmless if
             # a rebuild follows: the build re-sends everything)
@@ -688,11 +694,11 @@ class DomainDevice:
                 observed = self.steps_since_build + 1
                 self.target_interval = max(2, (observed * 4) // 5)
                 self.build()
-                self._chk(self._L.md_dom_forces(self._h, float(dt), 1, 1 if last else 0, uwk))
+                self._chk(self._L.md_dom_forces(self._h, float(dt), 1, 1 if want else 0, uwk))
             else:
-                self._chk(self._L.md_dom_step_end(self._h, float(dt), 1 if last else 0, uwk))
+                self._chk(self._L.md_dom_step_end(self._h, float(dt), 1 if want else 0, uwk))
                 self.steps_since_build += 1
-            if nvt or last:
+            if nvt or want:
                 U, W, K = self.ex.allreduce([uwk[0], uwk[1], uwk[2]])
             if nvt:
                 scale = float(bussi_scale(K, ktemp[s], nf, dt, tau, r1[s], r2[s]))
@@ -704,4 +710,4 @@ class DomainDevice:
             if not last and not any_viol and self.steps_since_build >= self.target_interval:
                 self.build()
                 self.target_interval += 1
-        return U, W, K
+        return (U, W, K) if thermo else None

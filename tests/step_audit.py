@@ -36,6 +36,8 @@ only if the whole segment saw neither a prune nor a build ("unknown" otherwise).
 
 The Brownian loop and the FIRE minimiser have modes of their own, audit_brownian and audit_fire (with
 audit_fire_convergence), on the same ledger, knife edges and image exceptions: see the comment block above BD_MIXED.
+The slab-decomposed loops (DomainDevice.run / run_async / run_native) are audited by audit_run through a multi-process
+stepper, tests/domain_audit_worker.py.
 """
 import contextlib
 
