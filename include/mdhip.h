@@ -502,6 +502,56 @@ int md_cur_read(md_ctx *ctx, int64_t *nstatic, double *s_tot, double *s_long, in
                 double *c_long, double *z);
 int md_cur_reset(md_ctx *ctx);
 
+/* Marked pair correlations, sampled on the device: the spatial correlation of a per-particle field -- the orientational
+ * correlation g6(r) = <psi6(i) psi6*(j) delta(r - r_ij)> in 2-D, G_l(r) built from q_lm in 3-D, or any field the caller
+ * uploads (velocities, displacements, mobility: C_vv(r), the displacement correlations behind chi4).
+ *
+ * Definition.  Every particle carries NC real marks a_c(i); there are NC weights w_c.  For the unordered pair {i, j}
+ * p_c = a_c(i)*a_c(j) (one product: the same whichever particle is visited first) and t_ij is the chain
+ * acc = 0; for c = 0..NC-1: acc = fma(w_c, p_c, acc).  The pair's distance, periodic translation and bin are md_rdf's,
+ * operation for operation: d2 = (del0*del0 + del1*del1) + del2*del2 with the end of the larger particle id translated,
+ * bin k iff e2[k] <= d2 < e2[k+1] on the table e2[k] = (k*delta)^2, delta = r_max / nbins; every face distance must be
+ * >= 3*r_max.  The pair contributes the integer I_ij = llrint(t_ij * 2^31 / tmax); tmax is rounded up to a power of two
+ * by md_mpc_setup, so the scaling is exact.  Per bin and per sample the device forms cnt[k] (the number of pairs) and
+ * sum[k] = sum I_ij, and per sample self = sum_i I_ii.  These are integers: the result does not depend on the order in
+ * which the pairs are visited, the launch shape or what the handle did before -- given the frame and the marks it is a
+ * function of those alone.  The quantum is tmax * 2^-31; quantisation moves sum/cnt by at most tmax * 2^-32.
+ *
+ * range_error is sticky until md_mpc_setup or md_mpc_reset: bit 0 (1) -- a term with |t| > tmax*(1 + 2^-10), which
+ * contributes 0 to sum and 1 to cnt; bit 1 (2) -- a bin with cnt[k] >= 2^31 in one sample.  Nothing wraps silently: with
+ * both absent |sum[k]| < 2^63.
+ *
+ * Accumulated since setup or reset: acc_cnt[k] (integers), acc_sum[k] and acc_self (doubles: acc = acc + (double)sum,
+ * one conversion and one add per sample, in sample order) and nsamples.  The last sample's integers stay readable.
+ *
+ * Sources.  MD_MPC_BOO: the marks are the stored Re, Im of q_lm, m = 0..l, of the bond-order sampler's last frame (3-D:
+ * NC = 2(l+1) = 10 or 14; 2-D: psi_k, NC = 2), the weights 4pi/(2l+1) * {1, 1, 2, 2, ...} (2-D: {1, 1}) and tmax = 1,
+ * so t_ij = 4pi/(2l+1) * sum_{m=-l..l} q_lm(i) q_lm*(j) <= q_l(i) q_l(j) <= 1 and sum/cnt * 2^-31 is the conventional
+ * G_l(r) = g_l(r) / g(r).  nc, weights and tmax are ignored (pass 0, NULL, 0).  The marks are fetched by particle id, so a
+ * list rebuild between md_boo_sample and md_mpc_sample cannot attach them to other particles; that the frame belongs
+ * to the same step is the caller's business (as for md_cluster_sample with MD_CLUSTER_SOLID).  MD_MPC_USER: the marks
+ * marks[i*NC + c] in particle-id order, NC = 1..3, uploaded by md_mpc_marks (which waits) and kept until replaced; the
+ * caller gives weights[NC] and tmax.
+ *
+ * md_mpc_setup: 1 <= nbins <= 4096; everything zeroed; calling it again starts over (user marks included).
+ * md_mpc_sample adds one sample of the current positions on the handle's stream, does not wait and changes nothing the
+ * handle computes afterwards.  md_mpc_last waits and returns the last sample's cnt[nbins], sum[nbins] and self (any may
+ * be NULL).  md_mpc_read waits and returns nsamples, acc_cnt[nbins], acc_sum[nbins], acc_self, the tmax in use and
+ * range_error (any may be NULL).  md_mpc_reset zeroes the accumulators, nsamples, the last sample and range_error and
+ * keeps the setup and the user marks.  Refused: a slab-decomposition handle, any call before md_mpc_setup, a face
+ * distance < 3*r_max, nbins outside 1..4096, nc outside 1..3 (user source), a weight, mark or r_max that is not finite,
+ * tmax not finite or <= 0, MD_MPC_BOO before md_boo_setup (at setup) or before the first md_boo_sample (at sample),
+ * MD_MPC_USER sampled before md_mpc_marks, md_mpc_marks on an MD_MPC_BOO setup, md_mpc_last before the first sample. */
+#define MD_MPC_BOO  0
+#define MD_MPC_USER 1
+int md_mpc_setup(md_ctx *ctx, int source, double r_max, int nbins, int nc, const double *weights, double tmax);
+int md_mpc_marks(md_ctx *ctx, const double *marks);
+int md_mpc_sample(md_ctx *ctx);
+int md_mpc_last(md_ctx *ctx, int64_t *cnt, int64_t *sum, int64_t *self);
+int md_mpc_read(md_ctx *ctx, int64_t *nsamples, int64_t *acc_cnt, double *acc_sum, double *acc_self, double *tmax,
+                int32_t *range_error);
+int md_mpc_reset(md_ctx *ctx);
+
 /* compute_kinetic: src/thermostat.jl:50-60 */
 int md_kinetic(md_ctx *ctx, double *kinetic);
 

@@ -21,7 +21,7 @@ export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, Pseudo
        FourPoint, overlap, chi4, s4, s4_vectors, write_chi4, write_s4, chi4_last,
        StructureFactor, select_wave_vectors, compute_sq, sofq, fqt, fqt_normalised, write_sq, write_fqt,
        CurrentCorrelations, current_cl, current_ct, current_cl0, current_ct0, vacf, vacf0, write_currents, write_vacf,
-       cur_last
+       cur_last, mpc_setup!, mpc_marks!, mpc_sample!, mpc_reset!, mpc_last, mpc_read
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -1090,6 +1090,39 @@ function write_s4(path, fp::FourPoint; dt=fp.dt)
             end
         end
     end
+end
+
+# ---- marked pair correlations, sampled on the device (md_mpc_*; device.py's mpc_* calls) -----------------------------
+const MD_MPC_BOO, MD_MPC_USER = 0, 1
+"the bond-order sampler's last frame as marks (G_l(r), g6(r)): nc, weights and tmax come from its setup"
+function mpc_setup!(dev::Device, r_max, nbins::Integer)
+    check(dev, ccall((:md_mpc_setup, LIB), Cint, (Ptr{Cvoid}, Cint, Float64, Cint, Cint, Ptr{Float64}, Float64),
+                     dev.h, MD_MPC_BOO, r_max, nbins, 0, C_NULL, 0.0))
+end
+"user marks: length(weights) = NC in 1..3 components per particle, tmax >= |t| of every term (rounded up to a power of two)"
+function mpc_setup!(dev::Device, r_max, nbins::Integer, weights::Vector{Float64}, tmax)
+    check(dev, ccall((:md_mpc_setup, LIB), Cint, (Ptr{Cvoid}, Cint, Float64, Cint, Cint, Ptr{Float64}, Float64),
+                     dev.h, MD_MPC_USER, r_max, nbins, length(weights), weights, tmax))
+end
+"marks: NC x N (component c of particle i at [c, i]), in particle order; kept until replaced"
+mpc_marks!(dev::Device, marks::Matrix{Float64}) =
+    check(dev, ccall((:md_mpc_marks, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), dev.h, marks))
+mpc_sample!(dev::Device) = check(dev, ccall((:md_mpc_sample, LIB), Cint, (Ptr{Cvoid},), dev.h))
+mpc_reset!(dev::Device) = check(dev, ccall((:md_mpc_reset, LIB), Cint, (Ptr{Cvoid},), dev.h))
+"(cnt, sum, self) of the last sample: the integers of the exactness contract; waits"
+function mpc_last(dev::Device, nbins::Integer)
+    cnt = zeros(Int64, nbins); sum = zeros(Int64, nbins); self = Ref{Int64}(0)
+    check(dev, ccall((:md_mpc_last, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int64}), dev.h, cnt, sum, self))
+    return cnt, sum, self[]
+end
+"(nsamples, acc_cnt, acc_sum, acc_self, tmax, range_error) since setup / reset; sum * tmax * 2^-31 / cnt is the correlation"
+function mpc_read(dev::Device, nbins::Integer)
+    ns = Ref{Int64}(0); cnt = zeros(Int64, nbins); sum = zeros(nbins); self = Ref{Float64}(0.0)
+    tmax = Ref{Float64}(0.0); err = Ref{Int32}(0)
+    check(dev, ccall((:md_mpc_read, LIB), Cint,
+                     (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                     dev.h, ns, cnt, sum, self, tmax, err))
+    return ns[], cnt, sum, self[], tmax[], err[]
 end
 
 # ---- output: src/io.jl ---------------------------------------------------------------------------------------------

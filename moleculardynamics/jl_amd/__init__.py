@@ -10,7 +10,8 @@ from .initialization import (initialize_state, initialize_velocities, lattice_po
 from .simulation import run_simulation
 from .analysis import (RadialDistribution, compute_rdf, SelfDynamics, StructureFactor, compute_sq, select_wave_vectors,
                        StressTensor, compute_stress, BondOrder, compute_bond_order, ClusterAnalysis,
-                       compute_clusters, CageDynamics, FourPoint, CurrentCorrelations)
+                       compute_clusters, CageDynamics, FourPoint, CurrentCorrelations, OrientationalCorrelation,
+                       compute_orientational_correlation, compute_marked_correlation)
 from .minimize import fire_minimize, minimize
 from .device import MDDevice
 from ._lib import MdhipError
@@ -22,5 +23,6 @@ __all__ = [
     "fire_minimize", "minimize", "LennardJonesShifted", "LennardJonesForceShifted", "LennardJonesXPLOR",
     "RadialDistribution", "compute_rdf", "SelfDynamics", "StructureFactor", "compute_sq", "select_wave_vectors",
     "StressTensor", "compute_stress", "BondOrder", "compute_bond_order", "ClusterAnalysis", "compute_clusters", "CageDynamics",
-    "FourPoint", "CurrentCorrelations",
+    "FourPoint", "CurrentCorrelations", "OrientationalCorrelation", "compute_orientational_correlation",
+    "compute_marked_correlation",
 ]

@@ -12,6 +12,7 @@ SO_PATH = os.path.join(_HERE, "csrc", "libmdhip.so")
 MD_POT_LJ, MD_POT_PSEUDOHS, MD_POT_POLYDISPERSE, MD_POT_LJ_MODIFIED, MD_POT_CUSTOM = 0, 1, 2, 3, 100
 MD_NVE, MD_NVT = 0, 1
 MD_CLUSTER_ALL, MD_CLUSTER_SOLID = 0, 1
+MD_MPC_BOO, MD_MPC_USER = 0, 1
 
 # every symbol include/mdhip.h declares
 EXPORTS = [
@@ -34,6 +35,7 @@ EXPORTS = [
     "md_cage_setup", "md_cage_origin", "md_cage_sample", "md_cage_particles", "md_cage_read", "md_cage_reset",
     "md_chi4_setup", "md_chi4_origin", "md_chi4_sample", "md_chi4_last", "md_chi4_read", "md_chi4_reset",
     "md_cur_setup", "md_cur_sample", "md_cur_last", "md_cur_read", "md_cur_reset",
+    "md_mpc_setup", "md_mpc_marks", "md_mpc_sample", "md_mpc_last", "md_mpc_read", "md_mpc_reset",
 ]
 
 
@@ -236,6 +238,18 @@ def load():
     L.md_cur_read.restype = C.c_int
     L.md_cur_reset.argtypes = [vp]
     L.md_cur_reset.restype = C.c_int
+    L.md_mpc_setup.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, dp, C.c_double]
+    L.md_mpc_setup.restype = C.c_int
+    L.md_mpc_marks.argtypes = [vp, dp]
+    L.md_mpc_marks.restype = C.c_int
+    L.md_mpc_sample.argtypes = [vp]
+    L.md_mpc_sample.restype = C.c_int
+    L.md_mpc_last.argtypes = [vp, i64p, i64p, i64p]
+    L.md_mpc_last.restype = C.c_int
+    L.md_mpc_read.argtypes = [vp, i64p, i64p, dp, dp, dp, ip]
+    L.md_mpc_read.restype = C.c_int
+    L.md_mpc_reset.argtypes = [vp]
+    L.md_mpc_reset.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

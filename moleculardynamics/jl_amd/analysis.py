@@ -4,7 +4,8 @@ the self dynamics (MSD, F_s(q, t), van Hove), the collective side (density modes
 neighbour-averaged qbar_l, psi_k in 2-D, the solid-particle count) and the clusters (connected components of the bond
 graph: sizes, the size distribution, the largest -- solid -- cluster), the cage-relative dynamics (displacements
 relative to the origin neighbours' mean, the bond-breaking correlation C_B), the four-point functions of the self
-overlap (chi4(t), S4(q, t)) and the currents (C_L(q, t), C_T(q, t), the velocity autocorrelation).
+overlap (chi4(t), S4(q, t)), the currents (C_L(q, t), C_T(q, t), the velocity autocorrelation) and the marked pair
+correlations (the orientational correlation g6(r) / G_l(r), the spatial correlation of any per-particle field).
 
 The pair histogram itself is accumulated by libmdhip (md_rdf_*: integer counts, exact and independent of the order the
 pairs are visited in); this module keeps the samples, normalises them and writes them out.
@@ -19,7 +20,8 @@ import numpy as np
 # ---------------------------------------------------------------------------------------------------------------------
 # The sampler protocol.  run_simulation drives every sampler class of this module through four private methods:
 #   _begin(dev, run)            set the sampler up on the device and derive what it needs for this run; `run` carries
-#                               total_steps, frequency, n, dim, dt, unitcell and brownian
+#                               total_steps, frequency, n, dim, dt, unitcell, brownian and bond_order (the run's
+#                               BondOrder or None)
 #   _next(step)                 the first step >= `step` at which the sampler acts in this run, or None
 #   _act(dev, step)             the device calls of that step
 #   _finish(dev, run, pathname) read back, accumulate into the object, write the files
@@ -1612,3 +1614,188 @@ class FourPoint(_Scheduled, _WaveVectors):
         self.write(os.path.join(pathname, "chi4.txt"))
         if self.sum_s4 is not None:
             self.write_s4(os.path.join(pathname, "s4.txt"))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Marked pair correlations, sampled on the device (md_mpc_*): the orientational correlation function -- g6(r) of psi_6
+# in 2-D, whose decay (exponential, algebraic, constant) tells the liquid, the hexatic and the solid apart, G_l(r) of
+# q_lm in 3-D -- and the spatial correlation of any per-particle field.  The device accumulates integers (pair counts
+# and sums of terms quantised to tmax 2^-31), so a sample is a function of the frame and the marks alone.
+
+def _pair_density(counts, nsamples, n_particles, volume, edges, dimension):
+    """RadialDistribution.g's normalisation: counts / (nsamples N (N - 1) / (2 V) V_k)."""
+    if nsamples == 0 or n_particles < 2:
+        return np.zeros(len(counts))
+    ideal = nsamples * n_particles * (n_particles - 1.0) / (2.0 * volume) * shell_volumes(edges, dimension)
+    return counts / ideal
+
+
+def _per_pair(sums, counts, quantum):
+    """sums * quantum / counts, nan where a bin is empty."""
+    out = np.full(len(counts), np.nan)
+    np.divide(np.asarray(sums, dtype=np.float64) * quantum, counts, out=out, where=np.asarray(counts) > 0)
+    return out
+
+
+class OrientationalCorrelation:
+    """The orientational correlation function of the bond-order sampler's marks on `nbins` bins of width r_max / nbins,
+    accumulated on the device until reset(): G(r) = <t_ij>_r with t_ij = 4 pi / (2l + 1) sum_m q_lm(i) q_lm*(j) in 3-D and
+    Re psi_k(i) psi_k*(j) in 2-D, averaged over the pairs at distance r; g(r); and g_l(r) = G(r) g(r).
+
+    Passed to run_simulation(..., bond_order=..., orientational=...), it takes a sample at every `every`-th output step,
+    after the bond-order sample of the same step: `every` must be a multiple of bond_order.every.
+
+    Fields: edges, r (bin centres), counts (pairs per bin, summed over the samples), sums (the device's acc_sum: the
+    integer terms, one double add per sample), self_sum (sum over samples of sum_i I_ii), tmax, nsamples, order, r_neigh."""
+
+    def __init__(self, r_max, nbins, every=1):
+        r_max = float(r_max)
+        if not (r_max > 0.0 and math.isfinite(r_max)):
+            raise ValueError("r_max must be finite and > 0")
+        if int(nbins) != nbins or not 1 <= int(nbins) <= 4096:
+            raise ValueError("nbins must be in 1..4096")
+        if int(every) != every or int(every) < 1:
+            raise ValueError("every must be a positive integer")
+        self.r_max, self.nbins, self.every = r_max, int(nbins), int(every)
+        self.edges = np.arange(self.nbins + 1, dtype=np.float64) * (r_max / self.nbins)
+        self.r = 0.5 * (self.edges[:-1] + self.edges[1:])
+        self.order, self.r_neigh, self.tmax = 0, 0.0, 1.0
+        self.n_particles, self.volume, self.dimension = 0, 0.0, 3
+        self.reset()
+
+    def reset(self):
+        self.counts = np.zeros(self.nbins, dtype=np.int64)
+        self.sums = np.zeros(self.nbins)
+        self.self_sum = 0.0
+        self.nsamples = 0
+
+    def _accumulate(self, nsamples, counts, sums, self_sum, tmax, n_particles, unitcell, order, r_neigh):
+        if self.nsamples > 0 and float(tmax) != self.tmax:
+            raise ValueError("tmax differs from the one already accumulated; reset() first")
+        self.nsamples += int(nsamples)
+        self.counts += np.asarray(counts, dtype=np.int64).reshape(self.nbins)
+        self.sums += np.asarray(sums, dtype=np.float64).reshape(self.nbins)
+        self.self_sum += float(self_sum)
+        u = np.asarray(unitcell, dtype=np.float64)
+        self.tmax, self.n_particles, self.volume, self.dimension = float(tmax), int(n_particles), abs(float(np.linalg.det(u))), u.shape[0]
+        self.order, self.r_neigh = int(order), float(r_neigh)
+
+    # -- results ----------------------------------------------------------------------------------------------------
+    @property
+    def quantum(self):
+        """The value of one unit of `sums`: tmax 2^-31."""
+        return self.tmax * 2.0 ** -31
+
+    def g(self):
+        """The radial distribution function of the same pairs."""
+        return _pair_density(self.counts, self.nsamples, self.n_particles, self.volume, self.edges, self.dimension)
+
+    def G(self):
+        """G(r): the mean of t_ij over the pairs of a bin (nan for an empty bin); 1 in a perfect crystal."""
+        return _per_pair(self.sums, self.counts, self.quantum)
+
+    def g_l(self):
+        """g_l(r) = G(r) g(r) (g6(r) for k = 6 in 2-D); 0 for an empty bin."""
+        return np.where(self.counts > 0, np.nan_to_num(self.G()) * self.g(), 0.0)
+
+    def mean_self(self):
+        """<t_ii>: <q_l(i)^2> in 3-D, <|psi_k(i)|^2> in 2-D, over particles and samples."""
+        if self.nsamples == 0 or self.n_particles == 0:
+            raise ValueError("no sample yet")
+        return self.self_sum * self.quantum / (self.nsamples * self.n_particles)
+
+    def write(self, path):
+        """A header naming the order, then # r_mid count g(r) G(r) g_l(r), one row per bin; the last line is <t_ii>."""
+        g, G, gl = self.g(), self.G(), self.g_l()
+        with open(path, "w") as io:
+            io.write("# %s %d r_neigh %.6f tmax %.6g nsamples %d\n"
+                     % ("l" if self.dimension == 3 else "k", self.order, self.r_neigh, self.tmax, self.nsamples))
+            io.write("# r_mid count g(r) G(r) g_l(r)\n")
+            for k in range(self.nbins):
+                io.write("%.6f %d %.6f %.8f %.8f\n" % (self.r[k], self.counts[k], g[k], G[k], gl[k]))
+            io.write("# <t_ii> %.8f\n" % self.mean_self())
+
+    # -- run_simulation's sampler protocol: a sample at every `every`-th output step, after bond_order's ----------------
+    def _begin(self, dev, run):
+        bo = getattr(run, "bond_order", None)
+        if bo is None:
+            raise ValueError("orientational= needs bond_order= in the same run: its marks are the bond-order frame's")
+        if self.every % bo.every != 0:
+            raise ValueError("orientational.every must be a multiple of bond_order.every: every sample needs the "
+                             "bond-order sample of its step")
+        self._period, self._total_steps = run.frequency * self.every, run.total_steps
+        self._order, self._r_neigh = bo.order, bo.r_neigh
+        dev.mpc_setup(self.r_max, self.nbins)
+
+    def _next(self, step):
+        return _next_multiple(step, self._period, self._total_steps)
+
+    def _act(self, dev, step):
+        dev.mpc_sample()
+
+    def _finish(self, dev, run, pathname):
+        ns, cnt, sums, own, tmax, err = dev.mpc_read()
+        if err:
+            raise RuntimeError("the orientational correlation sampler reports range_error = %d (1: a term beyond tmax, "
+                               "2: a bin with 2^31 pairs in one sample)" % err)
+        self._accumulate(ns, cnt, sums, own, tmax, run.n, run.unitcell, self._order, self._r_neigh)
+        if self.nsamples > 0:
+            self.write(os.path.join(pathname, "orient_corr.txt"))
+
+
+def compute_orientational_correlation(state, params, r_neigh, order, r_max, nbins):
+    """One sample of the orientational correlation of `state`'s positions, taken on its device handle (any potential):
+    the bond order within r_neigh (l in 3-D, k in 2-D) first, then the pair walk out to r_max on the same frame; returns
+    an OrientationalCorrelation."""
+    from .simulation import _configure_device
+    BondOrder(r_neigh, order=order)                         # the argument checks
+    oc = OrientationalCorrelation(r_max, nbins)
+    dev = _configure_device(state, params)
+    dev.upload(x=state.system.positions, images=state.images, diameters=state.diameters)
+    dev.boo_setup(r_neigh, order, 1, 0.7, 7, 0)
+    dev.boo_sample()
+    dev.mpc_setup(oc.r_max, oc.nbins)
+    dev.mpc_sample()
+    ns, cnt, sums, own, tmax, err = dev.mpc_read()
+    if err:
+        raise RuntimeError("range_error = %d" % err)
+    oc._accumulate(ns, cnt, sums, own, tmax, dev.n, state.unitcell, order, r_neigh)
+    return oc
+
+
+def default_tmax(marks, weights):
+    """The next power of two >= sum_c |w_c| max_i |a_c(i)|^2 (1 when every mark is zero): no term can exceed it."""
+    m = np.abs(np.asarray(marks, dtype=np.float64))
+    bound = float(np.dot(np.abs(np.asarray(weights, dtype=np.float64)), m.max(axis=0) ** 2)) if m.size else 0.0
+    if not math.isfinite(bound):
+        raise ValueError("marks and weights must be finite")
+    return 2.0 ** math.ceil(math.log2(bound)) if bound > 0.0 else 1.0
+
+
+def compute_marked_correlation(state, params, marks, r_max, nbins, weights=None, tmax=None):
+    """One sample of the spatial correlation of the per-particle field `marks` (N, or N x NC with NC <= 3, in particle
+    order) over `state`'s positions, taken on its device handle: the pair {i, j} contributes t_ij = sum_c weights[c]
+    a_c(i) a_c(j) (weights default to 1) to its distance bin.  tmax bounds |t_ij| (default: default_tmax).  Returns a dict:
+    r, edges, count (pairs per bin), sum (the integer terms per bin), self (sum_i I_ii), tmax, quantum (tmax 2^-31), C
+    (sum quantum / count, nan for an empty bin: C_vv(r) for velocities), g (the radial distribution of the same pairs)."""
+    m = np.ascontiguousarray(marks, dtype=np.float64)
+    m = m.reshape(len(m), -1)
+    w = np.ones(m.shape[1]) if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != m.shape[1]:
+        raise ValueError("one weight per mark component")
+    tmax = default_tmax(m, w) if tmax is None else float(tmax)
+    dev = state.system.device
+    dev.upload(x=state.system.positions, images=state.images)
+    dev.mpc_setup(r_max, nbins, weights=w, tmax=tmax)
+    dev.mpc_marks(m)
+    dev.mpc_sample()
+    cnt, tot, own = dev.mpc_last()
+    _, _, _, _, tmax, err = dev.mpc_read()
+    if err:
+        raise RuntimeError("range_error = %d: a term exceeds tmax = %g" % (err, tmax))
+    edges = np.arange(int(nbins) + 1, dtype=np.float64) * (float(r_max) / int(nbins))
+    u = np.asarray(state.unitcell, dtype=np.float64)
+    quantum = tmax * 2.0 ** -31
+    return dict(r=0.5 * (edges[:-1] + edges[1:]), edges=edges, count=cnt, sum=tot, self=own, tmax=tmax, quantum=quantum,
+                C=_per_pair(tot, cnt, quantum),
+                g=_pair_density(cnt, 1, dev.n, abs(float(np.linalg.det(u))), edges, u.shape[0]))

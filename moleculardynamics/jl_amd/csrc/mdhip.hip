@@ -15,6 +15,7 @@
 #include "md_sq.hpp"
 #include "md_stress.hpp"
 #include "md_boo.hpp"
+#include "md_mpc.hpp"
 #include "md_cluster.hpp"
 #include "md_cage.hpp"
 #include "md_chi4.hpp"
@@ -506,6 +507,29 @@ struct md_ctx {
         DBuf<double> part, jl, s_tot, s_long, c_tot, c_long, org; // (vector, a, part, block); nvec x dim x 2; nvec; nvec; nrows x nvec (2); nslots x nvec x dim x 2
         DBuf<double> ov, zpart, z;        // nslots frames of n x dim velocities; batch x zblk; nrows + 1
     } current;
+
+    // marked pair correlations (md_mpc_*): a grid and sort scratch of its own (not the rdf sampler's: both can be set up
+    // at once), the marks by particle id (user source) and in sorted order, the inverse of the bond-order frame's
+    // permutation (boo source); the per-sample words, the last sample, the accumulators, the sticky error bits
+    struct Mpc {
+        bool on = false;
+        bool sampled = false;             // last_* hold a sample
+        bool have_marks = false;          // user source: md_mpc_marks has been called
+        int source = 0, nc = 0, nbins = 0;
+        double r_max = 0.0, tmax = 0.0;
+        MpcWeights w{};
+        RdfGrid grid{};
+        int64_t nsamples = 0;
+        DBuf<double> e2, marks, smarks;   // nbins + 1; n x nc by id; n x nc in sorted order
+        DBuf<int32_t> inv;                // n
+        DBuf<double4> wrec, srec;
+        DBuf<uint32_t> keys_in, keys_out, vals_in, vals_out;
+        DBuf<int32_t> cell_start, cell_end, work, range_error;
+        DBuf<char> sort_tmp;
+        DBuf<unsigned long long> cur_cnt, last_cnt, acc_cnt; // nbins each
+        DBuf<long long> cur_sum, last_sum, self;  // nbins; nbins; {cur, last}
+        DBuf<double> acc_sum, acc_self;   // nbins; 1
+    } mpc;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -1687,6 +1711,81 @@ void boo_zero(md_ctx *c)
     B.nsamples = 0;
 }
 
+// ---- marked pair correlations (md_mpc.hpp): launches ----------------------------------------------------------------
+template <int D, int NC>
+void mpc_set_lds(size_t lds)
+{
+    HIPCHK(hipFuncSetAttribute((const void *)k_mpc_hist<D, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+}
+
+template <int D, int NC>
+void mpc_launch(md_ctx *ctx, const double *src, const int32_t *inv, size_t stride_i, size_t stride_c, size_t lds)
+{
+    md_ctx::Mpc &M = ctx->mpc;
+    const int n = (int)ctx->n;
+    const RdfGrid &g = M.grid;
+    hipStream_t st = ctx->stream;
+    k_mpc_gather<NC><<<nblocks(n), MD_BLOCK, 0, st>>>(n, M.keys_out.p, M.vals_out.p, M.wrec.p, src, inv, stride_i, stride_c,
+                                                      M.w, M.srec.p, M.smarks.p, M.cell_start.p, M.cell_end.p, M.self.p,
+                                                      M.range_error.p);
+    HIPCHK(hipGetLastError());
+    // one wave per home cell at a time, cells handed out by the work counter; the grid only needs to fill the chip
+    const int waves_per_block = MD_RDF_BLOCK / 64;
+    const int nblk = (int)std::min<int64_t>((g.ncell + waves_per_block - 1) / waves_per_block, 1024);
+    const float inv_delta = (float)(M.nbins / M.r_max);
+    k_mpc_hist<D, NC><<<nblk, MD_RDF_BLOCK, lds, st>>>(g, M.nbins, inv_delta, M.w, M.e2.p, M.srec.p, M.smarks.p,
+                                                       M.cell_start.p, M.cell_end.p, M.work.p, M.cur_cnt.p,
+                                                       (unsigned long long *)M.cur_sum.p, M.range_error.p);
+    HIPCHK(hipGetLastError());
+}
+
+// the instantiations: D = 2 with NC in {1, 2, 3}; D = 3 with NC in {1, 2, 3, 10, 14}
+template <class F2, class F3>
+void mpc_dispatch(int dim, int nc, F2 &&two, F3 &&three)
+{
+    if (dim == 2) {
+        switch (nc) {
+        case 1: two(std::integral_constant<int, 1>{}); return;
+        case 2: two(std::integral_constant<int, 2>{}); return;
+        case 3: two(std::integral_constant<int, 3>{}); return;
+        }
+    } else {
+        switch (nc) {
+        case 1: three(std::integral_constant<int, 1>{}); return;
+        case 2: three(std::integral_constant<int, 2>{}); return;
+        case 3: three(std::integral_constant<int, 3>{}); return;
+        case 10: three(std::integral_constant<int, 10>{}); return;
+        case 14: three(std::integral_constant<int, 14>{}); return;
+        }
+    }
+    throw HipError("md_mpc: no kernel for this dimension and number of mark components");
+}
+
+size_t mpc_lds_bytes(int nbins, int nc)
+{
+    return sizeof(double) * (size_t)(MD_RDF_BLOCK * nc + MD_MPC_MAX_NC + 2) + sizeof(double) * (nbins + 1) + sizeof(uint32_t) * nbins +
+           sizeof(long long) * nbins;
+}
+
+void mpc_zero(md_ctx *c)
+{
+    md_ctx::Mpc &M = c->mpc;
+    hipStream_t st = c->stream;
+    const size_t nb = (size_t)M.nbins;
+    HIPCHK(hipMemsetAsync(M.cur_cnt.p, 0, sizeof(unsigned long long) * nb, st));
+    HIPCHK(hipMemsetAsync(M.cur_sum.p, 0, sizeof(long long) * nb, st));
+    HIPCHK(hipMemsetAsync(M.last_cnt.p, 0, sizeof(unsigned long long) * nb, st));
+    HIPCHK(hipMemsetAsync(M.last_sum.p, 0, sizeof(long long) * nb, st));
+    HIPCHK(hipMemsetAsync(M.acc_cnt.p, 0, sizeof(unsigned long long) * nb, st));
+    HIPCHK(hipMemsetAsync(M.acc_sum.p, 0, sizeof(double) * nb, st));
+    HIPCHK(hipMemsetAsync(M.self.p, 0, sizeof(long long) * 2, st));
+    HIPCHK(hipMemsetAsync(M.acc_self.p, 0, sizeof(double), st));
+    HIPCHK(hipMemsetAsync(M.range_error.p, 0, sizeof(int32_t), st));
+    HIPCHK(hipStreamSynchronize(st));
+    M.nsamples = 0;
+    M.sampled = false;
+}
+
 // ---- cluster sampler (md_cluster.hpp): launches -------------------------------------------------------------------
 template <int D>
 void launch_cluster(md_ctx *c)
@@ -2487,28 +2586,23 @@ static void export_frame(md_ctx *ctx, double *x, int32_t *im, double *v = nullpt
 // ---------------------------------------------------------------------------------------------
 // Radial distribution function (md_rdf.hpp): a sample reads the state and writes only the rdf scratch, so the step
 // loop, the list and the cell order are exactly what they would have been without it.
-int md_rdf_setup(md_ctx *ctx, double r_max, int nbins)
+// The cell grid of a pair walk out to r_max (md_rdf_*, md_mpc_*), after the face-distance rule: cells at least r_max
+// wide between their faces (fractional cut, as configure_grid does for the list), at least 3 per direction (every pair
+// within r_max is then visited once, with its minimum image); no more cells than about two per particle -- wider cells
+// are still correct, only the walk grows.
+static RdfGrid pair_walk_grid(md_ctx *ctx, const char *who, double r_max)
 {
-    API_BEGIN
-    if (ctx->dom.on) throw HipError("md_rdf_setup: not available on a slab-decomposition handle");
-    if (!(r_max > 0.0) || !std::isfinite(r_max)) throw HipError("md_rdf_setup: r_max must be finite and > 0");
-    check_range("md_rdf_setup", "nbins", nbins, 1, MD_RDF_MAX_BINS);
     for (int c = 0; c < ctx->dim; ++c)
         if (ctx->perp[c] < 3.0 * r_max) {
             char b[320];
             snprintf(b, sizeof b,
-                     "md_rdf_setup: r_max = %.17g is too large: the face distance %.17g of lattice direction %d must be "
+                     "%s: r_max = %.17g is too large: the face distance %.17g of lattice direction %d must be "
                      ">= 3*r_max (limit r_max <= %.17g)",
-                     r_max, ctx->perp[c], c, ctx->perp[c] / 3.0);
+                     who, r_max, ctx->perp[c], c, ctx->perp[c] / 3.0);
             throw HipError(b);
         }
-    md_ctx::Rdf &R = ctx->rdf;
-    R.on = false;
-    RdfGrid &g = R.grid;
+    RdfGrid g{};
     const int64_t n = ctx->n;
-    // cells at least r_max wide between their faces (fractional cut, as configure_grid does for the list), at least 3
-    // per direction (every pair within r_max is then visited once, with its minimum image); no more cells than about
-    // two per particle -- wider cells are still correct, only the walk grows
     for (int c = 0; c < 3; ++c) {
         g.nc[c] = 1;
         if (c >= ctx->dim) continue;
@@ -2530,6 +2624,21 @@ int md_rdf_setup(md_ctx *ctx, double r_max, int nbins)
         g.A[c] = ctx->A[c];
         g.Ainv[c] = ctx->Ainv[c];
     }
+    return g;
+}
+
+int md_rdf_setup(md_ctx *ctx, double r_max, int nbins)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_rdf_setup: not available on a slab-decomposition handle");
+    if (!(r_max > 0.0) || !std::isfinite(r_max)) throw HipError("md_rdf_setup: r_max must be finite and > 0");
+    check_range("md_rdf_setup", "nbins", nbins, 1, MD_RDF_MAX_BINS);
+    const RdfGrid grid = pair_walk_grid(ctx, "md_rdf_setup", r_max);
+    md_ctx::Rdf &R = ctx->rdf;
+    R.on = false;
+    RdfGrid &g = R.grid;
+    g = grid;
+    const int64_t n = ctx->n;
     const std::vector<double> e2 = squared_edges(r_max, nbins);
     hipStream_t st = ctx->stream;
     R.e2.alloc(nbins + 1);
@@ -3700,6 +3809,194 @@ int md_cur_reset(md_ctx *ctx)
     API_BEGIN
     sampler_of(ctx, &md_ctx::current, "md_cur_reset", "cur");
     cur_zero(ctx);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Marked pair correlations (md_mpc.hpp): md_rdf_sample's pipeline on buffers of its own with a mark carried along; a
+// sample reads the state, the marks and -- MD_MPC_BOO -- the bond-order sampler's last frame, and writes only the
+// sampler's own buffers.
+int md_mpc_setup(md_ctx *ctx, int source, double r_max, int nbins, int nc, const double *weights, double tmax)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_mpc_setup: not available on a slab-decomposition handle");
+    if (source != MD_MPC_BOO && source != MD_MPC_USER) throw HipError("md_mpc_setup: source must be MD_MPC_BOO or MD_MPC_USER");
+    if (!(r_max > 0.0) || !std::isfinite(r_max)) throw HipError("md_mpc_setup: r_max must be finite and > 0");
+    check_range("md_mpc_setup", "nbins", nbins, 1, MD_MPC_MAX_BINS);
+    MpcWeights W{};
+    if (source == MD_MPC_BOO) {
+        const md_ctx::Boo &B = ctx->boo;
+        if (!B.on) throw HipError("md_mpc_setup: MD_MPC_BOO needs the bond-order sampler (call md_boo_setup first)");
+        // t_ij = pref (Re q_0 q_0' + Im q_0 q_0' + 2 sum_{m>0} ...) <= q_l(i) q_l(j) <= 1
+        nc = 2 * B.nm;
+        for (int c = 0; c < nc; ++c) W.w[c] = B.coef.pref * (c < 2 ? 1.0 : 2.0);
+        tmax = 1.0;
+    } else {
+        check_range("md_mpc_setup", "nc", nc, 1, 3);
+        if (!weights) throw HipError("md_mpc_setup: weights is null");
+        for (int c = 0; c < nc; ++c) {
+            if (!std::isfinite(weights[c])) throw HipError("md_mpc_setup: every weight must be finite");
+            W.w[c] = weights[c];
+        }
+        if (!(tmax > 0.0) || !std::isfinite(tmax)) throw HipError("md_mpc_setup: tmax must be finite and > 0");
+        // rounded up to a power of two: the scaling by 2^31 / tmax is then exact
+        int ex = 0;
+        const double mant = std::frexp(tmax, &ex); // tmax = mant 2^ex, mant in [0.5, 1)
+        if (mant != 0.5) tmax = std::ldexp(1.0, ex);
+        if (ex < -900 || ex > 900) throw HipError("md_mpc_setup: tmax must be in 2^-900..2^900");
+    }
+    W.scale = 2147483648.0 / tmax;
+    W.lim = tmax * (1.0 + 1.0 / 1024.0);
+    const RdfGrid grid = pair_walk_grid(ctx, "md_mpc_setup", r_max);
+    md_ctx::Mpc &M = ctx->mpc;
+    M.on = false;
+    M.have_marks = false;
+    M.source = source;
+    M.nc = nc;
+    M.nbins = nbins;
+    M.r_max = r_max;
+    M.tmax = tmax;
+    M.w = W;
+    M.grid = grid;
+    const size_t lds = mpc_lds_bytes(nbins, nc);
+    mpc_dispatch(ctx->dim, nc, [&](auto k) { mpc_set_lds<2, decltype(k)::value>(lds); },
+                 [&](auto k) { mpc_set_lds<3, decltype(k)::value>(lds); });
+    const size_t n = (size_t)ctx->n;
+    const std::vector<double> e2 = squared_edges(r_max, nbins);
+    hipStream_t st = ctx->stream;
+    M.e2.alloc(nbins + 1);
+    M.marks.alloc(source == MD_MPC_USER ? n * nc : 1);
+    M.smarks.alloc(n * nc);
+    M.inv.alloc(source == MD_MPC_BOO ? n : 1);
+    M.wrec.alloc(n);
+    M.srec.alloc(n);
+    M.keys_in.alloc(n);
+    M.keys_out.alloc(n);
+    M.vals_in.alloc(n);
+    M.vals_out.alloc(n);
+    M.cell_start.alloc((size_t)grid.ncell + 1);
+    M.cell_end.alloc((size_t)grid.ncell + 1);
+    M.work.alloc(1);
+    M.range_error.alloc(1);
+    M.cur_cnt.alloc(nbins);
+    M.last_cnt.alloc(nbins);
+    M.acc_cnt.alloc(nbins);
+    M.cur_sum.alloc(nbins);
+    M.last_sum.alloc(nbins);
+    M.self.alloc(2);
+    M.acc_sum.alloc(nbins);
+    M.acc_self.alloc(1);
+    size_t tmp_bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, M.keys_in.p, M.keys_out.p, M.vals_in.p, M.vals_out.p, n, 0u,
+                                     (unsigned)std::max(1, ceil_log2((uint64_t)grid.ncell)), st));
+    M.sort_tmp.alloc(tmp_bytes);
+    HIPCHK(hipMemcpyAsync(M.e2.p, e2.data(), sizeof(double) * (nbins + 1), hipMemcpyHostToDevice, st));
+    mpc_zero(ctx); // (waits: the edge table is a host vector)
+    M.on = true;
+    API_END
+}
+
+int md_mpc_marks(md_ctx *ctx, const double *marks)
+{
+    API_BEGIN
+    md_ctx::Mpc &M = sampler_of(ctx, &md_ctx::mpc, "md_mpc_marks", "mpc");
+    if (M.source != MD_MPC_USER) throw HipError("md_mpc_marks: the marks of an MD_MPC_BOO setup are the bond-order frame's");
+    if (!marks) throw HipError("md_mpc_marks: marks is null");
+    const size_t count = (size_t)ctx->n * M.nc;
+    for (size_t i = 0; i < count; ++i)
+        if (!std::isfinite(marks[i])) throw HipError("md_mpc_marks: every mark must be finite");
+    HIPCHK(hipMemcpyAsync(M.marks.p, marks, sizeof(double) * count, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream)); // (the caller's array)
+    M.have_marks = true;
+    API_END
+}
+
+int md_mpc_sample(md_ctx *ctx)
+{
+    API_BEGIN
+    require_state(ctx, "md_mpc_sample");
+    md_ctx::Mpc &M = sampler_of(ctx, &md_ctx::mpc, "md_mpc_sample", "mpc");
+    const md_ctx::Boo &B = ctx->boo;
+    const bool boo = M.source == MD_MPC_BOO;
+    if (boo) {
+        if (!(B.on && B.sampled)) throw HipError("md_mpc_sample: MD_MPC_BOO needs a bond-order frame (call md_boo_sample first)");
+        if (2 * B.nm != M.nc)
+            throw HipError("md_mpc_sample: the bond-order setup changed since md_mpc_setup (call md_mpc_setup again)");
+    } else if (!M.have_marks) {
+        throw HipError("md_mpc_sample: no marks yet (call md_mpc_marks first)");
+    }
+    const int n = (int)ctx->n;
+    const RdfGrid &g = M.grid;
+    hipStream_t st = ctx->stream;
+    DevState s = ctx->dev(ctx->cur);
+    if (ctx->dim == 3)
+        k_rdf_key<3><<<nblocks(n), MD_BLOCK, 0, st>>>(n, s, ctx->grid, g, M.wrec.p, M.keys_in.p, M.vals_in.p);
+    else
+        k_rdf_key<2><<<nblocks(n), MD_BLOCK, 0, st>>>(n, s, ctx->grid, g, M.wrec.p, M.keys_in.p, M.vals_in.p);
+    HIPCHK(hipGetLastError());
+    size_t tmp_bytes = M.sort_tmp.n;
+    HIPCHK(rocprim::radix_sort_pairs(M.sort_tmp.p, tmp_bytes, M.keys_in.p, M.keys_out.p, M.vals_in.p, M.vals_out.p,
+                                     (size_t)n, 0u, (unsigned)std::max(1, ceil_log2((uint64_t)g.ncell)), st));
+    HIPCHK(hipMemsetAsync(M.cell_start.p, 0, sizeof(int32_t) * (g.ncell + 1), st));
+    HIPCHK(hipMemsetAsync(M.cell_end.p, 0, sizeof(int32_t) * (g.ncell + 1), st));
+    HIPCHK(hipMemsetAsync(M.work.p, 0, sizeof(int32_t), st));
+    if (boo) {
+        // marks travel by particle id: whatever re-sorted the handle's slots since md_boo_sample does not matter
+        k_mpc_inv<<<nblocks(n), MD_BLOCK, 0, st>>>(n, B.ids.p, M.inv.p);
+        HIPCHK(hipGetLastError());
+    }
+    const double *src = boo ? B.qlm.p : M.marks.p;
+    const int32_t *inv = boo ? M.inv.p : nullptr;
+    const size_t stride_i = boo ? 1 : (size_t)M.nc, stride_c = boo ? (size_t)n : 1;
+    const size_t lds = mpc_lds_bytes(M.nbins, M.nc);
+    mpc_dispatch(ctx->dim, M.nc,
+                 [&](auto k) { mpc_launch<2, decltype(k)::value>(ctx, src, inv, stride_i, stride_c, lds); },
+                 [&](auto k) { mpc_launch<3, decltype(k)::value>(ctx, src, inv, stride_i, stride_c, lds); });
+    k_mpc_finish<<<nblocks(M.nbins), MD_BLOCK, 0, st>>>(M.nbins, M.cur_cnt.p, M.cur_sum.p, M.self.p, M.last_cnt.p,
+                                                        M.last_sum.p, M.self.p + 1, M.acc_cnt.p, M.acc_sum.p,
+                                                        M.acc_self.p, M.range_error.p);
+    HIPCHK(hipGetLastError());
+    ++M.nsamples;
+    M.sampled = true;
+    API_END
+}
+
+int md_mpc_last(md_ctx *ctx, int64_t *cnt, int64_t *sum, int64_t *self)
+{
+    API_BEGIN
+    md_ctx::Mpc &M = sampler_of(ctx, &md_ctx::mpc, "md_mpc_last", "mpc");
+    if (!M.sampled) throw HipError("md_mpc_last: no sample yet (call md_mpc_sample first)");
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t) && sizeof(long long) == sizeof(int64_t),
+                  "the device words are read back as int64_t");
+    hipStream_t st = ctx->stream;
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, M.last_cnt.p, sizeof(int64_t) * M.nbins, hipMemcpyDeviceToHost, st));
+    if (sum) HIPCHK(hipMemcpyAsync(sum, M.last_sum.p, sizeof(int64_t) * M.nbins, hipMemcpyDeviceToHost, st));
+    if (self) HIPCHK(hipMemcpyAsync(self, M.self.p + 1, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_mpc_read(md_ctx *ctx, int64_t *nsamples, int64_t *acc_cnt, double *acc_sum, double *acc_self, double *tmax,
+                int32_t *range_error)
+{
+    API_BEGIN
+    md_ctx::Mpc &M = sampler_of(ctx, &md_ctx::mpc, "md_mpc_read", "mpc");
+    hipStream_t st = ctx->stream;
+    if (acc_cnt) HIPCHK(hipMemcpyAsync(acc_cnt, M.acc_cnt.p, sizeof(int64_t) * M.nbins, hipMemcpyDeviceToHost, st));
+    if (acc_sum) HIPCHK(hipMemcpyAsync(acc_sum, M.acc_sum.p, sizeof(double) * M.nbins, hipMemcpyDeviceToHost, st));
+    if (acc_self) HIPCHK(hipMemcpyAsync(acc_self, M.acc_self.p, sizeof(double), hipMemcpyDeviceToHost, st));
+    if (range_error) HIPCHK(hipMemcpyAsync(range_error, M.range_error.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (nsamples) *nsamples = M.nsamples;
+    if (tmax) *tmax = M.tmax;
+    API_END
+}
+
+int md_mpc_reset(md_ctx *ctx)
+{
+    API_BEGIN
+    sampler_of(ctx, &md_ctx::mpc, "md_mpc_reset", "mpc");
+    mpc_zero(ctx);
     API_END
 }
 

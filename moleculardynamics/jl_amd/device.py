@@ -529,6 +529,62 @@ class MDDevice:
     def chi4_reset(self):
         self._chk(self._L.md_chi4_reset(self._h))
 
+    # -- marked pair correlations: G_l(r), g6(r), C_aa(r) of an uploaded field -------------
+    def mpc_setup(self, r_max, nbins, weights=None, tmax=None):
+        """Allocate the device marked-pair-correlation sampler (md_mpc_setup) out to r_max on nbins <= 4096 bins.
+        weights=None: the marks are q_lm / psi_k of the bond-order sampler's last frame (MD_MPC_BOO; boo_setup first),
+        tmax = 1.  weights = NC in 1..3 numbers: the marks are the caller's (MD_MPC_USER; mpc_marks), a pair contributes
+        t = sum_c weights[c] a_c(i) a_c(j), and tmax bounds |t| (rounded up to a power of two).  All zeroed."""
+        if weights is None:
+            self._chk(self._L.md_mpc_setup(self._h, _lib.MD_MPC_BOO, float(r_max), int(nbins), 0, None, 0.0))
+            nc = 0
+        else:
+            w = _f64(weights).reshape(-1)
+            if tmax is None:
+                raise ValueError("user marks need tmax")
+            self._chk(self._L.md_mpc_setup(self._h, _lib.MD_MPC_USER, float(r_max), int(nbins), int(w.size), _dp(w),
+                                           float(tmax)))
+            nc = int(w.size)
+        self._mpc_shape = (int(nbins), nc)
+
+    def mpc_marks(self, marks):
+        """Upload the marks float64[N, NC] (or [N] when NC = 1), in particle-id order; they stay until replaced; waits."""
+        _, nc = getattr(self, "_mpc_shape", (0, 0))
+        m = _f64(marks)
+        if nc > 0:
+            m = _f64(m.reshape(self.n, nc) if m.size == self.n * nc else m, (self.n, nc))
+        self._chk(self._L.md_mpc_marks(self._h, _dp(m)))
+
+    def mpc_sample(self):
+        """Add one sample of the current positions (does not wait, changes nothing the handle computes afterwards)."""
+        self._chk(self._L.md_mpc_sample(self._h))
+
+    def mpc_last(self):
+        """(cnt int64[nbins], sum int64[nbins], self int) of the last sample: pairs per bin, sum of the integer terms
+        I_ij = llrint(t_ij 2^31 / tmax) per bin, sum_i I_ii; waits."""
+        nbins, _ = getattr(self, "_mpc_shape", (0, 0))
+        cnt, tot = np.zeros(max(nbins, 1), dtype=np.int64), np.zeros(max(nbins, 1), dtype=np.int64)
+        own = C.c_int64()
+        i64 = C.POINTER(C.c_int64)
+        self._chk(self._L.md_mpc_last(self._h, cnt.ctypes.data_as(i64), tot.ctypes.data_as(i64), C.byref(own)))
+        return cnt[:nbins], tot[:nbins], own.value
+
+    def mpc_read(self):
+        """(nsamples, acc_cnt int64[nbins], acc_sum float64[nbins], acc_self float, tmax, range_error), accumulated since
+        setup / reset; acc_sum * tmax * 2^-31 / acc_cnt is the correlation.  range_error: bit 0 a term beyond tmax, bit 1
+        a bin with 2^31 pairs in one sample; waits."""
+        nbins, _ = getattr(self, "_mpc_shape", (0, 0))
+        ns, err = C.c_int64(), C.c_int32()
+        cnt = np.zeros(max(nbins, 1), dtype=np.int64)
+        tot = np.zeros(max(nbins, 1))
+        own, tmax = C.c_double(), C.c_double()
+        self._chk(self._L.md_mpc_read(self._h, C.byref(ns), cnt.ctypes.data_as(C.POINTER(C.c_int64)), _dp(tot),
+                                      C.byref(own), C.byref(tmax), C.byref(err)))
+        return ns.value, cnt[:nbins], tot[:nbins], own.value, tmax.value, err.value
+
+    def mpc_reset(self):
+        self._chk(self._L.md_mpc_reset(self._h))
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

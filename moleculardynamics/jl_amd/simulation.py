@@ -36,7 +36,8 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, sq=None, currents=None, stress=None, four_point=None, clusters=None, cage=None, bond_order=None):
+                   dynamics=None, orientational=None, sq=None, currents=None, stress=None, four_point=None, clusters=None,
+                   cage=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -92,7 +93,13 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     has wave vectors, the structure factor S4(q, t) of the slow particles into, on the device, at the steps of its
     schedule (SelfDynamics' rules: the stops are added to the loop's output steps, the schedule restarts at step 0 in
     every call, the samples accumulate in the object).  Written to pathname/chi4.txt and, with vectors, pathname/s4.txt.
-    It never evaluates the potential.  Nothing else the run produces changes."""
+    It never evaluates the potential.  Nothing else the run produces changes.
+
+    orientational: an OrientationalCorrelation (analysis.py) to sample the orientational correlation function into --
+    G_l(r) of q_lm in 3-D, g6(r) of psi_6 in 2-D -- on the device, at every orientational.every-th output step.  Its
+    marks are bond_order's sample of the same step: bond_order= is required and orientational.every must be a multiple of
+    bond_order.every.  Written to pathname/orient_corr.txt.  It never evaluates the potential.  Nothing else the run
+    produces changes."""
     if clusters is not None and clusters.members == "solid":
         if bond_order is None:
             raise ValueError('clusters with members="solid" needs bond_order= in the same run')
@@ -120,12 +127,14 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     brown_seed = int(state.rng.integers(1 << 63)) if brownian else 0
     # the samplers (analysis.py's protocol), in the order their device calls are made at a step they share
     # (clusters after bond_order: with members="solid" it reads the bond-order frame of the same step; then cage;
-    # four_point last; currents right after sq)
+    # four_point; currents right after sq; orientational last: it reads the bond-order frame of the same step)
     samplers = [s for s in (rdf, dynamics, sq, stress, bond_order) + (clusters, cage, four_point) if s is not None]
     if currents is not None:
         samplers.insert(sum(s is not None for s in (rdf, dynamics, sq)), currents)
+    if orientational is not None:
+        samplers.append(orientational)
     run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
-                                unitcell=state.unitcell, brownian=brownian)
+                                unitcell=state.unitcell, brownian=brownian, bond_order=bond_order)
     for s in samplers:
         s._begin(dev, run)
     vir_acc = [0.0, 0.0]
