@@ -10,10 +10,11 @@
 //                   md_dyn.hpp, w = d2 < a2; the wave's 64 consecutive ids packed by __ballot into one 64-bit word of the
 //                   mask (bits past N are 0), written by one lane; Q counted by popcount per wave and one 64-bit integer
 //                   atomic per block
-//   k_chi4_modes    (md_sq.hpp: sq_walk<D, true>) k_sq_rho's walk over the ORIGIN's f under the mask: one mask word per
-//                   wave and iteration, loaded wave-uniformly; a zero word skips the iteration's whole tile of terms
-//   k_chi4_reduce   one wave per vector: the block partials in k_sq_reduce's tree -> W; lane 0 adds |W|^2 to the row and
-//                   stores W; one thread adds Q, Q Q and 1 into the row, keeps Q for md_chi4_last and zeroes the counter
+//   k_chi4_modes    (md_sq.hpp: mode_walk with MASKED) k_sq_rho's walk over the ORIGIN's f under the mask: one mask word
+//                   per wave and iteration, loaded wave-uniformly; a zero word skips the iteration's whole tile of terms
+//   k_chi4_reduce   one wave per vector: the block partials in k_sq_reduce's tree (md_sq.hpp: sq_row_sum) -> W; lane 0
+//                   adds |W|^2 to the row and stores W; one thread adds Q, Q Q and 1 into the row, keeps Q for
+//                   md_chi4_last and zeroes the counter
 //
 // Exactness contract: del and d2 are section 11's (dyn_disp, d2_ref, no fma), w_i = d2 < a2 with
 // a2 = a a formed once on the host; Q and its moments are integers; W is section 12's sum (phase, sq_cossin, the tree
@@ -66,7 +67,7 @@ __global__ void __launch_bounds__(MD_CHI4_BLOCK)
 }
 
 // One wave per vector (none when nvec == 0: one block still runs for the integers).  part[(v * 2 + comp) * nblk + block]
-// as k_chi4_modes (sq_walk) wrote it; wlast[2 v], wlast[2 v + 1] = W(v) of this sample; s4row = the row's nvec sums of
+// as k_chi4_modes (mode_walk) wrote it; wlast[2 v], wlast[2 v + 1] = W(v) of this sample; s4row = the row's nvec sums of
 // |W|^2; irow = the row's MD_CHI4_NROW integers.
 __global__ void __launch_bounds__(MD_SQ_REDUCE_BLOCK)
     k_chi4_reduce(int nvec, int nblk, const double *__restrict__ part, double *__restrict__ wlast,
@@ -85,14 +86,8 @@ __global__ void __launch_bounds__(MD_SQ_REDUCE_BLOCK)
     const int lane = threadIdx.x & 63;
     const int v = blockIdx.x * (MD_SQ_REDUCE_BLOCK / 64) + (threadIdx.x >> 6);
     if (v >= nvec) return; // (the whole wave)
-    const double *p = part + (size_t)v * 2 * nblk;
-    double a = 0.0, b = 0.0;
-    for (int k = lane; k < nblk; k += 64) {
-        a += p[k];
-        b += p[nblk + k];
-    }
-    a = sq_wave_sum(a);
-    b = sq_wave_sum(b);
+    double a, b;
+    sq_row_sum(part + (size_t)v * 2 * nblk, nblk, lane, a, b);
     if (lane != 0) return;
     wlast[2 * v] = a;
     wlast[2 * v + 1] = b;

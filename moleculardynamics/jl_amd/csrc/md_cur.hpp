@@ -6,12 +6,13 @@
 // One md_cur_sample call = one k_export of the current frame (wrapped x and v in particle-id order), then
 //   k_sq_frac      md_sq's f = U^-1 x, one array per axis
 //   k_cur_vaxis    v, one array per axis (va[a * n + i]), so the walk reads it coalesced
-//   k_cur_modes    grid = (tiles of MD_CUR_TILE vectors, fastest) x (blocks of MD_CUR_BLOCK * MD_CUR_PPT ids): sq_walk's
-//                  shape -- particles across lanes, the tile's vectors wave-uniform (scalar loads), no LDS in the walk --
-//                  with 2 * D * MD_CUR_TILE fp64 accumulators per thread; block partials per (vector, component, part,
-//                  block).  The blocks in flight together share a few particle blocks, so f and v come from L2
-//   k_cur_reduce   one wave per vector: the partials in md_sq's fixed tree -> j; then lane 0 adds the static sums, the
-//                  correlations of this call in call order and stores the origin, in that order
+//   k_cur_modes    grid = (tiles of MD_CUR_TILE vectors, fastest) x (blocks of MD_CUR_BLOCK * MD_CUR_PPT ids): md_sq.hpp's
+//                  mode_walk with CurTerm -- particles across lanes, the tile's vectors wave-uniform (scalar loads), no
+//                  LDS in the walk -- with 2 * D * MD_CUR_TILE fp64 accumulators per thread; block partials per (vector,
+//                  component, part, block).  The blocks in flight together share a few particle blocks, so f and v come
+//                  from L2
+//   k_cur_reduce   one wave per vector: the partials in md_sq's fixed tree (sq_row_sum) -> j; then lane 0 adds the static
+//                  sums, the correlations of this call in call order and stores the origin, in that order
 //   k_cur_vacf, k_cur_vacf_reduce   (with vacf) Z of every (slot, row) pair over particle ids, md_dyn's tree
 //
 // Exactness contract: the phase is md_sq's operation for operation (t = (n_0 f_0 + n_1 f_1) + n_2 f_2
@@ -33,6 +34,7 @@
 #define MD_CUR_VACF_REDUCE_BLOCK 1024
 
 static_assert(MD_SQ_TILE % MD_CUR_TILE == 0, "wave_vector_table pads to whole md_sq tiles");
+static_assert(MD_CUR_BLOCK == MD_SQ_BLOCK && MD_CUR_PPT == MD_SQ_PPT, "mode_walk's block and its tree are md_sq's");
 
 struct CurBatch {
     int count;
@@ -51,6 +53,28 @@ __global__ void __launch_bounds__(MD_BLOCK)
     for (int a = 0; a < D; ++a) va[(size_t)a * n + i] = v[(size_t)i * D + a];
 }
 
+// mode_walk's term for j: particle i brings v_i (va, one array per axis) and adds fma(v_a, c, Re j_a), fma(v_a, s, Im j_a)
+// per axis; acc[a * 2 + {Re, Im}].
+template <int D>
+struct CurTerm {
+    static constexpr int NPV = 2 * D;
+    double vel[D];
+    __device__ __forceinline__ void load(const double *__restrict__ va, int n, int i)
+    {
+#pragma unroll
+        for (int a = 0; a < D; ++a) vel[a] = va[(size_t)a * n + i];
+    }
+    __device__ __forceinline__ void add(double c, double s, double *acc) const
+    {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            acc[a * 2] = fma(vel[a], c, acc[a * 2]);
+            acc[a * 2 + 1] = fma(vel[a], s, acc[a * 2 + 1]);
+        }
+    }
+};
+
 // nd: md_sq's table (3 doubles per vector, zero-padded to whole tiles).  part[((v * D + a) * 2 + part) * nblk + block].
 // One-dimensional grid of ntiles * nblk blocks, the tile index running fastest: a tile of 4 re-reads f and v (48 B per
 // particle) once per tile, twice md_sq's traffic per term, and with the particle block running fastest every tile streamed
@@ -61,59 +85,9 @@ __global__ void __launch_bounds__(MD_CUR_BLOCK)
     k_cur_modes(int n, int nblk, int ntiles, const double *__restrict__ fr, const double *__restrict__ va,
                 const double *__restrict__ nd, double *__restrict__ part)
 {
-#pragma clang fp contract(off)
-    constexpr int NACC = 2 * D * MD_CUR_TILE;
-    __shared__ double wsum[MD_CUR_BLOCK / 64][NACC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int pblk = (int)(blockIdx.x / (unsigned)ntiles);
     const int v0 = (int)(blockIdx.x - (unsigned)pblk * (unsigned)ntiles) * MD_CUR_TILE;
-    double nv[MD_CUR_TILE][3];
-#pragma unroll
-    for (int j = 0; j < MD_CUR_TILE; ++j)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) nv[j][c] = nd[(size_t)(v0 + j) * 3 + c]; // (uniform: scalar loads)
-    double acc[NACC];             // [(j * D + a) * 2 + {Re, Im}]
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
-    const int base = pblk * (MD_CUR_BLOCK * MD_CUR_PPT) + threadIdx.x;
-    for (int m = 0; m < MD_CUR_PPT; ++m) {
-        const int i = base + m * MD_CUR_BLOCK;
-        if (i < n) {
-            const double f0 = fr[i], f1 = fr[(size_t)n + i];
-            double f2 = 0.0;
-            if constexpr (D == 3) f2 = fr[2 * (size_t)n + i];
-            double vel[D];
-#pragma unroll
-            for (int a = 0; a < D; ++a) vel[a] = va[(size_t)a * n + i];
-#pragma unroll
-            for (int j = 0; j < MD_CUR_TILE; ++j) {
-                double t = nv[j][0] * f0 + nv[j][1] * f1;
-                if constexpr (D == 3) t = t + nv[j][2] * f2;
-                const double r = t - rint(t);
-                double c, s;
-                sq_cossin(r, c, s);
-#pragma unroll
-                for (int a = 0; a < D; ++a) {
-                    acc[(j * D + a) * 2] = fma(vel[a], c, acc[(j * D + a) * 2]);
-                    acc[(j * D + a) * 2 + 1] = fma(vel[a], s, acc[(j * D + a) * 2 + 1]);
-                }
-            }
-        }
-    }
-    // fixed tree: shuffle within the wave, then the waves in order
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        const double w = sq_wave_sum(acc[k]);
-        if (lane == 0) wsum[wave][k] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < NACC) {
-        const int k = threadIdx.x;
-        double s = wsum[0][k];
-#pragma unroll
-        for (int w = 1; w < MD_CUR_BLOCK / 64; ++w) s = s + wsum[w][k];
-        part[((size_t)v0 * 2 * D + k) * nblk + pblk] = s;
-    }
+    mode_walk<D, MD_CUR_TILE, false, CurTerm<D>>(n, nblk, pblk, v0, fr, va, nd, part, nullptr, 0);
 }
 
 // pL = (e_0 j_0 + e_1 j_1) + e_2 j_2 of one part (Re or Im) of j
@@ -143,16 +117,7 @@ __global__ void __launch_bounds__(MD_CUR_REDUCE_BLOCK)
     double re[3] = {0.0, 0.0, 0.0}, im[3] = {0.0, 0.0, 0.0};
     if (reduce) {
 #pragma unroll
-        for (int a = 0; a < D; ++a) {
-            const double *p = part + ((size_t)v * D + a) * 2 * nblk;
-            double x = 0.0, y = 0.0;
-            for (int k = lane; k < nblk; k += 64) {
-                x += p[k];
-                y += p[nblk + k];
-            }
-            re[a] = sq_wave_sum(x);
-            im[a] = sq_wave_sum(y);
-        }
+        for (int a = 0; a < D; ++a) sq_row_sum(part + ((size_t)v * D + a) * 2 * nblk, nblk, lane, re[a], im[a]);
     }
     if (lane != 0) return;
     double *jv = jout + (size_t)v * 2 * D;

@@ -12,6 +12,9 @@
 //                no LDS in the walk; block partials in a fixed tree, written per (vector, component, block)
 //   k_sq_reduce  one wave per vector: the block partials in a fixed tree -> rho; then lane 0 adds |rho|^2 to s2, the
 //                correlations of this call to their rows and stores the origin, in that order
+// The particle walk and the partial tree are written once, here, for the three wave-vector samplers (md_sq, md_chi4,
+// md_cur): mode_walk<D, TILE, MASKED, Term> is the body of k_sq_rho, k_chi4_modes and k_cur_modes, sq_row_sum the
+// opening of k_sq_reduce, k_chi4_reduce and k_cur_reduce.
 //
 // Exactness contract: t = (n_0 f_0 + n_1 f_1) + n_2 f_2 with every operation rounded on its own,
 // r = t - rint(t) (exact), the term is (cos 2 pi r, sin 2 pi r) from two polynomials in r^2 for sin / cos of the half angle
@@ -99,29 +102,48 @@ __device__ __forceinline__ void sq_cossin(double r, double &c, double &s)
     c = fma(s2 * s2, -0.5, 1.0);
 }
 
-// nd: the wave vectors as doubles, 3 per vector (the third 0 in 2-D), padded with zero vectors to a multiple of
-// MD_SQ_TILE.  part[(v * 2 + comp) * nblk + block].
+// What a particle adds to the accumulators of one wave vector -- the term policy of mode_walk: NPV accumulators per
+// vector, load(aux, n, i) fetches what particle i brings besides f, add(c, s, acc) adds its term to acc[0..NPV).  Here
+// (rho, W) the term is (c, s) itself, a plain add each; CurTerm (md_cur.hpp) is the other one.
+struct SqTerm {
+    static constexpr int NPV = 2; // Re, Im
+    __device__ __forceinline__ void load(const double *, int, int) {}
+    __device__ __forceinline__ void add(double c, double s, double *acc) const
+    {
+#pragma clang fp contract(off)
+        acc[0] += c;
+        acc[1] += s;
+    }
+};
+
+// The walk of the wave-vector samplers (k_sq_rho, k_chi4_modes, k_cur_modes): particle block pblk (MD_SQ_BLOCK *
+// MD_SQ_PPT ids) against the TILE vectors from v0.  nd: the wave vectors as doubles, 3 per vector (the third 0 in 2-D),
+// padded with zero vectors to a multiple of MD_SQ_TILE; aux: what Term::load reads (nullptr for SqTerm).  The tile's
+// vectors are wave-uniform (scalar loads), a thread walks its MD_SQ_PPT ids in order with NPV * TILE fp64 accumulators and
+// no LDS; then the fixed tree -- a shuffle tree per accumulator, the four wave sums in order -- and one partial per
+// (vector, accumulator, block): part[((v0 + j) * NPV + k) * nblk + pblk].
 // MASKED (md_chi4.hpp): the same walk over the particles whose bit is set in mask (bit l of word k = particle id
 // 64 k + l, nwords words).  The 64 ids of a wave in one iteration are consecutive from a multiple of 64, so they share one
 // word: it is loaded once per wave and iteration through a wave-uniform address, a zero word skips the iteration, and a
 // particle whose bit is clear adds nothing -- the tree of the sum is the unmasked one.
-template <int D, bool MASKED>
-__device__ __forceinline__ void sq_walk(int n, int nblk, const double *__restrict__ fr, const double *__restrict__ nd,
-                                        double *__restrict__ part, const unsigned long long *__restrict__ mask, int nwords)
+template <int D, int TILE, bool MASKED, class Term>
+__device__ __forceinline__ void mode_walk(int n, int nblk, int pblk, int v0, const double *__restrict__ fr,
+                                          const double *__restrict__ aux, const double *__restrict__ nd,
+                                          double *__restrict__ part, const unsigned long long *__restrict__ mask, int nwords)
 {
 #pragma clang fp contract(off)
-    __shared__ double wsum[MD_SQ_BLOCK / 64][2 * MD_SQ_TILE];
+    constexpr int NPV = Term::NPV, NACC = NPV * TILE;
+    __shared__ double wsum[MD_SQ_BLOCK / 64][NACC];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int v0 = blockIdx.y * MD_SQ_TILE;
-    double nv[MD_SQ_TILE][3];
+    double nv[TILE][3];
 #pragma unroll
-    for (int j = 0; j < MD_SQ_TILE; ++j)
+    for (int j = 0; j < TILE; ++j)
 #pragma unroll
         for (int c = 0; c < 3; ++c) nv[j][c] = nd[(size_t)(v0 + j) * 3 + c]; // (uniform: scalar loads)
-    double re[MD_SQ_TILE], im[MD_SQ_TILE];
+    double acc[NACC];             // [j * NPV + k]
 #pragma unroll
-    for (int j = 0; j < MD_SQ_TILE; ++j) re[j] = im[j] = 0.0;
-    const int base = blockIdx.x * (MD_SQ_BLOCK * MD_SQ_PPT) + threadIdx.x;
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    const int base = pblk * (MD_SQ_BLOCK * MD_SQ_PPT) + threadIdx.x;
     for (int m = 0; m < MD_SQ_PPT; ++m) {
         const int i = base + m * MD_SQ_BLOCK;
         bool on = i < n;
@@ -135,34 +157,37 @@ __device__ __forceinline__ void sq_walk(int n, int nblk, const double *__restric
             const double f0 = fr[i], f1 = fr[(size_t)n + i];
             double f2 = 0.0;
             if constexpr (D == 3) f2 = fr[2 * (size_t)n + i];
+            Term term;
+            term.load(aux, n, i);
 #pragma unroll
-            for (int j = 0; j < MD_SQ_TILE; ++j) {
+            for (int j = 0; j < TILE; ++j) {
                 double t = nv[j][0] * f0 + nv[j][1] * f1;
                 if constexpr (D == 3) t = t + nv[j][2] * f2;
                 const double r = t - rint(t);
                 double c, s;
                 sq_cossin(r, c, s);
-                re[j] += c;
-                im[j] += s;
+                term.add(c, s, acc + j * NPV);
             }
         }
     }
     // fixed tree: shuffle within the wave, then the waves in order
 #pragma unroll
-    for (int j = 0; j < MD_SQ_TILE; ++j) {
-        const double a = sq_wave_sum(re[j]), b = sq_wave_sum(im[j]);
+    for (int j = 0; j < TILE; ++j) {
+        double w[NPV];
+#pragma unroll
+        for (int k = 0; k < NPV; ++k) w[k] = sq_wave_sum(acc[j * NPV + k]);
         if (lane == 0) {
-            wsum[wave][2 * j] = a;
-            wsum[wave][2 * j + 1] = b;
+#pragma unroll
+            for (int k = 0; k < NPV; ++k) wsum[wave][j * NPV + k] = w[k];
         }
     }
     __syncthreads();
-    if (threadIdx.x < 2 * MD_SQ_TILE) {
-        const int j = threadIdx.x;
-        double s = wsum[0][j];
+    if (threadIdx.x < NACC) {
+        const int k = threadIdx.x;
+        double s = wsum[0][k];
 #pragma unroll
-        for (int w = 1; w < MD_SQ_BLOCK / 64; ++w) s = s + wsum[w][j];
-        part[((size_t)v0 * 2 + j) * nblk + blockIdx.x] = s;
+        for (int w = 1; w < MD_SQ_BLOCK / 64; ++w) s = s + wsum[w][k];
+        part[((size_t)v0 * NPV + k) * nblk + pblk] = s;
     }
 }
 
@@ -170,7 +195,7 @@ template <int D>
 __global__ void __launch_bounds__(MD_SQ_BLOCK)
     k_sq_rho(int n, int nblk, const double *__restrict__ fr, const double *__restrict__ nd, double *__restrict__ part)
 {
-    sq_walk<D, false>(n, nblk, fr, nd, part, nullptr, 0);
+    mode_walk<D, MD_SQ_TILE, false, SqTerm>(n, nblk, blockIdx.x, blockIdx.y * MD_SQ_TILE, fr, nullptr, nd, part, nullptr, 0);
 }
 
 // W of md_chi4.hpp: the walk over the slow particles of one (origin, current frame) pair.
@@ -179,7 +204,22 @@ __global__ void __launch_bounds__(MD_SQ_BLOCK)
     k_chi4_modes(int n, int nblk, const double *__restrict__ fr, const double *__restrict__ nd, double *__restrict__ part,
                  const unsigned long long *__restrict__ mask, int nwords)
 {
-    sq_walk<D, true>(n, nblk, fr, nd, part, mask, nwords);
+    mode_walk<D, MD_SQ_TILE, true, SqTerm>(n, nblk, blockIdx.x, blockIdx.y * MD_SQ_TILE, fr, nullptr, nd, part, mask, nwords);
+}
+
+// The partial tree of k_sq_reduce, k_chi4_reduce and k_cur_reduce: lane 0 of the calling wave gets the sums (a, b) of one
+// (Re, Im) pair of partial rows, p[block] and p[nblk + block] -- lane l adds the blocks l, l + 64, ... in order, then a
+// shuffle tree.
+__device__ __forceinline__ void sq_row_sum(const double *__restrict__ p, int nblk, int lane, double &a, double &b)
+{
+#pragma clang fp contract(off)
+    double x = 0.0, y = 0.0;
+    for (int k = lane; k < nblk; k += 64) {
+        x += p[k];
+        y += p[nblk + k];
+    }
+    a = sq_wave_sum(x);
+    b = sq_wave_sum(y);
 }
 
 // One wave per vector.  reduce != 0: rho[v] from the block partials (and |rho|^2 into s2 if add_static); otherwise rho[v]
@@ -194,17 +234,7 @@ __global__ void __launch_bounds__(MD_SQ_REDUCE_BLOCK)
     const int v = blockIdx.x * (MD_SQ_REDUCE_BLOCK / 64) + (threadIdx.x >> 6);
     if (v >= nvec) return; // (the whole wave)
     double a, b;
-    if (reduce) {
-        const double *p = part + (size_t)v * 2 * nblk;
-        a = 0.0;
-        b = 0.0;
-        for (int k = lane; k < nblk; k += 64) {
-            a += p[k];
-            b += p[nblk + k];
-        }
-        a = sq_wave_sum(a);
-        b = sq_wave_sum(b);
-    }
+    if (reduce) sq_row_sum(part + (size_t)v * 2 * nblk, nblk, lane, a, b);
     if (lane != 0) return;
     if (reduce) {
         rho[2 * v] = a;

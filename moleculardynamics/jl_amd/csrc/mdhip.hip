@@ -132,6 +132,13 @@ struct SlotRows {
         snprintf(b, sizeof b, "%s: slot %d is out of range 0..%d", who, slot, nslots - 1);
         throw HipError(b);
     }
+    void check_origin(const char *who, int slot) const // the origin store of a sample call (md_sq, md_cur): -1 = none
+    {
+        if (slot >= -1 && slot < nslots) return;
+        char b[200];
+        snprintf(b, sizeof b, "%s: origin slot %d is out of range -1..%d", who, slot, nslots - 1);
+        throw HipError(b);
+    }
     // The (slot, row) pairs of one sample call: every slot holds an origin, every row exists.
     void check_batch(const char *who, const int32_t *slots, const int32_t *rows, int count, const char *empty_hint) const
     {
@@ -161,6 +168,31 @@ struct SlotRows {
     void read_counts(int64_t *out) const
     {
         if (out) std::copy(nsamples.begin(), nsamples.end(), out);
+    }
+};
+
+inline int blocks_of(int64_t n, int per) { return (int)((n + per - 1) / per); }
+
+// What mode_walk (md_sq.hpp) needs of a wave-vector sampler (md_sq, md_chi4, md_cur): the vectors, the particle blocks
+// and the block partials
+struct ModeSet {
+    int nvec = 0, nvec_pad = 0, nblk = 0;
+    DBuf<double> nd, part;         // nvec_pad x 3 wave vectors as doubles; (vector, accumulator, block)
+    // The nv x dim integer vectors as the table the mode kernels read -- doubles, 3 per vector, padded with zero vectors
+    // to whole md_sq tiles (none when nv == 0) -- and the partials of n particles, npv accumulators per vector.  Waits:
+    // the table is a host vector.
+    void init(const int32_t *nvecs, int nv, int dim, int64_t n, int npv, hipStream_t st)
+    {
+        nvec = nv;
+        nvec_pad = (nv + MD_SQ_TILE - 1) / MD_SQ_TILE * MD_SQ_TILE;
+        nblk = blocks_of(n, MD_SQ_BLOCK * MD_SQ_PPT);
+        std::vector<double> t((size_t)nvec_pad * 3, 0.0);
+        for (int v = 0; v < nv; ++v)
+            for (int c = 0; c < dim; ++c) t[(size_t)v * 3 + c] = (double)nvecs[(size_t)v * dim + c];
+        nd.alloc(t.size());
+        part.alloc((size_t)nvec_pad * npv * std::max(nblk, 1));
+        if (nv) HIPCHK(hipMemcpyAsync(nd.p, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
     }
 };
 
@@ -399,14 +431,12 @@ struct md_ctx {
     // density modes (md_sq_*): the slot / row bookkeeping (both may be empty), the wave vectors, the current frame and its
     // fractional coordinates, block partials, rho of the last sampled frame, the static and the correlation accumulators,
     // rho of the stored origins
-    struct Sq {
+    struct Sq : ModeSet {
         bool on = false;
-        int nvec = 0, nvec_pad = 0, nblk = 0;
         bool sampled = false;             // rho holds a frame
         int64_t nstatic = 0;
         SlotRows sr;
-        DBuf<double> nd;                  // nvec_pad x 3 wave vectors as doubles
-        DBuf<double> cx, fr, part, rho, s2, corr, org; // frame; f per axis; (vector, comp, block); 2 nvec; nvec; nrows x nvec; nslots x nvec x 2
+        DBuf<double> cx, fr, rho, s2, corr, org; // frame; f per axis; 2 nvec; nvec; nrows x nvec; nslots x nvec x 2
         DBuf<int32_t> ci;
     } sq;
 
@@ -475,16 +505,16 @@ struct md_ctx {
     // four-point dynamics (md_chi4_*): the slot / row bookkeeping; per origin slot the frame and -- with vectors -- its
     // fractional coordinates; the current frame; the mask, the block partials, Q and W of the sample in flight / the last
     // one; the rows
-    struct Chi4 {
+    struct Chi4 : ModeSet {
         bool on = false;
         bool sampled = false;             // mask / qlast / wlast hold a sample
-        int nvec = 0, nvec_pad = 0, nblk = 0, nwords = 0;
+        int nwords = 0;
         double a = 0.0, a2 = 0.0;
         SlotRows sr;                      // (sr.nsamples: the host's count, behind the sum_q2 overflow guard)
         DBuf<double> ox;                  // nslots frames of n x dim wrapped coordinates, in particle-id order
         DBuf<int32_t> oi;                 // nslots frames of n x dim image counts
         DBuf<double> of;                  // nslots frames of dim x n fractional coordinates, one array per axis (nvec > 0)
-        DBuf<double> nd, cx, part, wlast, s4; // nvec_pad x 3; frame; (vector, comp, block); 2 nvec; nrows x nvec
+        DBuf<double> cx, wlast, s4;       // frame; 2 nvec; nrows x nvec
         DBuf<int32_t> ci;
         DBuf<unsigned long long> mask, qcur; // nwords; 1
         DBuf<long long> qlast, irow;      // 1; nrows x MD_CHI4_NROW
@@ -494,17 +524,17 @@ struct md_ctx {
     // directions; the current frame, its f and v per axis; block partials, j of the last sampled frame, the static and
     // the correlation accumulators, j of the stored origins; with vacf the origins' velocity frames, the pair partials
     // and z (nrows lag rows, then the equal-time row)
-    struct Cur {
+    struct Cur : ModeSet {
         bool on = false;
         bool vacf = false;
-        int nvec = 0, nvec_pad = 0, nblk = 0, zblk = 0;
+        int zblk = 0;
         bool sampled = false;             // jl holds a frame
         int64_t nstatic = 0;
         SlotRows sr;
-        DBuf<double> nd, e;               // nvec_pad x 3 wave vectors as doubles; nvec x dim unit directions
+        DBuf<double> e;                   // nvec x dim unit directions
         DBuf<double> cx, cv, fr, va;      // frame x, v (n x dim); f and v per axis
         DBuf<int32_t> ci;
-        DBuf<double> part, jl, s_tot, s_long, c_tot, c_long, org; // (vector, a, part, block); nvec x dim x 2; nvec; nvec; nrows x nvec (2); nslots x nvec x dim x 2
+        DBuf<double> jl, s_tot, s_long, c_tot, c_long, org; // nvec x dim x 2; nvec; nvec; nrows x nvec (2); nslots x nvec x dim x 2
         DBuf<double> ov, zpart, z;        // nslots frames of n x dim velocities; batch x zblk; nrows + 1
     } current;
 
@@ -1837,8 +1867,6 @@ void sq_zero(md_ctx *c)
     S.sr.clear_counts();
 }
 
-inline int blocks_of(int64_t n, int per) { return (int)((n + per - 1) / per); }
-
 // The DynParams of a sample against the current cell: n, dim, U and nblk; with q, the nq wave numbers and nquant = 2 + nq
 // (0 without: md_chi4's kernels read n and U alone); with nbins > 0, the van Hove bins.
 DynParams dyn_params(const md_ctx *c, const std::vector<double> *q = nullptr, int nbins = 0, double r_max = 0.0)
@@ -1867,6 +1895,20 @@ Batch batch_from(const int32_t *slots, const int32_t *rows, int i0, int count, i
     std::copy(slots + i0, slots + i0 + B.count, B.slot);
     std::copy(rows + i0, rows + i0 + B.count, B.row);
     return B;
+}
+
+// A sample call's (slot, row) pairs batch by batch: fn(B, first, last) -- once with an empty batch when count == 0, for
+// the samplers whose launch also reduces the frame and stores the origin (md_sq, md_cur)
+template <class Batch, class F>
+void for_batches(const int32_t *slots, const int32_t *rows, int count, int max_batch, F fn)
+{
+    int i0 = 0;
+    do {
+        const Batch B = batch_from<Batch>(slots, rows, i0, count, max_batch);
+        const bool first = i0 == 0;
+        i0 += B.count;
+        fn(B, first, i0 >= count);
+    } while (i0 < count);
 }
 
 // ---- cage-relative dynamics (md_cage.hpp): launches ----------------------------------------------------------------
@@ -1948,7 +1990,6 @@ void launch_cur_modes(md_ctx *c, hipStream_t st)
 {
     md_ctx::Cur &S = c->current;
     const int n = (int)c->n;
-    k_sq_frac<D><<<nblocks(n), MD_BLOCK, 0, st>>>(n, c->grid, S.cx.p, S.fr.p);
     k_cur_vaxis<D><<<nblocks(n), MD_BLOCK, 0, st>>>(n, S.cv.p, S.va.p);
     const int ntiles = S.nvec_pad / MD_CUR_TILE;
     k_cur_modes<D><<<(unsigned)S.nblk * (unsigned)ntiles, MD_CUR_BLOCK, 0, st>>>(n, S.nblk, ntiles, S.fr.p, S.va.p, S.nd.p,
@@ -2491,8 +2532,8 @@ int md_neighbor_pairs(md_ctx *ctx, int32_t *pairs, int64_t cap, int64_t *count)
 // ---------------------------------------------------------------------------------------------
 // Shared by the sampler entry points below, with sampler_of above: the argument checks here; for the four samplers that
 // correlate the current frame with stored origins (md_dyn_*, md_sq_*, md_cage_*, md_chi4_*, md_cur_*) also SlotRows and
-// alloc_or_refuse at the top of this file and dyn_zero / sq_zero / cage_zero / chi4_zero / cur_zero, dyn_params and
-// batch_from above.
+// alloc_or_refuse at the top of this file and dyn_zero / sq_zero / cage_zero / chi4_zero / cur_zero, dyn_params,
+// batch_from and for_batches above; for the three that sum over wave vectors (md_sq_*, md_chi4_*, md_cur_*) ModeSet.
 static void check_range(const char *who, const char *name, int v, int lo, int hi)
 {
     if (v >= lo && v <= hi) return;
@@ -2559,16 +2600,6 @@ static void check_wave_vectors(const char *who, const int32_t *nvecs, int nvec, 
             throw HipError(b);
         }
     }
-}
-
-// ... and the table the mode kernels read: the vectors as doubles, 3 per vector, padded with zero vectors to whole tiles
-static std::vector<double> wave_vector_table(const int32_t *nvecs, int nvec, int dim)
-{
-    const int nvec_pad = (nvec + MD_SQ_TILE - 1) / MD_SQ_TILE * MD_SQ_TILE;
-    std::vector<double> nd((size_t)nvec_pad * 3, 0.0);
-    for (int v = 0; v < nvec; ++v)
-        for (int c = 0; c < dim; ++c) nd[(size_t)v * 3 + c] = (double)nvecs[(size_t)v * dim + c];
-    return nd;
 }
 
 // The gather md_download makes, of the wrapped coordinates and image counts -- and, with v, the velocities -- into a
@@ -2836,6 +2867,18 @@ int md_dyn_reset(md_ctx *ctx)
 // ---------------------------------------------------------------------------------------------
 // Density modes, S(q) and coherent F(q, t) (md_sq.hpp): a sample launches k_export into the sampler's own frame buffer and
 // reads nothing else of the state, so the step loop, the list and the cell order are what they would have been without it.
+// k_sq_frac of the frame x (n x dim, particle-id order): f = U^-1 x into fr, one array per axis (md_chi4_origin and
+// md_cur_sample launch it too; it stands here so that the kernels are emitted where they were)
+static void launch_frac(md_ctx *ctx, const double *x, double *fr)
+{
+    const int n = (int)ctx->n;
+    if (ctx->dim == 3)
+        k_sq_frac<3><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, x, fr);
+    else
+        k_sq_frac<2><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, x, fr);
+    HIPCHK(hipGetLastError());
+}
+
 int md_sq_setup(md_ctx *ctx, const int32_t *nvecs, int nvec, int nslots, int nrows)
 {
     API_BEGIN
@@ -2850,28 +2893,20 @@ int md_sq_setup(md_ctx *ctx, const int32_t *nvecs, int nvec, int nslots, int nro
     S.on = false;
     const int64_t n = ctx->n;
     const size_t frame = (size_t)n * dim;
-    const int nblk = blocks_of(n, MD_SQ_BLOCK * MD_SQ_PPT);
-    const std::vector<double> nd = wave_vector_table(nvecs, nvec, dim);
-    const int nvec_pad = (int)(nd.size() / 3);
-    S.nd.alloc(nd.size());
+    hipStream_t st = ctx->stream;
+    S.init(nvecs, nvec, dim, n, 2, st);
     S.cx.alloc(frame);
     S.ci.alloc(frame);
     S.fr.alloc(frame);
-    S.part.alloc((size_t)nvec_pad * 2 * nblk);
     S.rho.alloc((size_t)nvec * 2);
     S.s2.alloc(nvec);
     S.corr.alloc((size_t)nrows * nvec);
     S.org.alloc((size_t)nslots * nvec * 2);
-    hipStream_t st = ctx->stream;
-    HIPCHK(hipMemcpyAsync(S.nd.p, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(S.rho.p, 0, sizeof(double) * nvec * 2, st));
     if (nslots) HIPCHK(hipMemsetAsync(S.org.p, 0, sizeof(double) * nslots * nvec * 2, st));
-    S.nvec = nvec;
-    S.nvec_pad = nvec_pad;
     S.sr.init(nslots, nrows);
-    S.nblk = nblk;
     S.sampled = false;
-    sq_zero(ctx); // (waits: the vector table is a host vector)
+    sq_zero(ctx); // (waits)
     S.on = true;
     API_END
 }
@@ -2882,32 +2917,22 @@ int md_sq_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32_
     md_ctx::Sq &S = sampler_of(ctx, &md_ctx::sq, "md_sq_sample", "sq");
     require_state(ctx, "md_sq_sample");
     S.sr.check_batch("md_sq_sample", slots, rows, count, "store an origin with origin_slot first");
-    if (origin_slot < -1 || origin_slot >= S.sr.nslots) {
-        char b[200];
-        snprintf(b, sizeof b, "md_sq_sample: origin slot %d is out of range -1..%d", origin_slot, S.sr.nslots - 1);
-        throw HipError(b);
-    }
+    S.sr.check_origin("md_sq_sample", origin_slot);
     hipStream_t st = ctx->stream;
     const int n = (int)ctx->n;
     export_frame(ctx, S.cx.p, S.ci.p);
-    if (ctx->dim == 3) {
-        k_sq_frac<3><<<nblocks(n), MD_BLOCK, 0, st>>>(n, ctx->grid, S.cx.p, S.fr.p);
+    launch_frac(ctx, S.cx.p, S.fr.p);
+    if (ctx->dim == 3)
         k_sq_rho<3><<<dim3(S.nblk, S.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(n, S.nblk, S.fr.p, S.nd.p, S.part.p);
-    } else {
-        k_sq_frac<2><<<nblocks(n), MD_BLOCK, 0, st>>>(n, ctx->grid, S.cx.p, S.fr.p);
+    else
         k_sq_rho<2><<<dim3(S.nblk, S.nvec_pad / MD_SQ_TILE), MD_SQ_BLOCK, 0, st>>>(n, S.nblk, S.fr.p, S.nd.p, S.part.p);
-    }
     HIPCHK(hipGetLastError());
     const int rblk = (S.nvec + MD_SQ_REDUCE_BLOCK / 64 - 1) / (MD_SQ_REDUCE_BLOCK / 64);
-    int i0 = 0;
-    do {
-        const SqBatch B = batch_from<SqBatch>(slots, rows, i0, count, MD_SQ_MAX_BATCH);
-        const bool last = i0 + B.count >= count;
-        k_sq_reduce<<<rblk, MD_SQ_REDUCE_BLOCK, 0, st>>>(S.nvec, S.nblk, i0 == 0, add_static != 0, B, last ? origin_slot : -1,
+    for_batches<SqBatch>(slots, rows, count, MD_SQ_MAX_BATCH, [&](const SqBatch &B, bool first, bool last) {
+        k_sq_reduce<<<rblk, MD_SQ_REDUCE_BLOCK, 0, st>>>(S.nvec, S.nblk, first, add_static != 0, B, last ? origin_slot : -1,
                                                         S.part.p, S.rho.p, S.s2.p, S.corr.p, S.org.p);
         HIPCHK(hipGetLastError());
-        i0 += B.count;
-    } while (i0 < count);
+    });
     S.sampled = true;
     if (add_static) ++S.nstatic;
     S.sr.count_rows(rows, count);
@@ -3495,33 +3520,25 @@ int md_chi4_setup(md_ctx *ctx, double a, const int32_t *nvecs, int nvec, int nsl
     snprintf(b, sizeof b, "%d origin slots (nslots*N*d*%d = %d*%lld*%d*%d)", nslots, per, nslots, (long long)n, dim, per);
     alloc_or_refuse("md_chi4_setup", "MDHIP_CHI4_ALLOC_LIMIT", slots_size * per, b, std::make_pair(&X.ox, slots_size),
                     std::make_pair(&X.oi, slots_size), std::make_pair(&X.of, nvec > 0 ? slots_size : (size_t)0));
-    const int nblk = blocks_of(n, MD_SQ_BLOCK * MD_SQ_PPT);
     const int nwords = (int)((n + 63) / 64);
-    const std::vector<double> nd = wave_vector_table(nvecs, nvec, dim);
-    const int nvec_pad = (int)(nd.size() / 3);
-    X.nd.alloc(nd.size());
+    hipStream_t st = ctx->stream;
+    X.init(nvecs, nvec, dim, n, 2, st);
     X.cx.alloc(frame);
     X.ci.alloc(frame);
-    X.part.alloc((size_t)nvec_pad * 2 * std::max(nblk, 1));
     X.wlast.alloc((size_t)nvec * 2);
     X.s4.alloc((size_t)nrows * std::max(nvec, 1));
     X.mask.alloc(nwords);
     X.qcur.alloc(1);
     X.qlast.alloc(1);
     X.irow.alloc((size_t)nrows * MD_CHI4_NROW);
-    hipStream_t st = ctx->stream;
-    if (!nd.empty()) HIPCHK(hipMemcpyAsync(X.nd.p, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(X.qcur.p, 0, sizeof(unsigned long long), st));
     HIPCHK(hipMemsetAsync(X.qlast.p, 0, sizeof(long long), st));
-    X.nvec = nvec;
-    X.nvec_pad = nvec_pad;
     X.sr.init(nslots, nrows);
-    X.nblk = nblk;
     X.nwords = nwords;
     X.a = a;
     X.a2 = a * a;
     X.sampled = false;
-    chi4_zero(ctx); // (waits: the vector table is a host vector)
+    chi4_zero(ctx); // (waits)
     X.on = true;
     API_END
 }
@@ -3532,18 +3549,10 @@ int md_chi4_origin(md_ctx *ctx, int slot)
     md_ctx::Chi4 &X = sampler_of(ctx, &md_ctx::chi4, "md_chi4_origin", "chi4");
     require_state(ctx, "md_chi4_origin");
     X.sr.check_slot("md_chi4_origin", slot);
-    const int n = (int)ctx->n;
-    const size_t frame = (size_t)n * ctx->dim;
+    const size_t frame = (size_t)ctx->n * ctx->dim;
     double *ox = X.ox.p + (size_t)slot * frame;
     export_frame(ctx, ox, X.oi.p + (size_t)slot * frame);
-    if (X.nvec > 0) {
-        double *of = X.of.p + (size_t)slot * frame;
-        if (ctx->dim == 3)
-            k_sq_frac<3><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, ox, of);
-        else
-            k_sq_frac<2><<<nblocks(n), MD_BLOCK, 0, ctx->stream>>>(n, ctx->grid, ox, of);
-        HIPCHK(hipGetLastError());
-    }
+    if (X.nvec > 0) launch_frac(ctx, ox, X.of.p + (size_t)slot * frame);
     X.sr.filled[slot] = 1;
     API_END
 }
@@ -3666,19 +3675,16 @@ int md_cur_setup(md_ctx *ctx, const int32_t *nvecs, const double *e, int nvec, i
     // MDHIP_CUR_ALLOC_LIMIT=bytes refuses velocity origin slots above this size
     snprintf(b, sizeof b, "%d velocity origin slots (nslots*N*d*8 = %d*%lld*%d*8)", nslots, nslots, (long long)n, dim);
     alloc_or_refuse("md_cur_setup", "MDHIP_CUR_ALLOC_LIMIT", slots_size * 8, b, std::make_pair(&S.ov, slots_size));
-    const int nblk = blocks_of(n, MD_CUR_BLOCK * MD_CUR_PPT);
     const int zblk = blocks_of(n, MD_CUR_VACF_BLOCK * MD_CUR_VACF_PPT);
-    const std::vector<double> nd = wave_vector_table(nvecs, nvec, dim);
-    const int nvec_pad = (int)(nd.size() / 3);
     const size_t nv = (size_t)nvec;
-    S.nd.alloc(nd.size());
+    hipStream_t st = ctx->stream;
+    S.init(nvecs, nvec, dim, n, 2 * dim, st);
     S.e.alloc(nv * dim);
     S.cx.alloc(frame);
     S.cv.alloc(frame);
     S.ci.alloc(frame);
     S.fr.alloc(nvec ? frame : 0);
     S.va.alloc(nvec ? frame : 0);
-    S.part.alloc((size_t)nvec_pad * 2 * dim * std::max(nblk, 1));
     S.jl.alloc(nv * 2 * dim);
     S.s_tot.alloc(nv);
     S.s_long.alloc(nv);
@@ -3687,18 +3693,13 @@ int md_cur_setup(md_ctx *ctx, const int32_t *nvecs, const double *e, int nvec, i
     S.org.alloc((size_t)nslots * nv * 2 * dim);
     S.zpart.alloc(vacf ? (size_t)MD_CUR_MAX_BATCH * std::max(zblk, 1) : 0);
     S.z.alloc(vacf ? (size_t)nrows + 1 : 0);
-    hipStream_t st = ctx->stream;
     if (nvec) {
-        HIPCHK(hipMemcpyAsync(S.nd.p, nd.data(), sizeof(double) * nd.size(), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(S.e.p, e, sizeof(double) * nv * dim, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemsetAsync(S.jl.p, 0, sizeof(double) * nv * 2 * dim, st));
         if (nslots) HIPCHK(hipMemsetAsync(S.org.p, 0, sizeof(double) * nslots * nv * 2 * dim, st));
     }
     S.vacf = vacf != 0;
-    S.nvec = nvec;
-    S.nvec_pad = nvec_pad;
     S.sr.init(nslots, nrows);
-    S.nblk = nblk;
     S.zblk = zblk;
     S.sampled = false;
     cur_zero(ctx); // (waits: the tables are host memory)
@@ -3712,29 +3713,22 @@ int md_cur_sample(md_ctx *ctx, int add_static, const int32_t *slots, const int32
     md_ctx::Cur &S = sampler_of(ctx, &md_ctx::current, "md_cur_sample", "cur");
     require_state(ctx, "md_cur_sample");
     S.sr.check_batch("md_cur_sample", slots, rows, count, "store an origin with origin_slot first");
-    if (origin_slot < -1 || origin_slot >= S.sr.nslots) {
-        char b[200];
-        snprintf(b, sizeof b, "md_cur_sample: origin slot %d is out of range -1..%d", origin_slot, S.sr.nslots - 1);
-        throw HipError(b);
-    }
+    S.sr.check_origin("md_cur_sample", origin_slot);
     hipStream_t st = ctx->stream;
     const int n = (int)ctx->n, dim = ctx->dim;
     export_frame(ctx, S.cx.p, S.ci.p, S.cv.p);
     if (S.nvec > 0) {
+        launch_frac(ctx, S.cx.p, S.fr.p);
         if (dim == 3)
             launch_cur_modes<3>(ctx, st);
         else
             launch_cur_modes<2>(ctx, st);
-        int i0 = 0;
-        do {
-            const CurBatch B = batch_from<CurBatch>(slots, rows, i0, count, MD_CUR_MAX_BATCH);
-            const bool last = i0 + B.count >= count;
+        for_batches<CurBatch>(slots, rows, count, MD_CUR_MAX_BATCH, [&](const CurBatch &B, bool first, bool last) {
             if (dim == 3)
-                launch_cur_reduce<3>(ctx, st, i0 == 0, add_static != 0, B, last ? origin_slot : -1);
+                launch_cur_reduce<3>(ctx, st, first, add_static != 0, B, last ? origin_slot : -1);
             else
-                launch_cur_reduce<2>(ctx, st, i0 == 0, add_static != 0, B, last ? origin_slot : -1);
-            i0 += B.count;
-        } while (i0 < count);
+                launch_cur_reduce<2>(ctx, st, first, add_static != 0, B, last ? origin_slot : -1);
+        });
     }
     if (S.vacf) {
         // the equal-time pair (the frame against itself, into the row after the lag rows) first, then the call's pairs
