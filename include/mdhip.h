@@ -594,6 +594,30 @@ typedef struct {
 int md_profile(md_ctx *ctx, int enable);
 int md_get_stats(md_ctx *ctx, md_stats *out);
 
+/* The Verlet rows as they are, for audits (tests/row_audit.py): never builds, prunes or changes anything.  Two calls like
+ * md_neighbor_pairs: entries = NULL, cap = 0 for *count, then again with room for it.
+ *   which    0: the outer rows (cutoff + skin, built at x0); 1: the inner rows (cutoff + inner skin, pruned at x1) -- an
+ *            error unless info[6] (inner_valid) is set
+ *   info     NULL or MD_LIST_ROWS_INFO doubles:
+ *            [0] list cutoff  [1] effective skin (after the box clip)  [2] list radius rl = cutoff + skin
+ *            [3] inner skin (0 without valid inner rows)  [4] d1 = max |x1 - x0| as the prune step measured it (Euclidean)
+ *            [5] list_valid  [6] inner_valid  [7] tiled (16-bit rows into per-tile halo lists)  [8] fused build
+ *            (k_build_tile; 0 with [7] set: the two-kernel fallback)  [9] own-first halo numbering  [10] the inner rows
+ *            index the inner halo image  [11] n  [12] rows are 32-bit global slots (no tiles)  [13] real ghost slots
+ *            [14] halo words carry owner | shift code (virtual ghosts)  [15] this build supports inner rows
+ *   entries  cap x 5 int32, one (id_i, id_j, n_0, n_1, n_2) per row entry, rows in slot order, every row in row order,
+ *            both directions of a pair (j in the row of i, and i in the row of j).  n in {-1, 0, 1}^d is the periodic image
+ *            the entry stands for: the record the pair loop reads is x_j + n . A (A: columns = lattice vectors).
+ *            Sentinel / padding entries are left out.  An entry that cannot be decoded has id_j = -1 or an image
+ *            component of 2.
+ *   x0, x1, pos   all NULL, or n x d each by particle id (the layout of md_download), in the handle's own unwrapped frame:
+ *            positions at the last list build, at the last prune (== x0 without valid inner rows), and now.
+ * A handle whose rows are not valid (after md_upload, md_run_brownian, md_fire_minimize, ...) reports info with
+ * list_valid = 0 and *count = 0.  Slab-decomposition handles are refused. */
+#define MD_LIST_ROWS_INFO 16
+int md_list_rows(md_ctx *ctx, int which, double *info, int32_t *entries, int64_t cap, int64_t *count, double *x0,
+                 double *x1, double *pos);
+
 /* ---------------------------------------------------------------------------------------------
  * Slab decomposition: one handle per GPU, each owning the particles of one slab of the x axis
  * (new relative to the reference, which is single-process).  y and z

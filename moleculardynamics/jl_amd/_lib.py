@@ -13,13 +13,14 @@ MD_POT_LJ, MD_POT_PSEUDOHS, MD_POT_POLYDISPERSE, MD_POT_LJ_MODIFIED, MD_POT_CUST
 MD_NVE, MD_NVT = 0, 1
 MD_CLUSTER_ALL, MD_CLUSTER_SOLID = 0, 1
 MD_MPC_BOO, MD_MPC_USER = 0, 1
+MD_LIST_ROWS_INFO = 16
 
 # every symbol include/mdhip.h declares
 EXPORTS = [
     "md_create", "md_destroy", "md_last_error", "md_set_potential", "md_set_potential_source", "md_set_skin",
     "md_set_inner_skin",
     "md_upload", "md_download", "md_snapshot_begin", "md_snapshot_end", "md_compute_forces", "md_neighbor_pairs", "md_run", "md_kinetic",
-    "md_scale_velocities", "md_profile", "md_get_stats", "md_version", "md_fire_minimize", "md_run_brownian",
+    "md_scale_velocities", "md_profile", "md_get_stats", "md_list_rows", "md_version", "md_fire_minimize", "md_run_brownian",
     "md_create_domain", "md_dom_set_uniform", "md_dom_upload", "md_dom_download", "md_dom_migrate_pack",
     "md_dom_migrate_unpack", "md_dom_halo_pack", "md_dom_halo_unpack", "md_dom_build", "md_dom_get_sendbuf",
     "md_dom_put_recvbuf", "md_dom_set_step_buffers", "md_dom_step_begin", "md_dom_step_end", "md_dom_forces", "md_dom_set_scale",
@@ -93,6 +94,8 @@ def load():
     L.md_compute_forces.restype = C.c_int
     L.md_neighbor_pairs.argtypes = [vp, ip, C.c_int64, C.POINTER(C.c_int64)]
     L.md_neighbor_pairs.restype = C.c_int
+    L.md_list_rows.argtypes = [vp, C.c_int, dp, ip, C.c_int64, C.POINTER(C.c_int64), dp, dp, dp]
+    L.md_list_rows.restype = C.c_int
     L.md_run.argtypes = [vp, C.c_int64, C.c_double, C.c_int, C.c_double, C.c_double, dp, dp, dp, dp]
     L.md_run.restype = C.c_int
     L.md_kinetic.argtypes = [vp, dp]

@@ -20,6 +20,7 @@
 #include "md_cage.hpp"
 #include "md_chi4.hpp"
 #include "md_cur.hpp"
+#include "md_listrows.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -2526,6 +2527,106 @@ int md_neighbor_pairs(md_ctx *ctx, int32_t *pairs, int64_t cap, int64_t *count)
         HIPCHK(hipMemcpyAsync(pairs, out.p, (size_t)ncopy * 2 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
     }
+    API_END
+}
+
+// Instrumentation: the Verlet rows as they are (include/mdhip.h).  Never builds or prunes; reads what the next force
+// evaluation would walk (which = 0: outer rows, 1: inner rows) through md_listrows.hpp.
+int md_list_rows(md_ctx *ctx, int which, double *info, int32_t *entries, int64_t cap, int64_t *count, double *x0,
+                 double *x1, double *pos)
+{
+    API_BEGIN
+    require_state(ctx, "md_list_rows");
+    if (ctx->dom.on) throw HipError("md_list_rows: not available on a slab-decomposition handle");
+    if (which != 0 && which != 1) throw HipError("md_list_rows: which must be 0 (outer rows) or 1 (inner rows)");
+    if (cap < 0 || (cap > 0 && !entries)) throw HipError("md_list_rows: bad output buffer");
+    if ((x0 || x1 || pos) && !(x0 && x1 && pos)) throw HipError("md_list_rows: x0, x1 and pos are given together or not at all");
+    hipStream_t st = ctx->stream;
+    const int n = (int)ctx->n;
+    const bool valid = ctx->list_valid;
+    const bool inner = valid && ctx->inner_valid;
+    if (which == 1 && !inner) throw HipError("md_list_rows: no valid inner rows (inner_valid = 0)");
+    if (info) {
+        double d1 = 0.0;
+        if (inner) {
+            Scalars h = read_scalars(ctx);
+            unsigned long long bits = h.d1max2_bits;
+            double d12;
+            memcpy(&d12, &bits, sizeof d12);
+            d1 = std::sqrt(d12);
+        }
+        const double v[MD_LIST_ROWS_INFO] = {ctx->rc, ctx->skin, ctx->rl, inner ? ctx->inner_skin : 0.0, d1,
+                                             valid ? 1.0 : 0.0, inner ? 1.0 : 0.0, (valid && ctx->use_tiles) ? 1.0 : 0.0,
+                                             (valid && ctx->use_tiles && !ctx->have_nlist32) ? 1.0 : 0.0,
+                                             (valid && ctx->own_first) ? 1.0 : 0.0,
+                                             (inner && ctx->inner_halo_live) ? 1.0 : 0.0, (double)ctx->n,
+                                             (valid && !ctx->use_tiles) ? 1.0 : 0.0, (double)ctx->nghost,
+                                             (valid && ctx->virtual_ghosts) ? 1.0 : 0.0, (valid && ctx->prune_on) ? 1.0 : 0.0};
+        memcpy(info, v, sizeof v);
+    }
+    DevState s = ctx->dev(ctx->cur);
+    if (pos && n > 0) {
+        const size_t nd = (size_t)n * ctx->dim;
+        DBuf<double> o;
+        o.alloc(3 * nd);
+        if (ctx->dim == 3)
+            k_listrows_positions<3><<<ctx->nblk, MD_BLOCK, 0, st>>>(n, s, o.p, o.p + nd, o.p + 2 * nd);
+        else
+            k_listrows_positions<2><<<ctx->nblk, MD_BLOCK, 0, st>>>(n, s, o.p, o.p + nd, o.p + 2 * nd);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(x0, o.p, nd * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(x1, o.p + nd, nd * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(pos, o.p + 2 * nd, nd * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    int64_t total = 0;
+    if (valid && n > 0) {
+        ListRowsView V{};
+        V.n = n;
+        V.nghost = (int)ctx->nghost;
+        V.id = s.id;
+        V.maxn = ctx->maxn;
+        V.sentinel32 = (uint32_t)ctx->cap;
+        V.gowner = ctx->gowner.p;
+        V.gcode = ctx->gcode.p;
+        if (ctx->use_tiles) {
+            const bool hin = which == 1 && ctx->inner_halo_live;
+            V.rows16 = which == 1 ? ctx->nlist16_in.p : ctx->nlist16.p;
+            V.rowlen = which == 1 ? ctx->nmax_tile_in.p : ctx->nmax_tile.p;
+            V.rs = ctx->tile_rs;
+            V.halo = hin ? ctx->halo_in.p : ctx->halo.p;
+            V.hcap = hin ? ctx->hcap_in : ctx->hcap;
+            V.halo_count = hin ? ctx->halo_in_count.p : ctx->halo_count.p;
+        } else {
+            V.rows32 = ctx->nlist.p;
+            V.rowlen = ctx->nmax_tile.p;
+        }
+        DBuf<int32_t> cnt;
+        cnt.alloc((size_t)n);
+        k_listrows<false><<<ctx->nblk, MD_BLOCK, 0, st>>>(V, cnt.p, nullptr, nullptr, 0);
+        HIPCHK(hipGetLastError());
+        std::vector<int32_t> hc((size_t)n);
+        HIPCHK(hipMemcpyAsync(hc.data(), cnt.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        std::vector<int64_t> off((size_t)n);
+        for (int k = 0; k < n; ++k) {
+            off[k] = total;
+            total += hc[k];
+        }
+        const int64_t ncopy = std::min(total, cap);
+        if (ncopy > 0) {
+            DBuf<int64_t> doff;
+            doff.alloc((size_t)n);
+            DBuf<int32_t> out;
+            out.alloc((size_t)ncopy * 5);
+            HIPCHK(hipMemcpyAsync(doff.p, off.data(), sizeof(int64_t) * n, hipMemcpyHostToDevice, st));
+            k_listrows<true><<<ctx->nblk, MD_BLOCK, 0, st>>>(V, nullptr, doff.p, out.p, (long long)ncopy);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(entries, out.p, (size_t)ncopy * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+        }
+    }
+    if (count) *count = total;
     API_END
 }
 

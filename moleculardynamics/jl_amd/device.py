@@ -594,3 +594,25 @@ class MDDevice:
         s = MdStats()
         self._chk(self._L.md_get_stats(self._h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in MdStats._fields_}
+
+    LIST_ROWS_INFO = ("rc", "skin", "rl", "inner_skin", "d1", "list_valid", "inner_valid", "tiled", "fused_build",
+                      "own_first", "inner_halo_live", "n", "rows32", "n_ghost", "virtual_ghosts", "prune_on")
+
+    def list_rows(self, which=0):
+        """The Verlet rows as they are (md_list_rows; builds and changes nothing).  which = 0: outer rows, 1: inner rows
+        (an error without valid inner rows).  Returns dict(which, info, entries, x0, x1, pos): info = the named fields of
+        LIST_ROWS_INFO (flags and n as int), entries int32[m, 5] = (id_i, id_j, n_0, n_1, n_2) in row order, both
+        directions of every pair, x0 / x1 / pos float64[n, d] by particle id in the device's own unwrapped frame.  A handle
+        whose rows are not valid gives info["list_valid"] == 0 and no entries."""
+        info = np.zeros(_lib.MD_LIST_ROWS_INFO)
+        shp = (self.n, self.dim)
+        x0, x1, pos = np.empty(shp), np.empty(shp), np.empty(shp)
+        cnt = C.c_int64()
+        self._chk(self._L.md_list_rows(self._h, int(which), _dp(info), None, 0, C.byref(cnt), _dp(x0), _dp(x1), _dp(pos)))
+        ent = np.empty((max(cnt.value, 1), 5), dtype=np.int32)
+        cnt2 = C.c_int64()
+        self._chk(self._L.md_list_rows(self._h, int(which), None, _ip(ent), cnt.value, C.byref(cnt2), None, None, None))
+        if cnt2.value != cnt.value:
+            raise MdhipError("row entry count changed between calls")
+        named = {k: (float(v) if i < 5 else int(v)) for i, (k, v) in enumerate(zip(self.LIST_ROWS_INFO, info))}
+        return dict(which=int(which), info=named, entries=ent[: cnt.value], x0=x0, x1=x1, pos=pos)
