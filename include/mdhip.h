@@ -738,6 +738,36 @@ int md_dom_enable_pruning(md_ctx *ctx, int on);
 int md_dom_max_disp0(md_ctx *ctx, double *d0);
 int md_dom_invalidate_inner(md_ctx *ctx);
 
+/* Swap Monte Carlo: rounds of diameter exchanges at fixed positions, to be interleaved with blocks
+ * of md_run (Berthier, Flenner, Fullerton, Scalliet, Singh, J. Stat. Mech. 2019).  The diameter is pos[].w; the rows do not
+ * depend on it (list_cutoff is the caller's number), so no round ever invalidates the list.
+ * One ROUND, a function of (positions, diameters, seed, round index) alone:  Philox4x32-10, key = seed, counter =
+ * (0-based particle index i, round lo, round hi, 1) gives w0..w3.  i proposes iff w0 < min(2^32 - 1, floor(fraction 2^32));
+ * its partner is j = (w1 * N) >> 32 (anywhere in the box; j == i: the proposal is void); the swap's key is (w2 << 32) | i.
+ * Both members take the minimum key offered to them; a swap that holds it at both members is live, the others have lost
+ * the claim.  A live swap that finds, within list_cutoff of either member, a member of a live swap with a smaller key is
+ * blocked (one pass, conservative: it yields even when that swap is blocked itself).  Otherwise: filtered when
+ * |sigma_i - sigma_j| > max_diameter_difference (<= 0: no filter), else accepted iff (w3 + 0.5) / 2^32 < exp(-dU / ktemp),
+ * dU = sum over the neighbours k != partner of u(r, sigma_partner, sigma_k) - u(r, sigma_self, sigma_k) for both members,
+ * pairs and pair energies as md_compute_forces takes them.  An accepted swap exchanges the two diameters.
+ * md_swap_setup: fraction in (0, 1].  Single-GPU handles only.
+ * md_swap_rounds: rebuilds the list first when it is not valid (as md_compute_forces does), enqueues rounds first_round ..
+ * first_round + nrounds - 1 without a host wait in between, then makes every copy of a diameter the handle holds
+ * consistent and finishes with one force evaluation, as md_compute_forces: the handle's forces belong to the new diameters
+ * and *energy, *virial are their U and W.  counts = {proposed, void, lost the claim, blocked, filtered, accepted} over the
+ * call's rounds; *decided = accepted + rejected; *du_accepted = sum of dU over the accepted swaps.  Any output may be NULL.
+ * Refused: before md_swap_setup; ktemp <= 0; all diameters equal; MD_POT_CUSTOM -- the pair energy of a run-time compiled
+ * potential is not reachable from the swap kernel.
+ * md_swap_last: the last round by particle index: partner (-1: i did not propose), status (0 none, 1 void, 2 lost the
+ * claim, 3 blocked, 4 filtered, 5 rejected, 6 accepted; at the proposer) and dU (decided swaps, else 0).
+ * md_diameters: the current diameters by particle index.                                                              */
+int md_swap_setup(md_ctx *ctx, double fraction, double max_diameter_difference /* <= 0: none */, uint64_t seed);
+int md_swap_rounds(md_ctx *ctx, int64_t nrounds, double ktemp, int64_t first_round,
+                   int64_t *counts /* [6]: proposed, void, lost the claim, blocked, filtered, accepted */,
+                   int64_t *decided, double *du_accepted, double *energy, double *virial);
+int md_swap_last(md_ctx *ctx, int32_t *partner, int32_t *status, double *du);
+int md_diameters(md_ctx *ctx, double *diameters);
+
 /* Library build info: returns e.g. "mdhip 0.1 gfx950". */
 const char *md_version(void);
 

@@ -1125,6 +1125,34 @@ function mpc_read(dev::Device, nbins::Integer)
     return ns[], cnt, sum, self[], tmax[], err[]
 end
 
+# ---- swap Monte Carlo on the device (md_swap_*; device.py's swap_* calls) ---------------------------------------------
+"fraction in (0, 1]; max_diameter_difference <= 0: no filter; seed keys the Philox stream"
+swap_setup!(dev::Device, fraction, max_diameter_difference, seed::Integer) =
+    check(dev, ccall((:md_swap_setup, LIB), Cint, (Ptr{Cvoid}, Float64, Float64, UInt64),
+                     dev.h, fraction, max_diameter_difference, seed))
+"rounds first_round .. first_round + nrounds - 1, then a force refresh: (counts[6], decided, du_accepted, U, W); waits"
+function swap_rounds!(dev::Device, nrounds::Integer, ktemp, first_round::Integer = 0)
+    counts = zeros(Int64, 6); dec = Ref{Int64}(0)
+    du = Ref{Float64}(0.0); u = Ref{Float64}(0.0); w = Ref{Float64}(0.0)
+    check(dev, ccall((:md_swap_rounds, LIB), Cint,
+                     (Ptr{Cvoid}, Int64, Float64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                     dev.h, nrounds, ktemp, first_round, counts, dec, du, u, w))
+    return counts, dec[], du[], u[], w[]
+end
+"(partner, status, du) of the last round, by particle (0-based partner, -1: did not propose); waits"
+function swap_last(dev::Device, n::Integer)
+    partner = zeros(Int32, n); status = zeros(Int32, n); du = zeros(n)
+    check(dev, ccall((:md_swap_last, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}),
+                     dev.h, partner, status, du))
+    return partner, status, du
+end
+"the current diameters, in particle order; waits"
+function diameters(dev::Device, n::Integer)
+    d = zeros(n)
+    check(dev, ccall((:md_diameters, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), dev.h, d))
+    return d
+end
+
 # ---- output: src/io.jl ---------------------------------------------------------------------------------------------
 function generate_log_times(; max_iter::Int=10000, logn::Int=40, logbase::Float64=1.35, save::Bool=true)   # src/io.jl:17-36
     dtime = Int[]

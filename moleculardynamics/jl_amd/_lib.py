@@ -37,6 +37,7 @@ EXPORTS = [
     "md_chi4_setup", "md_chi4_origin", "md_chi4_sample", "md_chi4_last", "md_chi4_read", "md_chi4_reset",
     "md_cur_setup", "md_cur_sample", "md_cur_last", "md_cur_read", "md_cur_reset",
     "md_mpc_setup", "md_mpc_marks", "md_mpc_sample", "md_mpc_last", "md_mpc_read", "md_mpc_reset",
+    "md_swap_setup", "md_swap_rounds", "md_swap_last", "md_diameters",
 ]
 
 
@@ -253,6 +254,14 @@ def load():
     L.md_mpc_read.restype = C.c_int
     L.md_mpc_reset.argtypes = [vp]
     L.md_mpc_reset.restype = C.c_int
+    L.md_swap_setup.argtypes = [vp, C.c_double, C.c_double, C.c_uint64]
+    L.md_swap_setup.restype = C.c_int
+    L.md_swap_rounds.argtypes = [vp, C.c_int64, C.c_double, C.c_int64, i64p, i64p, dp, dp, dp]
+    L.md_swap_rounds.restype = C.c_int
+    L.md_swap_last.argtypes = [vp, ip, ip, dp]
+    L.md_swap_last.restype = C.c_int
+    L.md_diameters.argtypes = [vp, dp]
+    L.md_diameters.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -20,8 +20,8 @@ import numpy as np
 # ---------------------------------------------------------------------------------------------------------------------
 # The sampler protocol.  run_simulation drives every sampler class of this module through four private methods:
 #   _begin(dev, run)            set the sampler up on the device and derive what it needs for this run; `run` carries
-#                               total_steps, frequency, n, dim, dt, unitcell, brownian and bond_order (the run's
-#                               BondOrder or None)
+#                               total_steps, frequency, n, dim, dt, unitcell, brownian, bond_order (the run's
+#                               BondOrder or None), ensemble and rng (the state's generator; montecarlo.py uses both)
 #   _next(step)                 the first step >= `step` at which the sampler acts in this run, or None
 #   _act(dev, step)             the device calls of that step
 #   _finish(dev, run, pathname) read back, accumulate into the object, write the files

@@ -21,6 +21,7 @@
 #include "md_chi4.hpp"
 #include "md_cur.hpp"
 #include "md_listrows.hpp"
+#include "md_swap.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -561,6 +562,20 @@ struct md_ctx {
         DBuf<long long> cur_sum, last_sum, self;  // nbins; nbins; {cur, last}
         DBuf<double> acc_sum, acc_self;   // nbins; 1
     } mpc;
+
+    // swap Monte Carlo (md_swap_*): the claims, the live keys, the compact member list and the per-entry results of the
+    // round in flight; partner / status / dU of the last round by particle id; the counters and the running sum of the
+    // accepted dU of one md_swap_rounds call
+    struct Swap {
+        bool on = false;
+        bool ran = false;                 // partner / status / du hold a round
+        double fraction = 0.0, max_diff = 0.0;
+        uint64_t seed = 0;
+        uint32_t thr = 0;
+        DBuf<unsigned long long> claim, livekey, counts; // n; n; MD_SWAP_NCOUNT
+        DBuf<int32_t> partner, status, entry, members, blocked, nmember, inv; // n; n; n; 2 n + 4; n + 2; 1; n
+        DBuf<double> half, du, part, du_acc;             // n + 2; n; blocks; 1
+    } swap;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -2023,6 +2038,29 @@ void cur_zero(md_ctx *c)
     HIPCHK(hipStreamSynchronize(c->stream));
     S.nstatic = 0;
     S.sr.clear_counts();
+}
+
+// ---- swap Monte Carlo (md_swap.hpp): the walk's launch ------------------------------------------------------------
+template <int D>
+void launch_swap_walk(md_ctx *c, const SwapRows &V, const DevState &s, const SwapBufs &B, int grid)
+{
+    const double c2 = c->rc * c->rc;
+    switch (c->pot_kind) {
+    case POT_LJ:
+        k_swap_walk<D, POT_LJ><<<grid, MD_BLOCK, 0, c->stream>>>(V, s, c->pp, c2, B);
+        break;
+    case POT_PSEUDOHS:
+        k_swap_walk<D, POT_PSEUDOHS><<<grid, MD_BLOCK, 0, c->stream>>>(V, s, c->pp, c2, B);
+        break;
+    case POT_POLYDISPERSE:
+        k_swap_walk<D, POT_POLYDISPERSE><<<grid, MD_BLOCK, 0, c->stream>>>(V, s, c->pp, c2, B);
+        break;
+    case POT_LJ_MOD:
+        k_swap_walk<D, POT_LJ_MOD><<<grid, MD_BLOCK, 0, c->stream>>>(V, s, c->pp, c2, B);
+        break;
+    default:
+        throw HipError("md_swap_rounds: potential kind not available");
+    }
 }
 
 } // namespace
@@ -4092,6 +4130,179 @@ int md_mpc_reset(md_ctx *ctx)
     API_BEGIN
     sampler_of(ctx, &md_ctx::mpc, "md_mpc_reset", "mpc");
     mpc_zero(ctx);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Swap Monte Carlo (md_swap.hpp)
+// ---------------------------------------------------------------------------------------------
+int md_swap_setup(md_ctx *ctx, double fraction, double max_diameter_difference, uint64_t seed)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_swap_setup: not available on a slab-decomposition handle");
+    if (!(fraction > 0.0) || !(fraction <= 1.0)) {
+        char b[160];
+        snprintf(b, sizeof b, "md_swap_setup: fraction must be in (0, 1], got %.17g", fraction);
+        throw HipError(b);
+    }
+    if (std::isnan(max_diameter_difference)) throw HipError("md_swap_setup: max_diameter_difference is NaN (<= 0 means none)");
+    md_ctx::Swap &S = ctx->swap;
+    S.on = false;
+    S.ran = false;
+    S.fraction = fraction;
+    S.max_diff = max_diameter_difference > 0.0 ? max_diameter_difference : 0.0;
+    S.seed = seed;
+    // thr = min(2^32 - 1, floor(fraction 2^32)): fraction 2^32 is exact in a double
+    const double t = std::floor(fraction * 4294967296.0);
+    S.thr = t >= 4294967295.0 ? 0xffffffffu : (uint32_t)t;
+    const size_t n = (size_t)ctx->n;
+    S.claim.alloc(n);
+    S.livekey.alloc(n);
+    S.counts.alloc(MD_SWAP_NCOUNT);
+    S.partner.alloc(n);
+    S.status.alloc(n);
+    S.entry.alloc(n);
+    S.members.alloc(2 * n + 4);
+    S.blocked.alloc(n + 2);
+    S.nmember.alloc(1);
+    S.inv.alloc(n);
+    S.half.alloc(n + 2);
+    S.du.alloc(n);
+    S.part.alloc((size_t)std::max(nblocks(ctx->n), 1));
+    S.du_acc.alloc(1);
+    S.on = true;
+    API_END
+}
+
+int md_swap_rounds(md_ctx *ctx, int64_t nrounds, double ktemp, int64_t first_round, int64_t *counts, int64_t *decided,
+                   double *du_accepted, double *energy, double *virial)
+{
+    API_BEGIN
+    require_state(ctx, "md_swap_rounds");
+    md_ctx::Swap &S = sampler_of(ctx, &md_ctx::swap, "md_swap_rounds", "swap");
+    if (!(ktemp > 0.0) || !std::isfinite(ktemp)) throw HipError("md_swap_rounds: ktemp must be finite and > 0");
+    if (nrounds < 0 || nrounds > 0x3fffffff) throw HipError("md_swap_rounds: nrounds must be in 0..2^30");
+    if (first_round < 0) throw HipError("md_swap_rounds: first_round must be >= 0");
+    if (ctx->pot_kind == POT_CUSTOM)
+        throw HipError("md_swap_rounds: not available for a run-time compiled potential (its pair energy is not reachable "
+                       "from the swap kernel)");
+    if (ctx->uniform_sigma) throw HipError("md_swap_rounds: all diameters are equal: there is nothing to exchange");
+    if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
+    hipStream_t st = ctx->stream;
+    const int n = (int)ctx->n;
+    const int nb = ctx->nblk;
+    DevState s = ctx->dev(ctx->cur);
+    SwapBufs B{};
+    B.n = n;
+    B.claim = S.claim.p;
+    B.livekey = S.livekey.p;
+    B.partner = S.partner.p;
+    B.status = S.status.p;
+    B.entry = S.entry.p;
+    B.members = S.members.p;
+    B.half = S.half.p;
+    B.blocked = S.blocked.p;
+    B.nmember = S.nmember.p;
+    B.du = S.du.p;
+    B.inv = S.inv.p;
+    B.counts = S.counts.p;
+    B.partials = S.part.p;
+    B.du_acc = S.du_acc.p;
+    SwapRows V{};
+    V.n = n;
+    V.nghost = (int)ctx->nghost;
+    V.cap = (long long)ctx->cap;
+    V.id = s.id;
+    V.maxn = ctx->maxn;
+    V.rowlen = ctx->nmax_tile.p;
+    V.gowner = ctx->gowner.p;
+    if (ctx->use_tiles) {
+        V.rows16 = ctx->nlist16.p;
+        V.rs = ctx->tile_rs;
+        V.halo = ctx->halo.p;
+        V.hcap = ctx->hcap;
+        V.halo_count = ctx->halo_count.p;
+    } else {
+        if (!ctx->have_nlist32) throw HipError("internal: neither tiled nor 32-bit rows exist");
+        V.rows32 = ctx->nlist.p;
+    }
+    HIPCHK(hipMemsetAsync(S.claim.p, 0xff, sizeof(unsigned long long) * (size_t)n, st));
+    HIPCHK(hipMemsetAsync(S.livekey.p, 0xff, sizeof(unsigned long long) * (size_t)n, st));
+    HIPCHK(hipMemsetAsync(S.counts.p, 0, sizeof(unsigned long long) * MD_SWAP_NCOUNT, st));
+    HIPCHK(hipMemsetAsync(S.nmember.p, 0, sizeof(int32_t), st));
+    HIPCHK(hipMemsetAsync(S.du_acc.p, 0, sizeof(double), st));
+    k_swap_inv<<<nb, MD_BLOCK, 0, st>>>(n, s.id, S.inv.p);
+    // one wave per member, at most n members: never more blocks than that needs
+    const int grid = (int)std::min<int64_t>(MD_SWAP_WALK_BLOCKS, std::max<int64_t>(1, ((int64_t)n + 3) / 4));
+    for (int64_t r = 0; r < nrounds; ++r) {
+        const long long round = (long long)(first_round + r);
+        k_swap_propose<<<nb, MD_BLOCK, 0, st>>>(B, (unsigned long long)S.seed, round, S.thr);
+        k_swap_live<<<nb, MD_BLOCK, 0, st>>>(B, (unsigned long long)S.seed, round);
+        if (ctx->dim == 3)
+            launch_swap_walk<3>(ctx, V, s, B, grid);
+        else
+            launch_swap_walk<2>(ctx, V, s, B, grid);
+        k_swap_decide<<<nb, MD_BLOCK, 0, st>>>(B, s, (unsigned long long)S.seed, round, ktemp, S.max_diff);
+        k_swap_finish<<<1, 1024, 0, st>>>(nb, B);
+    }
+    HIPCHK(hipGetLastError());
+    if (nrounds > 0) S.ran = true;
+    // Every copy of a diameter the handle holds: the real ghost records are copies of their
+    // owners' whole records; the other position buffer becomes a copy of this one; the step records are rebuilt from
+    // pos[] by every step loop's entry.  The rows do not depend on the diameters and stay as they are.
+    launch_ghost_update(ctx, -1);
+    HIPCHK(hipMemcpyAsync(ctx->sb[ctx->cur ^ 1].pos.p, ctx->sb[ctx->cur].pos.p, sizeof(double4) * (size_t)ctx->next,
+                          hipMemcpyDeviceToDevice, st));
+    // forces, U and W of the new diameters (velocity-Verlet's next half-kick reads the forces)
+    launch_force(ctx, true, false, 0.0, -1, 1);
+    launch_finalize(ctx, true, false, 1.0, 0.0, -1);
+    HIPCHK(hipGetLastError());
+    unsigned long long hc[MD_SWAP_NCOUNT];
+    double hdu = 0.0;
+    HIPCHK(hipMemcpyAsync(hc, S.counts.p, sizeof hc, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&hdu, S.du_acc.p, sizeof hdu, hipMemcpyDeviceToHost, st));
+    Scalars h = read_scalars(ctx); // (the call's one wait)
+    if (counts) {
+        counts[0] = 0;
+        for (int c = MD_SWAP_VOID; c <= MD_SWAP_ACCEPTED; ++c) counts[0] += (int64_t)hc[c];
+        counts[1] = (int64_t)hc[MD_SWAP_VOID];
+        counts[2] = (int64_t)hc[MD_SWAP_LOST];
+        counts[3] = (int64_t)hc[MD_SWAP_BLOCKED];
+        counts[4] = (int64_t)hc[MD_SWAP_FILTERED];
+        counts[5] = (int64_t)hc[MD_SWAP_ACCEPTED];
+    }
+    if (decided) *decided = (int64_t)(hc[MD_SWAP_REJECTED] + hc[MD_SWAP_ACCEPTED]);
+    if (du_accepted) *du_accepted = hdu;
+    if (energy) *energy = h.U;
+    if (virial) *virial = h.W;
+    API_END
+}
+
+int md_swap_last(md_ctx *ctx, int32_t *partner, int32_t *status, double *du)
+{
+    API_BEGIN
+    md_ctx::Swap &S = sampler_of(ctx, &md_ctx::swap, "md_swap_last", "swap");
+    if (!S.ran) throw HipError("md_swap_last: no round has run yet (call md_swap_rounds first)");
+    const size_t n = (size_t)ctx->n;
+    hipStream_t st = ctx->stream;
+    if (partner) HIPCHK(hipMemcpyAsync(partner, S.partner.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (status) HIPCHK(hipMemcpyAsync(status, S.status.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (du) HIPCHK(hipMemcpyAsync(du, S.du.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_diameters(md_ctx *ctx, double *diameters)
+{
+    API_BEGIN
+    require_state(ctx, "md_diameters");
+    if (ctx->dom.on) throw HipError("md_diameters: not available on a slab-decomposition handle");
+    if (!diameters) throw HipError("md_diameters: diameters is null");
+    ctx->io_d.ensure((size_t)ctx->n);
+    k_swap_diameters<<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, ctx->dev(ctx->cur), ctx->io_d.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(diameters, ctx->io_d.p, sizeof(double) * (size_t)ctx->n, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     API_END
 }
 

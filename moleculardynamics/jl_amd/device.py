@@ -585,6 +585,45 @@ class MDDevice:
     def mpc_reset(self):
         self._chk(self._L.md_mpc_reset(self._h))
 
+    # -- swap Monte Carlo ------------------------------------------------------------------
+    SWAP_COUNTS = ("proposed", "void", "lost", "blocked", "filtered", "accepted")
+    SWAP_STATUS = ("none", "void", "lost", "blocked", "filtered", "rejected", "accepted")
+
+    def swap_setup(self, fraction, max_diameter_difference=None, seed=0):
+        """Allocate the device swap sampler (md_swap_setup): every round a particle proposes with probability `fraction`
+        in (0, 1]; max_diameter_difference=None: no filter; `seed` keys the Philox stream."""
+        mdd = 0.0 if max_diameter_difference is None else float(max_diameter_difference)
+        self._chk(self._L.md_swap_setup(self._h, float(fraction), mdd, C.c_uint64(int(seed) & (2 ** 64 - 1))))
+
+    def swap_rounds(self, nrounds, ktemp, first_round=0):
+        """Run rounds first_round .. first_round + nrounds - 1 of diameter exchanges at the current positions
+        (md_swap_rounds), then refresh the forces.  Returns dict(proposed, void, lost, blocked, filtered, accepted, decided,
+        du_accepted, U, W): the counts over the call's rounds, the sum of dU over the accepted swaps, and U, W of the new
+        diameters; waits."""
+        counts = np.zeros(6, dtype=np.int64)
+        dec = C.c_int64()
+        du, u, w = C.c_double(), C.c_double(), C.c_double()
+        self._chk(self._L.md_swap_rounds(self._h, int(nrounds), float(ktemp), int(first_round),
+                                         counts.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(dec), C.byref(du),
+                                         C.byref(u), C.byref(w)))
+        out = {k: int(v) for k, v in zip(self.SWAP_COUNTS, counts)}
+        out.update(decided=dec.value, du_accepted=du.value, U=u.value, W=w.value)
+        return out
+
+    def swap_last(self):
+        """(partner int32[N], status int32[N], du float64[N]) of the last round, by particle id: the proposer's partner
+        (-1: did not propose), its status (index into SWAP_STATUS) and dU of a decided swap; waits."""
+        partner, status = np.zeros(self.n, dtype=np.int32), np.zeros(self.n, dtype=np.int32)
+        du = np.zeros(self.n)
+        self._chk(self._L.md_swap_last(self._h, _ip(partner), _ip(status), _dp(du)))
+        return partner, status, du
+
+    def diameters(self):
+        """The current diameters float64[N], in particle-id order (md_diameters); waits."""
+        d = np.zeros(self.n)
+        self._chk(self._L.md_diameters(self._h, _dp(d)))
+        return d
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""

@@ -36,8 +36,8 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, orientational=None, sq=None, currents=None, stress=None, four_point=None, clusters=None,
-                   cage=None, bond_order=None):
+                   dynamics=None, orientational=None, swap=None, sq=None, currents=None, stress=None, four_point=None,
+                   clusters=None, cage=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -99,6 +99,15 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     G_l(r) of q_lm in 3-D, g6(r) of psi_6 in 2-D -- on the device, at every orientational.every-th output step.  Its
     marks are bond_order's sample of the same step: bond_order= is required and orientational.every must be a multiple of
     bond_order.every.  Written to pathname/orient_corr.txt.  It never evaluates the potential.  Nothing else the run
+    produces changes.
+
+    swap: a SwapMonteCarlo (montecarlo.py): after every swap.every-th step, swap.rounds rounds of diameter exchanges on
+    the device at the ensemble's target temperature of that step (or swap.ktemp), then the MD goes on from the new
+    diameters and forces.  Unlike the samplers it CHANGES the run.  Its stops are added to the loop's output steps; at a
+    step it shares with samplers it acts after all of them, so they see the frame the MD produced; a trajectory frame or
+    snapshot of that step carries the diameters after the block.  The round counter continues across blocks (and calls
+    with the same object).  After each block state.diameters is refreshed, so frames and final.xyz carry the diameters of
+    their moment.  Written to pathname/swap.txt.  Not available with a user potential.  With swap=None nothing the run
     produces changes."""
     if clusters is not None and clusters.members == "solid":
         if bond_order is None:
@@ -134,9 +143,12 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     if orientational is not None:
         samplers.append(orientational)
     run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
-                                unitcell=state.unitcell, brownian=brownian, bond_order=bond_order)
+                                unitcell=state.unitcell, brownian=brownian, bond_order=bond_order, ensemble=ensemble,
+                                rng=state.rng)
     for s in samplers:
         s._begin(dev, run)
+    if swap is not None:
+        swap._begin(dev, run)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -167,8 +179,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     def collect():
         if pending:
             x, img = dev.snapshot_end()
-            for path, at, mode in pending:
-                writer.submit(_io.write_to_file_lammps, path, at, state.unitcell, n, x, img, state.diameters, dim, mode=mode)
+            for path, at, mode, diam in pending:
+                writer.submit(_io.write_to_file_lammps, path, at, state.unitcell, n, x, img, diam, dim, mode=mode)
             pending.clear()
 
     step = 0
@@ -176,6 +188,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         # run up to and including the next output step (thermo / trajectory cadence, a snapshot time or a sampler's stop)
         stops = [-(-step // frequency) * frequency, _analysis._next_stop(snapshot_times, step)]
         stops += [s._next(step) for s in samplers]
+        if swap is not None:
+            stops.append(swap._next(step))
         last = min(min(t for t in stops if t is not None), total_steps - 1)
         U, W, K = segment(step, last - step + 1)
         collect()                       # the frame exported before this segment: its copy had the whole segment to finish
@@ -183,6 +197,12 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         for s in samplers:
             if s._next(last) == last:
                 s._act(dev, last)
+        if swap is not None and swap._next(last) == last:
+            # after every sampler: they saw the frame the MD produced.  A block replaces state.diameters by a new array
+            # (never in place: a frame in flight keeps the diameters of its own moment)
+            r = swap._act(dev, last)
+            state.diameters = dev.diameters()
+            U, W = r["U"], r["W"]
         want_frame = False
         if last % frequency == 0:
             if brownian:
@@ -200,10 +220,10 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             state.system.energy_and_forces.energy = U
             state.system.energy_and_forces.virial = W
             if write_trajectory:
-                pending.append((trajectory_file, last, "a"))
+                pending.append((trajectory_file, last, "a", state.diameters))
                 want_frame = True
         if _analysis._next_stop(snapshot_times, last) == last:
-            pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w"))
+            pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w", state.diameters))
             want_frame = True
         if want_frame:
             dev.snapshot_begin()
@@ -222,6 +242,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
                       mode="w")
     for s in samplers:
         s._finish(dev, run, pathname)
+    if swap is not None:
+        swap._finish(dev, run, pathname)
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
