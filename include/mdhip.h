@@ -768,6 +768,43 @@ int md_swap_rounds(md_ctx *ctx, int64_t nrounds, double ktemp, int64_t first_rou
 int md_swap_last(md_ctx *ctx, int32_t *partner, int32_t *status, double *du);
 int md_diameters(md_ctx *ctx, double *diameters);
 
+/* Hessian of the pair energy on the device (new relative to the reference): the operator H X, its
+ * diagonal blocks, and the lowest modes by Lanczos with the basis resident on the device.
+ *
+ * With U(r) the pair energy, t = U'(r)/r, k = U''(r), n = (x_i - x_j)/r, over the pairs md_compute_forces takes
+ * (d2 < the accepted threshold in the reference's form, each potential's own cutoff branch inside):
+ *   (H X)_i = sum_j [ (k - t) n (n . (X_i - X_j)) + t (X_i - X_j) ],      H_ii = sum_j [ (k - t) n n^T + t I ].
+ * H is the Hessian of the smooth part: the jump of U or U' at a sharp cutoff (plain LJ) contributes nothing.  t and k are
+ * analytic for MD_POT_LJ, MD_POT_PSEUDOHS, MD_POT_LJ_MODIFIED (all three modes) and MD_POT_POLYDISPERSE; they belong to the
+ * FORCE the library evaluates (t = -f/r, k = -df/dr).
+ * Arithmetic: one lane per particle walks its outer neighbour row in row order; per row entry the D x D block
+ * h_ab = fma((k - t)/d2, del_a del_b, t delta_ab) is formed once (del_a del_b rounded first, so h is symmetric bit for bit)
+ * and applied to X_i - X_j of every vector of the block with fma in component order.  Every pair is evaluated from both
+ * members; no atomics.  Both members of a pair use one rounding of the separation (across a periodic face: the lower
+ * slot's), so the dense matrix equals its transpose bit for bit, a uniform translation gives exactly 0.0, two calls on one
+ * handle are bit-identical, and a column does not depend on the other vectors of its block.
+ *
+ * md_hess_setup: needs a built-in potential and a single-GPU handle; builds the list if it is not valid (as
+ * md_compute_forces would) and freezes the operator on the frame the handle holds.  md_upload, md_run, md_run_brownian,
+ * md_fire_minimize, md_swap_rounds, md_set_potential*, md_set_skin / md_set_inner_skin and every list rebuild invalidate
+ * it: the other md_hess_ calls then fail until md_hess_setup is called again.  md_compute_forces on a valid list does not.
+ * md_hess_apply: X, Y are [m][N][D] by particle index (vector-major; each vector is the D x N column-major matrix the
+ * rest of this ABI uses), 1 <= m <= 8; waits.
+ * md_hess_blocks: diag[N][D][D] by particle index; waits.
+ * md_hess_lanczos: ksteps steps of Lanczos with full reorthogonalisation (classical Gram-Schmidt, two passes, against the
+ * D uniform translations and all earlier basis vectors; the dot products of a pass in one kernel, block partials then a
+ * fixed-order finish, no floating-point atomics), start vector = Philox4x32-10 words keyed by (seed, particle index)
+ * projected against the translations.  The basis (ksteps vectors of N D doubles) stays on the device; when it cannot be
+ * allocated the error names the size.  No host wait inside the loop.  Returns alpha[ksteps] (diagonal) and beta[ksteps]
+ * (beta[j] couples steps j and j + 1; the last is the residual norm).  1 <= ksteps <= N D - D.
+ * md_hess_ritz: Y = V S on the device for S[ksteps][nvec] (row-major; ksteps as in the last md_hess_lanczos), one apply
+ * per block of 8; returns modes[nvec][N][D] by particle index and resid[c] = |H y_c - theta[c] y_c|_2.                */
+int md_hess_setup(md_ctx *ctx);
+int md_hess_apply(md_ctx *ctx, int m, const double *X, double *Y);
+int md_hess_blocks(md_ctx *ctx, double *diag);
+int md_hess_lanczos(md_ctx *ctx, int ksteps, uint64_t seed, double *alpha, double *beta);
+int md_hess_ritz(md_ctx *ctx, int ksteps, int nvec, const double *S, const double *theta, double *modes, double *resid);
+
 /* Library build info: returns e.g. "mdhip 0.1 gfx950". */
 const char *md_version(void);
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "md_cur_setup", "md_cur_sample", "md_cur_last", "md_cur_read", "md_cur_reset",
     "md_mpc_setup", "md_mpc_marks", "md_mpc_sample", "md_mpc_last", "md_mpc_read", "md_mpc_reset",
     "md_swap_setup", "md_swap_rounds", "md_swap_last", "md_diameters",
+    "md_hess_setup", "md_hess_apply", "md_hess_blocks", "md_hess_lanczos", "md_hess_ritz",
 ]
 
 
@@ -262,6 +263,16 @@ def load():
     L.md_swap_last.restype = C.c_int
     L.md_diameters.argtypes = [vp, dp]
     L.md_diameters.restype = C.c_int
+    L.md_hess_setup.argtypes = [vp]
+    L.md_hess_setup.restype = C.c_int
+    L.md_hess_apply.argtypes = [vp, C.c_int, dp, dp]
+    L.md_hess_apply.restype = C.c_int
+    L.md_hess_blocks.argtypes = [vp, dp]
+    L.md_hess_blocks.restype = C.c_int
+    L.md_hess_lanczos.argtypes = [vp, C.c_int, C.c_uint64, dp, dp]
+    L.md_hess_lanczos.restype = C.c_int
+    L.md_hess_ritz.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp]
+    L.md_hess_ritz.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -508,6 +508,100 @@ __device__ __forceinline__ void pair_eval(double d2, double si, double sj, const
     }
 }
 
+// Second derivatives of the built-in potentials, beside pair_eval (md_hess.hpp).  With f(r) the force
+// pair_eval evaluates (fpr = f/r), t = -f/r and k = -df/dr: U'/r and U'' of the smooth branch.  The jump of U or U' at a
+// sharp cutoff contributes nothing.  The acceptance is pair_eval's: each potential's own cutoff branch (plain LJ: the
+// caller's d2 < pp.c2), the same sigma mixing expression, so both members of a pair get the same bits from the same d2.
+// The uniform-diameter forms of pair_eval ((s+s)/2 squared, sig_u) are these expressions at si == sj, bit for bit.
+template <int POT>
+__device__ __forceinline__ void pair_eval2(double d2, double si, double sj, const PotParams &pp, double &t, double &k)
+{
+    if constexpr (POT == POT_LJ) {
+        // U = 4 eps (w3^2 - w3), w3 = (sigma/r)^6:  U'/r = -(w3/r^2)(48 eps w3 - 24 eps),  U'' = (w3/r^2)(624 eps w3 - 168 eps)
+        // (md_rcp, two Newton steps: pair_eval's md_rcp1 is 2e-15 relative, which the r^-8 and r^-14 powers would multiply)
+        double inv = md_rcp(d2);
+        double sg = (si + sj) * 0.5;
+        double w = (sg * sg) * inv;
+        double w3 = (w * w) * w;
+        double wi = w3 * inv;
+        t = -(wi * __builtin_fma(pp.c48, w3, -pp.c24));
+        k = wi * __builtin_fma(13.0 * pp.c48, w3, -(7.0 * pp.c24));
+    } else if constexpr (POT == POT_PSEUDOHS) {
+        // f = A (lambda sr^(lambda+1) - (lambda-1) sr^lambda), sr = sigma/r (pair_eval's force, src/potentials.jl:11-29)
+        double r = sqrt(d2);
+        double sg = (si + sj) / 2.0;
+        double lambda = pp.p[0];
+        t = 0.0;
+        k = 0.0;
+        if (r < 1.0204081632653061) {
+            double sr = sg / r;
+            double pl = pow(sr, lambda);
+            double fij = lambda * (pl * sr) - (lambda - 1.0) * pl;
+            fij *= 134.5526623421209;
+            t = -(fij / r);
+            k = (134.5526623421209 * lambda) * ((lambda + 1.0) * (pl * sr) - (lambda - 1.0) * pl) / r;
+        }
+    } else if constexpr (POT == POT_LJ_MOD) {
+        double r = sqrt(d2);
+        double sg = (si + sj) / 2.0;
+        double eps = pp.p[0], rc = pp.p[2];
+        int mode = (int)pp.p[3];
+        t = 0.0;
+        k = 0.0;
+        if (r < rc) {
+            double sr = sg / r;
+            double sr2 = sr * sr;
+            double sr6 = (sr2 * sr2) * sr2;
+            double sr12 = sr6 * sr6;
+            double V = (4.0 * eps) * (sr12 - sr6);
+            double F = ((24.0 * eps) * (2.0 * sr12 - sr6)) / r;
+            double V2 = ((24.0 * eps) * (26.0 * sr12 - 7.0 * sr6)) / (r * r);
+            double fij, kij;
+            if (mode == 0) {
+                fij = F;
+                kij = V2;
+            } else if (mode == 1) {
+                fij = F - pp.p[6];
+                kij = V2;
+            } else {
+                // f = S F - V S',  -f' = S V'' - 2 F S' + V S''
+                double ron = pp.p[4];
+                double S = 1.0, dS = 0.0, ddS = 0.0;
+                if (r >= ron) {
+                    double rc2 = rc * rc, r2 = r * r, ron2 = ron * ron;
+                    double den = ((rc2 - ron2) * (rc2 - ron2)) * (rc2 - ron2);
+                    double a = rc2 - r2, b = rc2 + 2.0 * r2 - 3.0 * ron2, g = r2 - ron2;
+                    S = ((a * a) * b) / den;
+                    dS = (-12.0 * r * a * g) / den;
+                    ddS = (-12.0 * (a * g - 2.0 * r2 * g + 2.0 * r2 * a)) / den;
+                }
+                fij = S * F - V * dS;
+                kij = S * V2 - 2.0 * F * dS + V * ddS;
+            }
+            t = -(fij / r);
+            k = kij;
+        }
+    } else if constexpr (POT == POT_POLYDISPERSE) {
+        double r = sqrt(d2);
+        double se = 0.5 * (si + sj);
+        se *= (1.0 - pp.p[1] * fabs(si - sj));
+        double rc = pp.p[0];
+        t = 0.0;
+        k = 0.0;
+        if (r < rc * se) {
+            double c2 = 48.0 / md_ipow(rc, 14);
+            double c4 = -21.0 / md_ipow(rc, 16);
+            double se2 = se * se, se4 = se2 * se2, se12 = md_ipow(se, 12);
+            double fij = 12.0 * se12 / md_ipow(r, 13) - 2.0 * c2 * r / se2 - 4.0 * c4 * (r * r * r) / se4;
+            t = -(fij / r);
+            k = 156.0 * se12 / md_ipow(r, 14) + 2.0 * c2 / se2 + 12.0 * c4 * (r * r) / se4;
+        }
+    } else {
+        t = 0.0;
+        k = 0.0;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // list build, stage 1: wrap the owned particles that left [0,L) (src/boundary.jl:7-17
 // arithmetic, applied lazily: only when a particle is actually outside the cell) and count

@@ -22,6 +22,7 @@
 #include "md_cur.hpp"
 #include "md_listrows.hpp"
 #include "md_swap.hpp"
+#include "md_hess.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -577,6 +578,18 @@ struct md_ctx {
         DBuf<double> half, du, part, du_acc;             // n + 2; n; blocks; 1
     } swap;
 
+    // Hessian of the pair energy (md_hess_*): `frozen` = the operator belongs to the frame and the rows the handle holds
+    // right now; everything that moves particles, changes diameters or the potential, or rebuilds the list clears it.
+    // Block staging (xs, ys: n x 8 D, slot-major), the diagonal blocks, and the Lanczos storage: the basis (kcap vectors of
+    // n D), the work vector, chunk partials, pass coefficients, alpha and beta, the Ritz coefficients.
+    struct Hess {
+        bool frozen = false;
+        DBuf<double> xs, ys, diag, host_io;
+        DBuf<double> basis, w, part, coef, alpha, beta, S;
+        int kcap = 0;      // basis vectors allocated
+        int ksteps = 0;    // basis vectors the last md_hess_lanczos filled (0: none, or of an older frame)
+    } hess;
+
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
     // records and whichever buffer set the ping-pong points at: pos / v / f are stale.  Every entry that reads the state
@@ -881,6 +894,7 @@ template <int D>
 void rebuild_t(md_ctx *c)
 {
     hipStream_t st = c->stream;
+    c->hess.frozen = false; // (md_hess_*: the slots are about to be renumbered)
     // sources of this build: a single-GPU handle sorts its n particles; a slab handle sorts the
     // survivors of [0, n_old) plus arrivals, plus the x-halo copies received from its neighbours
     const bool dom = c->dom.on;
@@ -2063,6 +2077,108 @@ void launch_swap_walk(md_ctx *c, const SwapRows &V, const DevState &s, const Swa
     }
 }
 
+// ---- Hessian of the pair energy (md_hess.hpp): launches ---------------------------------------------------------------
+// One apply kernel, two host entry paths: md_hess_apply stages host blocks into slot order around it, the Lanczos loop and
+// md_hess_ritz hand it resident vectors.  X and Y are [slot][M][D]; M is 1, 4 or 8 (hess_block pads a block with zero vectors).
+inline int hess_block(int m) { return m <= 1 ? 1 : (m <= 4 ? 4 : MD_HESS_MAX_M); }
+
+HessPairArgs hess_pair_args(md_ctx *c)
+{
+    HessPairArgs P{};
+    P.pp = c->pp;
+    for (int i = 0; i < 9; ++i) P.Ainv[i] = c->Ainv[i];
+    return P;
+}
+
+template <int D, int POT>
+void launch_hess_apply_p(md_ctx *c, int M, const double *X, double *Y)
+{
+    HessApplyArgs A{hess_pair_args(c), X, Y};
+    switch (M) {
+    case 1:
+        launch_rows<D, HessApplyLane<D, POT, 1>>(c, c->pp.c2, A, "Hessian");
+        break;
+    case 4:
+        launch_rows<D, HessApplyLane<D, POT, 4>>(c, c->pp.c2, A, "Hessian");
+        break;
+    case MD_HESS_MAX_M:
+        launch_rows<D, HessApplyLane<D, POT, MD_HESS_MAX_M>>(c, c->pp.c2, A, "Hessian");
+        break;
+    default:
+        throw HipError("internal: no Hessian apply kernel for this block size");
+    }
+}
+
+template <int D, int POT>
+void launch_hess_diag_p(md_ctx *c, int, const double *, double *diag)
+{
+    launch_rows<D, HessDiagLane<D, POT>>(c, c->pp.c2, HessDiagArgs{hess_pair_args(c), diag}, "Hessian");
+}
+
+#define MD_HESS_DISPATCH(fn, c, M, X, Y)                                                                            \
+    do {                                                                                                            \
+        const bool d3_ = (c)->dim == 3;                                                                             \
+        switch ((c)->pot_kind) {                                                                                    \
+        case POT_LJ:                                                                                                \
+            d3_ ? fn<3, POT_LJ>(c, M, X, Y) : fn<2, POT_LJ>(c, M, X, Y);                                            \
+            break;                                                                                                  \
+        case POT_PSEUDOHS:                                                                                          \
+            d3_ ? fn<3, POT_PSEUDOHS>(c, M, X, Y) : fn<2, POT_PSEUDOHS>(c, M, X, Y);                                \
+            break;                                                                                                  \
+        case POT_POLYDISPERSE:                                                                                      \
+            d3_ ? fn<3, POT_POLYDISPERSE>(c, M, X, Y) : fn<2, POT_POLYDISPERSE>(c, M, X, Y);                        \
+            break;                                                                                                  \
+        case POT_LJ_MOD:                                                                                            \
+            d3_ ? fn<3, POT_LJ_MOD>(c, M, X, Y) : fn<2, POT_LJ_MOD>(c, M, X, Y);                                    \
+            break;                                                                                                  \
+        default:                                                                                                    \
+            throw HipError("md_hess: not available with a user potential (MD_POT_CUSTOM)");                         \
+        }                                                                                                           \
+        HIPCHK(hipGetLastError());                                                                                  \
+    } while (0)
+
+void launch_hess_apply(md_ctx *c, int M, const double *X, double *Y) { MD_HESS_DISPATCH(launch_hess_apply_p, c, M, X, Y); }
+void launch_hess_diag(md_ctx *c, double *diag) { MD_HESS_DISPATCH(launch_hess_diag_p, c, 0, (const double *)nullptr, diag); }
+
+// The operator of the frame the handle holds, or a refusal: never a stale frame.
+md_ctx::Hess &hess_of(md_ctx *ctx, const char *who)
+{
+    if (ctx->dom.on) throw HipError(std::string(who) + ": not available on a slab-decomposition handle");
+    if (ctx->pot_kind == POT_CUSTOM) throw HipError(std::string(who) + ": not available with a user potential (MD_POT_CUSTOM)");
+    if (!ctx->hess.frozen || !ctx->list_valid || ctx->state_invalid)
+        throw HipError(std::string(who) + ": no operator for the frame the handle holds now (md_upload, md_run*, md_fire_minimize, "
+                                          "md_swap_rounds, a change of the potential or a list rebuild since md_hess_setup "
+                                          "invalidate it): call md_hess_setup");
+    return ctx->hess;
+}
+
+// One Gram-Schmidt pass of w against the translations and the first nb basis vectors; mode / qa / out: k_hess_dots_finish
+void hess_gs_pass(md_ctx *c, int nb, int mode, double *out)
+{
+    md_ctx::Hess &H = c->hess;
+    const int D = c->dim;
+    const size_t nd = (size_t)c->n * D;
+    const int nchunk = (int)((nd + MD_HESS_CHUNK - 1) / MD_HESS_CHUNK);
+    const int nq = D + nb;
+    const double rsn = 1.0 / std::sqrt((double)c->n);
+    hipStream_t st = c->stream;
+    k_hess_dots<<<dim3(nchunk, (nq + MD_HESS_QPB - 1) / MD_HESS_QPB), MD_BLOCK, 0, st>>>(nd, D, rsn, H.basis.p, H.w.p, 0, nq, 0, H.part.p);
+    k_hess_dots_finish<<<nq, MD_BLOCK, 0, st>>>(nchunk, H.part.p, H.coef.p, mode, nq - 1, out);
+    k_hess_update<<<(unsigned)((nd + MD_BLOCK - 1) / MD_BLOCK), MD_BLOCK, 0, st>>>(nd, D, rsn, H.basis.p, H.coef.p, nq, H.w.p);
+}
+
+// |w| into norm_out[0], then (dst != nullptr) dst = w / |w|
+void hess_normalise(md_ctx *c, double *norm_out, double *dst)
+{
+    md_ctx::Hess &H = c->hess;
+    const size_t nd = (size_t)c->n * c->dim;
+    const int nchunk = (int)((nd + MD_HESS_CHUNK - 1) / MD_HESS_CHUNK);
+    hipStream_t st = c->stream;
+    k_hess_dots<<<nchunk, MD_BLOCK, 0, st>>>(nd, c->dim, 0.0, H.basis.p, H.w.p, 0, 1, 1, H.part.p);
+    k_hess_dots_finish<<<1, MD_BLOCK, 0, st>>>(nchunk, H.part.p, H.coef.p, 3, -1, norm_out);
+    if (dst) k_hess_scale<<<(unsigned)((nd + MD_BLOCK - 1) / MD_BLOCK), MD_BLOCK, 0, st>>>(nd, H.w.p, norm_out, dst);
+}
+
 } // namespace
 
 struct FusedScope { // md_run / slab windows: marks the handle's state invalid when the fused loop is left by an exception
@@ -2325,6 +2441,7 @@ int md_set_potential(md_ctx *ctx, int kind, const double *params, int nparams)
     }
     ctx->pot_kind = kind;
     ctx->list_valid = false; // the LDS record stride of the rows depends on the potential kind
+    ctx->hess.frozen = false;
     configure_potential(ctx);
     API_END
 }
@@ -2344,6 +2461,7 @@ int md_set_potential_source(md_ctx *ctx, const char *hip_src, const char *entry_
     for (int i = 0; i < 8; ++i) ctx->pp.p[i] = (i < nparams) ? params[i] : 0.0;
     ctx->pot_kind = POT_CUSTOM;
     ctx->list_valid = false;
+    ctx->hess.frozen = false;
     configure_potential(ctx);
     API_END
 }
@@ -2388,6 +2506,7 @@ int md_upload(md_ctx *ctx, const double *x, const double *v, const double *f, co
     API_BEGIN
     size_t nd = (size_t)ctx->n * ctx->dim;
     hipStream_t st = ctx->stream;
+    ctx->hess.frozen = false;
     if (x) {
         ctx->io_x.ensure(nd);
         HIPCHK(hipMemcpyAsync(ctx->io_x.p, x, nd * sizeof(double), hipMemcpyHostToDevice, st));
@@ -4187,6 +4306,7 @@ int md_swap_rounds(md_ctx *ctx, int64_t nrounds, double ktemp, int64_t first_rou
         throw HipError("md_swap_rounds: not available for a run-time compiled potential (its pair energy is not reachable "
                        "from the swap kernel)");
     if (ctx->uniform_sigma) throw HipError("md_swap_rounds: all diameters are equal: there is nothing to exchange");
+    ctx->hess.frozen = false; // (diameters are about to change)
     if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
     hipStream_t st = ctx->stream;
     const int n = (int)ctx->n;
@@ -4306,6 +4426,159 @@ int md_diameters(md_ctx *ctx, double *diameters)
     API_END
 }
 
+// ---------------------------------------------------------------------------------------------
+// Hessian of the pair energy (md_hess.hpp): walks the OUTER rows as md_stress_sample does, reads
+// positions and diameters and writes only its own buffers.
+int md_hess_setup(md_ctx *ctx)
+{
+    API_BEGIN
+    require_state(ctx, "md_hess_setup");
+    if (ctx->dom.on) throw HipError("md_hess_setup: not available on a slab-decomposition handle");
+    if (ctx->pot_kind == POT_CUSTOM) throw HipError("md_hess_setup: not available with a user potential (MD_POT_CUSTOM)");
+    if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
+    ctx->hess.ksteps = 0;
+    ctx->hess.frozen = true;
+    API_END
+}
+
+int md_hess_apply(md_ctx *ctx, int m, const double *X, double *Y)
+{
+    API_BEGIN
+    md_ctx::Hess &H = hess_of(ctx, "md_hess_apply");
+    check_range("md_hess_apply", "m", m, 1, MD_HESS_MAX_M);
+    if (!X || !Y) throw HipError("md_hess_apply: X / Y is null");
+    const int n = (int)ctx->n, D = ctx->dim, M = hess_block(m);
+    const size_t nd = (size_t)n * D;
+    hipStream_t st = ctx->stream;
+    H.host_io.ensure(nd * m);
+    H.xs.ensure(nd * M);
+    H.ys.ensure(nd * M);
+    const int32_t *id = ctx->dev(ctx->cur).id;
+    HIPCHK(hipMemcpyAsync(H.host_io.p, X, sizeof(double) * nd * m, hipMemcpyHostToDevice, st));
+    k_hess_import<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, id, D, m, M, H.host_io.p, H.xs.p);
+    launch_hess_apply(ctx, M, H.xs.p, H.ys.p);
+    k_hess_export<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, id, D, m, M, H.ys.p, H.host_io.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(Y, H.host_io.p, sizeof(double) * nd * m, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_hess_blocks(md_ctx *ctx, double *diag)
+{
+    API_BEGIN
+    md_ctx::Hess &H = hess_of(ctx, "md_hess_blocks");
+    if (!diag) throw HipError("md_hess_blocks: diag is null");
+    const int n = (int)ctx->n, D = ctx->dim;
+    const size_t nb = (size_t)n * D * D;
+    hipStream_t st = ctx->stream;
+    H.diag.ensure(nb);
+    H.host_io.ensure(nb);
+    launch_hess_diag(ctx, H.diag.p);
+    k_hess_export<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, ctx->dev(ctx->cur).id, D * D, 1, 1, H.diag.p, H.host_io.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(diag, H.host_io.p, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_hess_lanczos(md_ctx *ctx, int ksteps, uint64_t seed, double *alpha, double *beta)
+{
+    API_BEGIN
+    md_ctx::Hess &H = hess_of(ctx, "md_hess_lanczos");
+    const int n = (int)ctx->n, D = ctx->dim;
+    const size_t nd = (size_t)n * D;
+    if (nd <= (size_t)D) throw HipError("md_hess_lanczos: no degrees of freedom besides the translations");
+    check_range("md_hess_lanczos", "ksteps", ksteps, 1, (int)std::min<size_t>(nd - D, 1 << 20));
+    if (!alpha || !beta) throw HipError("md_hess_lanczos: alpha / beta is null");
+    H.ksteps = 0;
+    if (ksteps > H.kcap) {
+        H.kcap = 0;
+        const size_t bytes = sizeof(double) * nd * (size_t)ksteps;
+        char what[160];
+        snprintf(what, sizeof what, "a Lanczos basis of %d vectors of %zu doubles", ksteps, nd);
+        alloc_or_refuse("md_hess_lanczos", "MDHIP_HESS_LIMIT", bytes, what, std::make_pair(&H.basis, nd * (size_t)ksteps));
+        H.kcap = ksteps;
+    }
+    const int nchunk = (int)((nd + MD_HESS_CHUNK - 1) / MD_HESS_CHUNK);
+    H.w.ensure(nd);
+    H.part.ensure((size_t)(D + ksteps) * nchunk);
+    H.coef.ensure((size_t)D + ksteps + 1);
+    H.alpha.ensure(ksteps);
+    H.beta.ensure(ksteps);
+    hipStream_t st = ctx->stream;
+    double *V = H.basis.p;
+    double *scratch = H.coef.p + D + ksteps; // |start vector|
+    k_hess_start<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, ctx->dev(ctx->cur).id, D, (unsigned long long)seed, H.w.p);
+    hess_gs_pass(ctx, 0, 0, nullptr);
+    hess_gs_pass(ctx, 0, 0, nullptr);
+    hess_normalise(ctx, scratch, V);
+    for (int j = 0; j < ksteps; ++j) { // no host wait in here
+        launch_hess_apply(ctx, 1, V + (size_t)j * nd, H.w.p);
+        hess_gs_pass(ctx, j + 1, 1, H.alpha.p + j);
+        hess_gs_pass(ctx, j + 1, 2, H.alpha.p + j);
+        hess_normalise(ctx, H.beta.p + j, j + 1 < ksteps ? V + (size_t)(j + 1) * nd : nullptr);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(alpha, H.alpha.p, sizeof(double) * ksteps, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(beta, H.beta.p, sizeof(double) * ksteps, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int j = 0; j < ksteps; ++j)
+        if (!std::isfinite(alpha[j]) || !std::isfinite(beta[j]) || (j + 1 < ksteps && !(beta[j] > 0.0))) {
+            char b[200];
+            snprintf(b, sizeof b, "md_hess_lanczos: the iteration broke down at step %d (alpha = %g, beta = %g): an invariant "
+                                  "subspace was exhausted; use fewer steps or another seed", j, alpha[j], beta[j]);
+            throw HipError(b);
+        }
+    H.ksteps = ksteps;
+    API_END
+}
+
+int md_hess_ritz(md_ctx *ctx, int ksteps, int nvec, const double *S, const double *theta, double *modes, double *resid)
+{
+    API_BEGIN
+    md_ctx::Hess &H = hess_of(ctx, "md_hess_ritz");
+    if (H.ksteps <= 0) throw HipError("md_hess_ritz: no Lanczos basis for this frame (call md_hess_lanczos first)");
+    if (ksteps != H.ksteps) {
+        char b[160];
+        snprintf(b, sizeof b, "md_hess_ritz: ksteps = %d, but the basis on the device holds %d vectors", ksteps, H.ksteps);
+        throw HipError(b);
+    }
+    check_range("md_hess_ritz", "nvec", nvec, 1, ksteps);
+    if (!S || !theta || !modes || !resid) throw HipError("md_hess_ritz: S / theta / modes / resid is null");
+    const int n = (int)ctx->n, D = ctx->dim;
+    const size_t nd = (size_t)n * D;
+    hipStream_t st = ctx->stream;
+    const int32_t *id = ctx->dev(ctx->cur).id;
+    H.S.ensure((size_t)ksteps * nvec);
+    H.xs.ensure(nd * MD_HESS_MAX_M);
+    H.ys.ensure(nd * MD_HESS_MAX_M);
+    H.host_io.ensure(nd * MD_HESS_MAX_M);
+    HIPCHK(hipMemcpyAsync(H.S.p, S, sizeof(double) * (size_t)ksteps * nvec, hipMemcpyHostToDevice, st));
+    std::vector<double> hy(nd * MD_HESS_MAX_M);
+    for (int c0 = 0; c0 < nvec; c0 += MD_HESS_MAX_M) {
+        const int m = std::min(MD_HESS_MAX_M, nvec - c0), M = hess_block(m);
+        k_hess_combine<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, D, nd, ksteps, nvec, c0, M, H.basis.p, H.S.p, H.xs.p);
+        launch_hess_apply(ctx, M, H.xs.p, H.ys.p);
+        k_hess_export<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, id, D, m, M, H.xs.p, H.host_io.p);
+        HIPCHK(hipMemcpyAsync(modes + (size_t)c0 * nd, H.host_io.p, sizeof(double) * nd * m, hipMemcpyDeviceToHost, st));
+        k_hess_export<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, id, D, m, M, H.ys.p, H.host_io.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(hy.data(), H.host_io.p, sizeof(double) * nd * m, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (int c = 0; c < m; ++c) { // |H y - theta y|, elements in particle-id order
+            const double *y = modes + (size_t)(c0 + c) * nd, *h = hy.data() + (size_t)c * nd;
+            double a = 0.0;
+            for (size_t e = 0; e < nd; ++e) {
+                double r = h[e] - theta[c0 + c] * y[e];
+                a += r * r;
+            }
+            resid[c0 + c] = std::sqrt(a);
+        }
+    }
+    API_END
+}
+
 static void debug_tile_halos(md_ctx *ctx);
 int md_run(md_ctx *ctx, int64_t nsteps, double dt, int ensemble, double tau, double nf, const double *ktemp,
            const double *r1, const double *r2, double *uwk)
@@ -4323,6 +4596,7 @@ int md_run(md_ctx *ctx, int64_t nsteps, double dt, int ensemble, double tau, dou
         return 0;
     }
     hipStream_t st = ctx->stream;
+    ctx->hess.frozen = false;
     double term1 = 0.0;
     if (nvt) {
         ctx->d_kt.ensure(nsteps);

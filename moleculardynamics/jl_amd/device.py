@@ -624,6 +624,52 @@ class MDDevice:
         self._chk(self._L.md_diameters(self._h, _dp(d)))
         return d
 
+    # -- Hessian of the pair energy --------------------------------------------------------
+    HESS_MAX_BLOCK = 8
+
+    def hess_setup(self):
+        """Freeze the Hessian operator on the frame the handle holds (md_hess_setup): built-in potentials only; builds the
+        list when it is not valid.  Any upload, run, minimisation, swap round or list rebuild invalidates it."""
+        self._chk(self._L.md_hess_setup(self._h))
+
+    def hess_apply(self, X):
+        """Y = H X for a block X float64[m, N, d] (by particle id), 1 <= m <= 8 (md_hess_apply); waits."""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        if X.ndim != 3 or X.shape[1:] != (self.n, self.dim) or not 1 <= X.shape[0] <= self.HESS_MAX_BLOCK:
+            raise ValueError(f"expected a block of shape (m, {self.n}, {self.dim}) with 1 <= m <= {self.HESS_MAX_BLOCK}, "
+                             f"got {X.shape}")
+        Y = np.empty_like(X)
+        self._chk(self._L.md_hess_apply(self._h, int(X.shape[0]), _dp(X), _dp(Y)))
+        return Y
+
+    def hess_blocks(self):
+        """The diagonal blocks H_ii, float64[N, d, d] by particle id (md_hess_blocks); waits."""
+        out = np.empty((self.n, self.dim, self.dim))
+        self._chk(self._L.md_hess_blocks(self._h, _dp(out)))
+        return out
+
+    def hess_lanczos(self, ksteps, seed=0):
+        """ksteps Lanczos steps with full reorthogonalisation, the basis resident on the device (md_hess_lanczos).  Returns
+        (alpha[ksteps], beta[ksteps]): the tridiagonal matrix has diagonal alpha and off-diagonal beta[:-1]; waits."""
+        ksteps = int(ksteps)
+        if ksteps < 1:
+            raise ValueError("ksteps must be >= 1")
+        a, b = np.empty(ksteps), np.empty(ksteps)
+        self._chk(self._L.md_hess_lanczos(self._h, ksteps, C.c_uint64(int(seed) & (2 ** 64 - 1)), _dp(a), _dp(b)))
+        return a, b
+
+    def hess_ritz(self, S, theta):
+        """Ritz vectors Y = V S of the last hess_lanczos basis for S float64[ksteps, nvec] and the values theta[nvec]
+        (md_hess_ritz).  Returns (modes float64[nvec, N, d] by particle id, resid[nvec] = |H y - theta y|); waits."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        if S.ndim != 2 or S.shape[1] < 1:
+            raise ValueError("S must have shape (ksteps, nvec) with nvec >= 1")
+        theta = _f64(theta, (S.shape[1],))
+        modes = np.empty((S.shape[1], self.n, self.dim))
+        resid = np.empty(S.shape[1])
+        self._chk(self._L.md_hess_ritz(self._h, int(S.shape[0]), int(S.shape[1]), _dp(S), _dp(theta), _dp(modes), _dp(resid)))
+        return modes, resid
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""
