@@ -14,36 +14,12 @@ import os
 import numpy as np
 import pytest
 
+from tests.dyn_reference import bin_counts as _bin, restate as _restate
 from tests.util import lj_system, poly_system
 
 pytestmark = pytest.mark.gpu
 LJ = [1.0, 1.0, 2.5]
 Q4 = [1.0, 2.0 * math.pi, 7.0, 11.3]
-
-
-def _restate(x0, n0, x1, n1, U):
-    """del_c = (x1 - x0) + ((U_c0 dn0 + U_c1 dn1) + U_c2 dn2), d2 = (del0^2 + del1^2) + del2^2, each operation rounded."""
-    d = x0.shape[1]
-    dn = n1.astype(np.float64) - n0.astype(np.float64)
-    de = np.empty_like(x0)
-    for c in range(d):
-        t = U[c, 0] * dn[:, 0] + U[c, 1] * dn[:, 1]
-        if d == 3:
-            t = t + U[c, 2] * dn[:, 2]
-        de[:, c] = (x1[:, c] - x0[:, c]) + t
-    d2 = de[:, 0] * de[:, 0] + de[:, 1] * de[:, 1]
-    if d == 3:
-        d2 = d2 + de[:, 2] * de[:, 2]
-    return de, d2
-
-
-def _bin(d2, r_max, nbins):
-    delta = r_max / nbins
-    rk = np.arange(nbins + 1, dtype=np.float64) * delta
-    e2 = rk * rk
-    d2 = d2[d2 < e2[-1]]
-    k = np.searchsorted(e2, d2, "right") - 1
-    return np.bincount(k, minlength=nbins).astype(np.int64)
 
 
 def _device(s, cutoff=2.5, pot=LJ, kind=0):

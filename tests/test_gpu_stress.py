@@ -13,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+from tests.pair_reference import canon_delta as _canon_delta, d2_of as _d2, tric_delta as _tric_delta
 from tests.util import lj_system, poly_system
 
 pytestmark = pytest.mark.gpu
@@ -23,49 +24,6 @@ TRIC_U = np.array([[18.0, 4.5, 0.0], [0.0, 17.5, 0.0], [0.0, 0.0, 18.0]])   # te
 
 def _comp(d):
     return [(0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)] if d == 3 else [(0, 0), (1, 1), (0, 1)]
-
-
-def _canon_delta(x, box, pairs):
-    """oracle/md_oracle.c canon_d2's displacement for the (a < b) pairs: b translated, every operation rounded on its own
-    (the form _canon_d2 of tests/test_gpu_rdf.py squares)."""
-    a, b = x[pairs[:, 0]], x[pairs[:, 1]]
-    L = np.asarray(box, dtype=np.float64)
-    d0 = b - a
-    half = 0.5 * L
-    s = np.where(d0 > half, -1.0, np.where(d0 < -half, 1.0, 0.0))
-    return (b + s * L) - a
-
-
-def _tric_delta(x, U, pairs):
-    """oracle/md_oracle.c tric_d2's displacement: the 3^d translations t_r = (s0 U_r0 + s1 U_r1) + s2 U_r2 in its loop
-    order, the first strict minimum of d2 kept."""
-    d = x.shape[1]
-    a, b = x[pairs[:, 0]], x[pairs[:, 1]]
-    best = np.full(len(pairs), 1e300)
-    out = np.zeros_like(a)
-    for s2 in ((-1, 0, 1) if d == 3 else (0,)):
-        for s1 in (-1, 0, 1):
-            for s0 in (-1, 0, 1):
-                de = np.empty_like(a)
-                for r in range(d):
-                    t = float(s0) * U[r, 0] + float(s1) * U[r, 1]
-                    if d == 3:
-                        t = t + float(s2) * U[r, 2]
-                    de[:, r] = (b[:, r] + t) - a[:, r]
-                d2 = de[:, 0] * de[:, 0] + de[:, 1] * de[:, 1]
-                if d == 3:
-                    d2 = d2 + de[:, 2] * de[:, 2]
-                better = d2 < best
-                best = np.where(better, d2, best)
-                out[better] = de[better]
-    return out
-
-
-def _d2(de):
-    d2 = de[:, 0] * de[:, 0] + de[:, 1] * de[:, 1]
-    if de.shape[1] == 3:
-        d2 = d2 + de[:, 2] * de[:, 2]
-    return d2
 
 
 def _virial_ref(oracle, pot, de, pairs, diam):
