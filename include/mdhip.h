@@ -805,6 +805,49 @@ int md_hess_blocks(md_ctx *ctx, double *diag);
 int md_hess_lanczos(md_ctx *ctx, int ksteps, uint64_t seed, double *alpha, double *beta);
 int md_hess_ritz(md_ctx *ctx, int ksteps, int nvec, const double *S, const double *theta, double *modes, double *resid);
 
+/* Elastic moduli of the frame md_hess_setup froze -- meant for a minimum (md_fire_minimize) -- on the device (new relative
+ * to the reference): the Born term, the affine force field, and the non-affine term by conjugate
+ * gradients around the operator of md_hess_apply.
+ *
+ * Definitions.  del = x_j(+translation) - x_i, r = |del|, t = U'/r, k = U'', c = (k - t)/r^2, over the pairs of md_hess_*;
+ * V = |det(cell)|.  Strain is the Green-Lagrange tensor eta: r'^2 = r^2 + 2 del^T eta del.  eta_ab and eta_ba are ONE
+ * tensor component; no engineering factor 2 and no Voigt factor appears anywhere.
+ *   stress     sigma_ab  = (1/V) sum_pairs t del_a del_b            (= -W_ab / V of md_stress_*; tension is positive)
+ *   Born       CB_abcd   = (1/V) sum_pairs c del_a del_b del_c del_d   (totally symmetric)
+ *   affine     Xi_{i,c;ab} = d2U / dx_ic d eta_ab = sum_j [ -c del_a del_b del_c - t (delta_ac del_b + delta_bc del_a) ]
+ *   non-affine u_ab = -H^+ Xi_ab  on the space orthogonal to the uniform translations;   N_st = (1/V) Xi_s . u_t
+ *   moduli     C = CB + N = (1/V) d2 U_min / d eta d eta along the relaxed path (the caller adds; see vibrations.py)
+ * Like H these belong to the smooth part of the energy: a jump of U or U' at a sharp cutoff contributes nothing.
+ * Components, everywhere: 3-D xx, yy, zz, xy, xz, yz (nc = 6); 2-D xx, yy, xy (nc = 3) -- md_stress_tensor's order.
+ * Arrays [nc][nc] are row-major tensor components C_{(ab)(cd)}.
+ *
+ * md_elas_affine: one lane per particle walks its outer row in row order and adds, per accepted pair, its Xi term and its
+ * half of the stress and Born sums (fma, fp64, no atomics); both members of a pair use the same separation bits (md_hess_*),
+ * so their Xi terms are exact negatives.  The sums: lanes by block_sum, blocks in block order, times 0.5 (exact) and 1/V
+ * once; born[s][t] is filled from the one sum of its sorted index set, so born equals its transpose bit for bit.  Like the
+ * stress tensor the sums depend on the row order: bit-reproducible on one handle, equal to rounding across handles; Xi of a
+ * particle is a function of the frame and of its row order.  stress[nc], born[nc][nc]; xi is [nc][N][D] by particle index
+ * or NULL.  Waits.
+ * md_elas_solve: needs md_elas_affine of the SAME md_hess_setup.  Column-wise conjugate gradients for the nc right-hand
+ * sides at once, all vectors resident: per iteration one block apply of H, p . H p and r . r by chunk partials and a
+ * fixed-order finish that forms alpha_c and beta_c on the device, x += alpha p and r -= alpha H p in one kernel, p = r +
+ * beta p in one; no floating-point atomics; the host polls the device-side status once per 32 iterations.  A column is
+ * frozen once |r_c| <= tol |Xi_c| (its iteration count is kept) or once p . H p <= 0 (MD_ELAS_INDEFINITE).  The right-hand
+ * side and the solution are projected once each against the uniform translation of the particles that have a bond; a
+ * particle without one (a zero row of H, zero Xi) gets exactly 0.0.  Returns per column iters[nc], resid[nc] = the TRUE
+ * |H u_c + Xi_c|_2 from one more apply, xi_norm[nc] = |Xi_c|_2 (projected); *status = MD_ELAS_CONVERGED (every column met
+ * tol) | MD_ELAS_MAX_ITER (some column still iterating after max_iter) | MD_ELAS_INDEFINITE; nonaffine[nc][nc] = N_st, not
+ * symmetrised (N - N^T measures the solve's error); u is [nc][N][D] by particle index or NULL.  tol > 0, max_iter >= 1.
+ * A saddle or non-convergence is reported in *status, not as an error.  Waits.
+ * Both need a frozen operator, a built-in potential and a single-GPU handle, and fail like md_hess_apply otherwise:
+ * whatever invalidates the operator invalidates both until md_hess_setup is called again.                              */
+#define MD_ELAS_CONVERGED 1
+#define MD_ELAS_MAX_ITER 2
+#define MD_ELAS_INDEFINITE 4
+int md_elas_affine(md_ctx *ctx, double *stress, double *born, double *xi);
+int md_elas_solve(md_ctx *ctx, double tol, int64_t max_iter, int64_t *iters, double *resid, double *xi_norm, int *status,
+                  double *nonaffine, double *u);
+
 /* Library build info: returns e.g. "mdhip 0.1 gfx950". */
 const char *md_version(void);
 

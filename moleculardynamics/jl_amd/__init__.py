@@ -14,7 +14,7 @@ from .analysis import (RadialDistribution, compute_rdf, SelfDynamics, StructureF
                        compute_orientational_correlation, compute_marked_correlation)
 from .minimize import fire_minimize, minimize
 from .montecarlo import SwapMonteCarlo, swap_rounds
-from .vibrations import HessianOperator, lowest_modes, participation_ratio
+from .vibrations import HessianOperator, elastic_moduli, lowest_modes, participation_ratio
 from .device import MDDevice
 from ._lib import MdhipError
 
@@ -27,4 +27,5 @@ __all__ = [
     "StressTensor", "compute_stress", "BondOrder", "compute_bond_order", "ClusterAnalysis", "compute_clusters", "CageDynamics",
     "FourPoint", "CurrentCorrelations", "OrientationalCorrelation", "compute_orientational_correlation",
     "compute_marked_correlation", "SwapMonteCarlo", "swap_rounds", "HessianOperator", "lowest_modes", "participation_ratio",
+    "elastic_moduli",
 ]

@@ -14,6 +14,7 @@ MD_NVE, MD_NVT = 0, 1
 MD_CLUSTER_ALL, MD_CLUSTER_SOLID = 0, 1
 MD_MPC_BOO, MD_MPC_USER = 0, 1
 MD_LIST_ROWS_INFO = 16
+MD_ELAS_CONVERGED, MD_ELAS_MAX_ITER, MD_ELAS_INDEFINITE = 1, 2, 4
 
 # every symbol include/mdhip.h declares
 EXPORTS = [
@@ -39,6 +40,7 @@ EXPORTS = [
     "md_mpc_setup", "md_mpc_marks", "md_mpc_sample", "md_mpc_last", "md_mpc_read", "md_mpc_reset",
     "md_swap_setup", "md_swap_rounds", "md_swap_last", "md_diameters",
     "md_hess_setup", "md_hess_apply", "md_hess_blocks", "md_hess_lanczos", "md_hess_ritz",
+    "md_elas_affine", "md_elas_solve",
 ]
 
 
@@ -273,6 +275,10 @@ def load():
     L.md_hess_lanczos.restype = C.c_int
     L.md_hess_ritz.argtypes = [vp, C.c_int, C.c_int, dp, dp, dp, dp]
     L.md_hess_ritz.restype = C.c_int
+    L.md_elas_affine.argtypes = [vp, dp, dp, dp]
+    L.md_elas_affine.restype = C.c_int
+    L.md_elas_solve.argtypes = [vp, C.c_double, C.c_int64, i64p, dp, dp, C.POINTER(C.c_int), dp, dp]
+    L.md_elas_solve.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -29,10 +29,11 @@ struct HessPairArgs {
     double Ainv[9]; // U^-1, row-major (the handle's), for the lattice signs of a translated neighbour
 };
 
-// The block of one row entry that the walk accepted (hit): false when the pair contributes nothing.
+// The separation both members of a pair share (see above), and t = U'/r, k = U'' at it: false when the pair contributes
+// nothing.  dx, dy, dz, d2 come in as the walk formed them and go out as the shared form.  (md_elas.hpp uses it too.)
 template <int D, int POT>
-__device__ __forceinline__ bool hess_pair(const HessPairArgs &P, const DevState &s, int kk, const double4 &pi, double dx, double dy,
-                                          double dz, double d2, uint32_t own, double (&h)[D][D])
+__device__ __forceinline__ bool hess_sep(const HessPairArgs &P, const DevState &s, int kk, const double4 &pi, double &dx, double &dy,
+                                         double &dz, double &d2, uint32_t own, double &t, double &k)
 {
 #pragma clang fp contract(off)
     if ((int)own == kk) return false; // (a particle's own periodic image: U does not depend on x_i through it)
@@ -60,8 +61,18 @@ __device__ __forceinline__ bool hess_pair(const HessPairArgs &P, const DevState 
         d2 = d2_ref<D>(dx, dy, dz);
         if (!(d2 < P.pp.c2)) return false;
     }
-    double t, k;
     pair_eval2<POT>(d2, pi.w, pj.w, P.pp, t, k);
+    return true;
+}
+
+// The block of one row entry that the walk accepted (hit): false when the pair contributes nothing.
+template <int D, int POT>
+__device__ __forceinline__ bool hess_pair(const HessPairArgs &P, const DevState &s, int kk, const double4 &pi, double dx, double dy,
+                                          double dz, double d2, uint32_t own, double (&h)[D][D])
+{
+#pragma clang fp contract(off)
+    double t, k;
+    if (!hess_sep<D, POT>(P, s, kk, pi, dx, dy, dz, d2, own, t, k)) return false;
     const double c = (k - t) * md_rcp(d2);
     const double del[3] = {dx, dy, dz};
 #pragma unroll

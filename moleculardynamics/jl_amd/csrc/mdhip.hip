@@ -23,6 +23,7 @@
 #include "md_listrows.hpp"
 #include "md_swap.hpp"
 #include "md_hess.hpp"
+#include "md_elas.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -588,7 +589,19 @@ struct md_ctx {
         DBuf<double> basis, w, part, coef, alpha, beta, S;
         int kcap = 0;      // basis vectors allocated
         int ksteps = 0;    // basis vectors the last md_hess_lanczos filled (0: none, or of an older frame)
+        uint64_t epoch = 0; // md_hess_setup calls so far: names the operator to whatever derives state from it (md_elas_*)
     } hess;
+
+    // Elastic moduli (md_elas_*): `epoch` = the md_hess_setup whose operator the affine pass walked (0: none); whatever
+    // clears hess.frozen forces a new md_hess_setup and with it a new epoch, so there is no second flag to clear.  The
+    // affine force field xi and the solver's vectors (n x M D each, slot-major, M = hess_block(nc)), which particles have
+    // a bond, the block / chunk partials, the finished sums and the solver's scalars.
+    struct Elas {
+        uint64_t epoch = 0;
+        DBuf<double> xi, x, r, p, hp, part, sums, mean, out, host_io;
+        DBuf<int32_t> bonded;
+        DBuf<ElasScal> sc;
+    } elas;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -2150,6 +2163,133 @@ md_ctx::Hess &hess_of(md_ctx *ctx, const char *who)
                                           "md_swap_rounds, a change of the potential or a list rebuild since md_hess_setup "
                                           "invalidate it): call md_hess_setup");
     return ctx->hess;
+}
+
+// ---- elastic moduli (md_elas.hpp): launches ---------------------------------------------------------------------------
+template <int D, int POT>
+void launch_elas_affine_p(md_ctx *c, int, const double *, double *)
+{
+    md_ctx::Elas &E = c->elas;
+    ElasAffineArgs A{hess_pair_args(c), E.xi.p, E.bonded.p, E.part.p, c->nblk};
+    launch_rows<D, ElasAffineLane<D, POT>>(c, c->pp.c2, A, "elasticity");
+}
+
+void launch_elas_affine(md_ctx *c) { MD_HESS_DISPATCH(launch_elas_affine_p, c, 0, (const double *)nullptr, (double *)nullptr); }
+
+// The operator md_hess_setup froze, with the affine pass of that very operator when `need_affine`
+md_ctx::Elas &elas_of(md_ctx *ctx, const char *who, bool need_affine)
+{
+    md_ctx::Hess &H = hess_of(ctx, who);
+    if (need_affine && ctx->elas.epoch != H.epoch)
+        throw HipError(std::string(who) + ": no affine pass for the operator the last md_hess_setup froze (call md_elas_affine first)");
+    return ctx->elas;
+}
+
+// The solver's launches for one dimension: M = hess_block(nc) vectors, npair = n M (slot, vector) pairs in nchunk chunks
+template <int D>
+struct ElasLaunch {
+    static constexpr int M = ElasShape<D>::M;
+    md_ctx *c;
+    ElasVecs V;
+    int nchunk;
+    double tol;
+    hipStream_t st;
+    void scalars(int mode) { k_elas_scalars<<<1, MD_BLOCK, 0, st>>>(nchunk, M, mode, tol, V.partials, V.sc); }
+    void mean_of(const double *src, const double *nbonded, double *mean)
+    {
+        k_elas_colsum<D, M><<<nchunk, MD_BLOCK, 0, st>>>(V.npair, src, V.partials);
+        k_elas_mean_finish<<<M * D, MD_BLOCK, 0, st>>>(nchunk, V.partials, nbonded, mean);
+    }
+    void init() { k_elas_init<D, M><<<nchunk, MD_BLOCK, 0, st>>>(V); scalars(0); }
+    void iterate()
+    {
+        launch_hess_apply(c, M, V.p, V.hp);
+        k_elas_php<D, M><<<nchunk, MD_BLOCK, 0, st>>>(V);
+        scalars(1);
+        k_elas_update<D, M><<<nchunk, MD_BLOCK, 0, st>>>(V);
+        scalars(2);
+        k_elas_direction<D, M><<<nchunk, MD_BLOCK, 0, st>>>(V);
+    }
+    void project() { k_elas_project<D, M><<<nchunk, MD_BLOCK, 0, st>>>(V); }
+    void residual(double *out)
+    {
+        launch_hess_apply(c, M, V.x, V.hp);
+        k_elas_resid<D, M><<<nchunk, MD_BLOCK, 0, st>>>(V);
+        k_elas_sum_finish<<<M, MD_BLOCK, 0, st>>>(nchunk, V.partials, 1.0, 1, out);
+    }
+    void contract(double inv_v, double *part, double *out)
+    {
+        constexpr int NC = ElasShape<D>::NC;
+        k_elas_contract<D><<<c->nblk, MD_BLOCK, 0, st>>>((int)c->n, V.xi, V.x, part);
+        k_elas_sum_finish<<<NC * NC, MD_BLOCK, 0, st>>>(c->nblk, part, inv_v, 0, out);
+    }
+};
+
+template <int D>
+void elas_solve_t(md_ctx *ctx, double tol, int64_t max_iter, int64_t *iters, double *resid, double *xi_norm, int *status,
+                  double *nonaffine, double *u)
+{
+    constexpr int NC = ElasShape<D>::NC, NB = ElasShape<D>::NB, M = ElasShape<D>::M;
+    md_ctx::Elas &E = ctx->elas;
+    const int n = (int)ctx->n;
+    const size_t ne = (size_t)n * M * D, npair = (size_t)n * M;
+    const int nchunk = (int)((npair + MD_ELAS_CHUNK - 1) / MD_ELAS_CHUNK);
+    hipStream_t st = ctx->stream;
+    E.x.ensure(ne);
+    E.r.ensure(ne);
+    E.p.ensure(ne);
+    E.hp.ensure(ne);
+    E.part.ensure(std::max((size_t)M * D * nchunk, std::max((size_t)NC * NC, (size_t)ElasShape<D>::NQ) * ctx->nblk));
+    E.mean.ensure(M * D);
+    E.out.ensure(M + NC * NC);
+    E.sc.ensure(1);
+    ElasLaunch<D> L{ctx, ElasVecs{npair, E.bonded.p, E.xi.p, E.x.p, E.r.p, E.p.p, E.hp.p, E.part.p, E.sc.p, E.mean.p}, nchunk, tol, st};
+    const double *nbonded = E.sums.p + NC + NB;
+    // the right-hand side, once against the translations of the bonded particles
+    L.mean_of(E.xi.p, nbonded, E.mean.p);
+    L.init();
+    HIPCHK(hipGetLastError());
+    ElasScal hs{};
+    auto poll = [&]() {
+        HIPCHK(hipMemcpyAsync(&hs, E.sc.p, sizeof hs, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    };
+    poll();
+    int64_t it = 0;
+    while (it < max_iter && hs.nactive > 0) { // the host waits once per 32 iterations (md_fire_minimize's convention)
+        const int64_t chunk_end = std::min<int64_t>(max_iter, it + 32);
+        for (; it < chunk_end; ++it) L.iterate();
+        HIPCHK(hipGetLastError());
+        poll();
+    }
+    // the solution, once against the same translations; then the true residual and the contraction
+    L.mean_of(E.x.p, nbonded, E.mean.p);
+    L.project();
+    L.residual(E.out.p);
+    L.contract(1.0 / ctx->volume, E.part.p, E.out.p + M);
+    HIPCHK(hipGetLastError());
+    double ho[MD_HESS_MAX_M + 36];
+    HIPCHK(hipMemcpyAsync(ho, E.out.p, sizeof(double) * (M + NC * NC), hipMemcpyDeviceToHost, st));
+    if (u) {
+        E.host_io.ensure((size_t)n * NC * D);
+        k_hess_export<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, ctx->dev(ctx->cur).id, D, NC, M, E.x.p, E.host_io.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(u, E.host_io.p, sizeof(double) * (size_t)n * NC * D, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    int bits = 0;
+    bool all_conv = true;
+    for (int v = 0; v < NC; ++v) {
+        iters[v] = (int64_t)hs.iters[v];
+        resid[v] = ho[v];
+        xi_norm[v] = std::sqrt(hs.rr0[v]);
+        if (hs.state[v] == MD_ELAS_ST_INDEFINITE) bits |= MD_ELAS_INDEFINITE;
+        if (hs.state[v] == MD_ELAS_ST_ACTIVE) bits |= MD_ELAS_MAX_ITER;
+        if (hs.state[v] != MD_ELAS_ST_CONVERGED) all_conv = false;
+    }
+    if (all_conv) bits |= MD_ELAS_CONVERGED;
+    *status = bits;
+    for (int q = 0; q < NC * NC; ++q) nonaffine[q] = ho[M + q];
 }
 
 // One Gram-Schmidt pass of w against the translations and the first nb basis vectors; mode / qa / out: k_hess_dots_finish
@@ -4438,6 +4578,7 @@ int md_hess_setup(md_ctx *ctx)
     if (!ctx->list_valid) rebuild(ctx); // the build md_compute_forces / md_run would make at these positions
     ctx->hess.ksteps = 0;
     ctx->hess.frozen = true;
+    ctx->hess.epoch++;
     API_END
 }
 
@@ -4576,6 +4717,61 @@ int md_hess_ritz(md_ctx *ctx, int ksteps, int nvec, const double *S, const doubl
             resid[c0 + c] = std::sqrt(a);
         }
     }
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Elastic moduli of the frame md_hess_setup froze (md_elas.hpp): reads positions, diameters and the
+// OUTER rows, writes only its own buffers.
+int md_elas_affine(md_ctx *ctx, double *stress, double *born, double *xi)
+{
+    API_BEGIN
+    md_ctx::Elas &E = elas_of(ctx, "md_elas_affine", false);
+    if (!stress || !born) throw HipError("md_elas_affine: stress / born is null");
+    const int n = (int)ctx->n, D = ctx->dim;
+    const int nc = D == 3 ? 6 : 3, nb = D == 3 ? 15 : 5, nq = nc + nb + 1, M = hess_block(nc);
+    hipStream_t st = ctx->stream;
+    E.epoch = 0;
+    E.xi.ensure((size_t)n * M * D);
+    E.bonded.ensure(n);
+    E.part.ensure((size_t)nq * ctx->nblk);
+    E.sums.ensure(MD_ELAS_MAX_NQ);
+    launch_elas_affine(ctx);
+    k_elas_affine_finish<<<nq, MD_BLOCK, 0, st>>>(ctx->nblk, nq, E.part.p, 1.0 / ctx->volume, E.sums.p);
+    HIPCHK(hipGetLastError());
+    double hsum[MD_ELAS_MAX_NQ];
+    HIPCHK(hipMemcpyAsync(hsum, E.sums.p, sizeof(double) * nq, hipMemcpyDeviceToHost, st));
+    if (xi) {
+        E.host_io.ensure((size_t)n * nc * D);
+        k_hess_export<<<ctx->nblk, MD_BLOCK, 0, st>>>(n, ctx->dev(ctx->cur).id, D, nc, M, E.xi.p, E.host_io.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(xi, E.host_io.p, sizeof(double) * (size_t)n * nc * D, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    for (int s = 0; s < nc; ++s) stress[s] = hsum[s];
+    for (int s = 0; s < nc; ++s)
+        for (int t = 0; t < nc; ++t) { // every entry of the totally symmetric tensor from its one sum
+            int ix[4] = {elas_ca(D, s), elas_cb(D, s), elas_ca(D, t), elas_cb(D, t)};
+            std::sort(ix, ix + 4);
+            born[s * nc + t] = hsum[nc + elas_born_index(D, ix[0], ix[1], ix[2], ix[3])];
+        }
+    E.epoch = ctx->hess.epoch;
+    API_END
+}
+
+int md_elas_solve(md_ctx *ctx, double tol, int64_t max_iter, int64_t *iters, double *resid, double *xi_norm, int *status,
+                  double *nonaffine, double *u)
+{
+    API_BEGIN
+    elas_of(ctx, "md_elas_solve", true);
+    if (!(tol > 0.0) || !std::isfinite(tol)) throw HipError("md_elas_solve: tol must be > 0");
+    if (max_iter < 1 || max_iter > 0x3fffffff) throw HipError("md_elas_solve: max_iter must be in 1..1073741823");
+    if (!iters || !resid || !xi_norm || !status || !nonaffine)
+        throw HipError("md_elas_solve: iters / resid / xi_norm / status / nonaffine is null");
+    if (ctx->dim == 3)
+        elas_solve_t<3>(ctx, tol, max_iter, iters, resid, xi_norm, status, nonaffine, u);
+    else
+        elas_solve_t<2>(ctx, tol, max_iter, iters, resid, xi_norm, status, nonaffine, u);
     API_END
 }
 

@@ -670,6 +670,50 @@ class MDDevice:
         self._chk(self._L.md_hess_ritz(self._h, int(S.shape[0]), int(S.shape[1]), _dp(S), _dp(theta), _dp(modes), _dp(resid)))
         return modes, resid
 
+    # -- elastic moduli of the frozen frame ------------------------------------------------
+    ELAS_CONVERGED, ELAS_MAX_ITER, ELAS_INDEFINITE = _lib.MD_ELAS_CONVERGED, _lib.MD_ELAS_MAX_ITER, _lib.MD_ELAS_INDEFINITE
+
+    @property
+    def elas_components(self):
+        """The strain components in the order of every elas_* array: tuples of axis indices."""
+        return ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)) if self.dim == 3 else ((0, 0), (1, 1), (0, 1))
+
+    def elas_affine(self, fields=False):
+        """The affine pass on the operator hess_setup froze (md_elas_affine).  Returns dict(stress[nc], born[nc, nc]) --
+        configurational stress and Born tensor per unit volume, tensor components in elas_components order -- and with
+        fields=True also xi float64[nc, N, d], the affine force field by particle id; waits."""
+        nc = len(self.elas_components)
+        stress, born = np.empty(nc), np.empty((nc, nc))
+        xi = np.empty((nc, self.n, self.dim)) if fields else None
+        self._chk(self._L.md_elas_affine(self._h, _dp(stress), _dp(born), _dp(xi) if fields else None))
+        out = dict(stress=stress, born=born)
+        if fields:
+            out["xi"] = xi
+        return out
+
+    def elas_solve(self, tol, max_iter, fields=True):
+        """H u_c = -Xi_c for the nc strain components at once by conjugate gradients on the device (md_elas_solve); needs
+        elas_affine of the same hess_setup.  Returns dict(nonaffine[nc, nc] = Xi_s . u_t / V (not symmetrised), iterations[nc],
+        residuals[nc] = the true |H u_c + Xi_c|, xi_norm[nc], status (bits ELAS_CONVERGED | ELAS_MAX_ITER | ELAS_INDEFINITE),
+        converged, indefinite) and with fields=True u float64[nc, N, d] by particle id; waits."""
+        tol, max_iter = float(tol), int(max_iter)
+        if not tol > 0.0:
+            raise ValueError("tol must be > 0")
+        if max_iter < 1:
+            raise ValueError("max_iter must be >= 1")
+        nc = len(self.elas_components)
+        iters = np.zeros(nc, dtype=np.int64)
+        resid, xin, nonaff = np.empty(nc), np.empty(nc), np.empty((nc, nc))
+        u = np.empty((nc, self.n, self.dim)) if fields else None
+        status = C.c_int(0)
+        self._chk(self._L.md_elas_solve(self._h, tol, max_iter, iters.ctypes.data_as(C.POINTER(C.c_int64)), _dp(resid), _dp(xin),
+                                        C.byref(status), _dp(nonaff), _dp(u) if fields else None))
+        out = dict(nonaffine=nonaff, iterations=iters, residuals=resid, xi_norm=xin, status=status.value,
+                   converged=bool(status.value & self.ELAS_CONVERGED), indefinite=bool(status.value & self.ELAS_INDEFINITE))
+        if fields:
+            out["u"] = u
+        return out
+
     # -- instrumentation ------------------------------------------------------------------
     def profile(self, enable=True):
         """True/1: time every force and kick-drift launch; k > 1: every k-th; False/0: off."""
