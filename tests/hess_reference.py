@@ -14,8 +14,11 @@ POT_LJ, POT_PSEUDOHS, POT_POLYDISPERSE, POT_LJ_MODIFIED = 0, 1, 2, 3
 PHS_A, PHS_B = 134.5526623421209, 1.0204081632653061
 
 
-def pair_tk(kind, params, r, si, sj, dtype=np.float64):
-    """(t, k, inside) = (U'/r, U'', the potential's own cutoff branch) at distances r for diameters si, sj."""
+def pair_full(kind, params, r, si, sj, dtype=np.float64):
+    """Everything tests/pair_table.py and pair_tk need of a pair at distances r for diameters si, sj, in one place:
+    dict(u, f, k, Su, Sf, Sk, inside) -- the energy, f = -dU/dr, U'' of the smooth branch (NOT masked by `inside`, the
+    potential's own cutoff branch), and for each of u, f, k the scale S = the sum of the absolute values of the terms of the
+    formula as written here (differences that cancel, rc^2 - r^2 of the XPLOR switch included, enter with both terms)."""
     T = dtype
     r, si, sj = (np.asarray(a, dtype=T) for a in (r, si, sj))
     p = [T(v) for v in params]
@@ -24,21 +27,35 @@ def pair_tk(kind, params, r, si, sj, dtype=np.float64):
         sg = (si + sj) / T(2)
         s6 = (sg / r) ** 6
         s12 = s6 * s6
+        u = T(4) * eps * (s12 - s6)
         f = T(24) * eps * (T(2) * s12 - s6) / r
         k = T(24) * eps * (T(26) * s12 - T(7) * s6) / (r * r)
+        ae = abs(eps)
+        Su = T(4) * ae * (s12 + s6)
+        Sf = T(24) * ae * (T(2) * s12 + s6) / r
+        Sk = T(24) * ae * (T(26) * s12 + T(7) * s6) / (r * r)
         inside = r < rc
     elif kind == POT_PSEUDOHS:
         lam = p[0]
         sr = ((si + sj) / T(2)) / r
+        u = T(PHS_A) * (sr ** lam - sr ** (lam - T(1))) + T(1)
         f = T(PHS_A) * (lam * sr ** (lam + T(1)) - (lam - T(1)) * sr ** lam)
         k = T(PHS_A) * lam * ((lam + T(1)) * sr ** (lam + T(1)) - (lam - T(1)) * sr ** lam) / r
+        Su = T(PHS_A) * (sr ** lam + sr ** (lam - T(1))) + T(1)
+        Sf = T(PHS_A) * (lam * sr ** (lam + T(1)) + abs(lam - T(1)) * sr ** lam)
+        Sk = T(PHS_A) * lam * ((lam + T(1)) * sr ** (lam + T(1)) + abs(lam - T(1)) * sr ** lam) / r
         inside = r < T(PHS_B)
     elif kind == POT_POLYDISPERSE:
         rc, eta = p[0], p[1]
         se = T(0.5) * (si + sj) * (T(1) - eta * np.abs(si - sj))
-        c2, c4 = T(48) / rc ** 14, T(-21) / rc ** 16
+        c0, c2, c4 = T(-28) / rc ** 12, T(48) / rc ** 14, T(-21) / rc ** 16
+        q = r / se
+        u = (se / r) ** 12 + c0 + c2 * (q * q) + c4 * q ** 4
         f = T(12) * se ** 12 / r ** 13 - T(2) * c2 * r / se ** 2 - T(4) * c4 * r ** 3 / se ** 4
         k = T(156) * se ** 12 / r ** 14 + T(2) * c2 / se ** 2 + T(12) * c4 * r ** 2 / se ** 4
+        Su = (se / r) ** 12 + abs(c0) + abs(c2) * (q * q) + abs(c4) * q ** 4
+        Sf = T(12) * se ** 12 / r ** 13 + T(2) * abs(c2) * r / se ** 2 + T(4) * abs(c4) * r ** 3 / se ** 4
+        Sk = T(156) * se ** 12 / r ** 14 + T(2) * abs(c2) / se ** 2 + T(12) * abs(c4) * r ** 2 / se ** 4
         inside = r < rc * se
     elif kind == POT_LJ_MODIFIED:
         eps, sc, rc, mode, ron = p[0], p[1], p[2], int(params[3]), p[4]
@@ -48,11 +65,20 @@ def pair_tk(kind, params, r, si, sj, dtype=np.float64):
         V = T(4) * eps * (s12 - s6)
         F = T(24) * eps * (T(2) * s12 - s6) / r
         V2 = T(24) * eps * (T(26) * s12 - T(7) * s6) / (r * r)
+        ae = abs(eps)
+        SV = T(4) * ae * (s12 + s6)
+        SF = T(24) * ae * (T(2) * s12 + s6) / r
+        SV2 = T(24) * ae * (T(26) * s12 + T(7) * s6) / (r * r)
+        sc6 = (sc / rc) ** 6
+        Vc = T(4) * eps * (sc6 * sc6 - sc6)
+        Fc = T(24) * eps * (T(2) * sc6 * sc6 - sc6) / rc
         if mode == 0:
-            f, k = F, V2
+            u, f, k = V - Vc, F, V2
+            Su, Sf, Sk = SV + abs(Vc), SF, SV2
         elif mode == 1:
-            sc6 = (sc / rc) ** 6
+            u = V - Vc + (r - rc) * Fc
             f, k = F - T(24) * eps * (T(2) * sc6 * sc6 - sc6) / rc, V2
+            Su, Sf, Sk = SV + abs(Vc) + (r + rc) * abs(Fc), SF + abs(Fc), SV2
         else:
             rc2, r2, ron2 = rc * rc, r * r, ron * ron
             den = (rc2 - ron2) ** 3
@@ -61,13 +87,28 @@ def pair_tk(kind, params, r, si, sj, dtype=np.float64):
             S = np.where(sw, a * a * b / den, T(1))
             dS = np.where(sw, T(-12) * r * a * g / den, T(0))
             ddS = np.where(sw, T(-12) * (a * g - T(2) * r2 * g + T(2) * r2 * a) / den, T(0))
+            u = V * S
             f = S * F - V * dS
             k = S * V2 - T(2) * F * dS + V * ddS
+            A_, B_, G_, ad = rc2 + r2, rc2 + T(2) * r2 + T(3) * ron2, r2 + ron2, abs(den)
+            SS = np.where(sw, A_ * A_ * B_ / ad, T(1))
+            SdS = np.where(sw, T(12) * r * A_ * G_ / ad, T(0))
+            SddS = np.where(sw, T(12) * (A_ * G_ + T(2) * r2 * G_ + T(2) * r2 * A_) / ad, T(0))
+            Su = SV * SS
+            Sf = SS * SF + SV * SdS
+            Sk = SS * SV2 + T(2) * SF * SdS + SV * SddS
         inside = r < rc
     else:
         raise KeyError(kind)
+    return dict(u=u, f=f, k=k, Su=Su, Sf=Sf, Sk=Sk, inside=inside)
+
+
+def pair_tk(kind, params, r, si, sj, dtype=np.float64):
+    """(t, k, inside) = (U'/r, U'', the potential's own cutoff branch) at distances r for diameters si, sj."""
+    q = pair_full(kind, params, r, si, sj, dtype)
+    r = np.asarray(r, dtype=dtype)
     zero = np.zeros_like(r)
-    return np.where(inside, -f / r, zero), np.where(inside, k, zero), inside
+    return np.where(q["inside"], -q["f"] / r, zero), np.where(q["inside"], q["k"], zero), q["inside"]
 
 
 def lattice(box_or_cell, dim):

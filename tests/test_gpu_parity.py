@@ -614,15 +614,6 @@ def test_pruning_changes_nothing():
         assert abs(uwk[0] - out[0][3][0]) <= 1e-10 * abs(out[0][3][0])
 
 
-def _sqrt_ge_threshold(r):
-    t = r * r
-    while np.sqrt(t) >= r:
-        t = np.nextafter(t, 0.0)
-    while np.sqrt(t) < r:
-        t = np.nextafter(t, np.inf)
-    return float(t)
-
-
 @pytest.mark.parametrize("list_cutoff", [2.5, 3.0])
 def test_cutoff_decisions_follow_reference_arithmetic(oracle, list_cutoff):
     """Adversarial dimers (tests/util.py cutoff_dimers): squared separations ON the threshold, one ulp either side,
@@ -631,8 +622,8 @@ def test_cutoff_decisions_follow_reference_arithmetic(oracle, list_cutoff):
     d2 >= the smallest double whose sqrt rounds to 2.5 (which is 6.25 - 1 ulp, not 6.25).  Pair set bit-exact;
     a single misclassified pair would change U by 1.6e-2 and two forces by 3.9e-2.  Exercises the generic kernels
     (md_compute_forces, md_neighbor_pairs) and both fast kernels (prune step and inner rows) through md_run."""
-    from tests.util import cutoff_dimers, d2_forms
-    target = 6.25 if list_cutoff == 2.5 else _sqrt_ge_threshold(2.5)
+    from tests.util import cutoff_dimers, d2_forms, sqrt_ge_threshold
+    target = 6.25 if list_cutoff == 2.5 else sqrt_ge_threshold(2.5)
     assert list_cutoff == 2.5 or target == np.nextafter(6.25, 0.0)
     s = cutoff_dimers(target)
     nd = s["n"] // 2

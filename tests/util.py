@@ -54,6 +54,16 @@ def d2_forms(a, b):
     return ref, t
 
 
+def sqrt_ge_threshold(r):
+    """The smallest double whose (correctly rounded) sqrt reaches r: `sqrt(d2) >= r` holds iff d2 >= this."""
+    t = r * r
+    while np.sqrt(t) >= r:
+        t = np.nextafter(t, 0.0)
+    while np.sqrt(t) < r:
+        t = np.nextafter(t, np.inf)
+    return float(t)
+
+
 def cutoff_dimers(target, n_side=8, spacing=9.0, seed=99):
     """n_side^3 dimers on a cubic lattice of the given spacing (no two dimers interact); dimer k's squared
     separation is steered, by nudging one coordinate in ulps, into category k % 6 relative to `target`:
