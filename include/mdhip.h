@@ -848,6 +848,51 @@ int md_elas_affine(md_ctx *ctx, double *stress, double *born, double *xi);
 int md_elas_solve(md_ctx *ctx, double tol, int64_t max_iter, int64_t *iters, double *resid, double *xi_norm, int *status,
                   double *nonaffine, double *u);
 
+/* Change the unit cell of a live handle and carry the particles along (new relative to the reference, which fixes the cell
+ * at initialisation).  box is d x d column-major, columns = lattice vectors, validated and inverted
+ * exactly as md_create does; a diagonal matrix takes the orthorhombic fast paths again, anything else is a general cell.
+ *
+ * MD_CELL_AFFINE: fractional coordinates are kept.  One pass over the state records: frac = U_old^-1 x (invL * x per
+ * component, or row times vector left to right, every operation rounded, no fma: the wrap's arithmetic), n = floor(frac),
+ * img += n, x = U_new (frac - n) in the new cell's form of that product -- wrap_to_box (src/boundary.jl:7-17) with the old
+ * inverse and the new matrix.  frac + img is kept exactly.  Velocities are left as they are; FORCES ARE LEFT STALE (those of
+ * the old cell) until the next evaluation (md_compute_forces, md_run, md_fire_minimize, ...).
+ * MD_CELL_LATTICE: the new cell must generate the same lattice.  M = U_old^-1 U_new must be integer to 1e-9 per entry
+ * (entries up to 2^10), |det M| = 1, and U_old M must give back U_new to 8 ulp of the largest term of each entry's sum.
+ * Cartesian positions do not move but for the wrap into the new cell (as md_download wraps: only a coordinate outside
+ * [0, 1) moves); img' = M^-1 img in integer arithmetic, plus the wrap's shift.  x + U img is kept to rounding.  A mark of
+ * md_nonaffine_mark is carried into the new basis by the same integer matrix.  Refused when an image count (of the state or
+ * of the mark) would leave int32: one pass that writes nothing decides that before the pass that writes.
+ *
+ * Refused, through md_last_error and with the handle's cell and state exactly as before: a singular or non-finite matrix;
+ * a face distance below 3 * list_cutoff (what the linked-cell build needs) or below 3 * r_max of md_rdf_ / md_mpc_; a slab
+ * handle; a handle whose state a failed step loop left incomplete; a frame in flight (md_snapshot_begin without its _end);
+ * a handle with md_dyn_, md_sq_, md_cur_, md_chi4_ or md_cage_ set up (they store time origins, or wave vectors
+ * commensurate with the cell the setup saw; the message names the sampler).
+ * On acceptance the cell grid is derived again, the ghost capacity and the row capacity follow the new grid and density
+ * as in md_create / md_set_skin (buffers only grow), the neighbour lists are invalid (the next evaluation rebuilds), the
+ * rebuild schedule measures its displacement rate again, the grids of md_rdf_ / md_mpc_ are derived again, and the frozen
+ * operator of md_hess_ / md_elas_ is dropped.  md_rdf_, md_stress_, md_boo_, md_cluster_, md_mpc_ keep working: they
+ * read one frame at a time (their running sums then mix cells -- the caller's business).  Waits.
+ * A handle on which md_set_cell is never called behaves exactly as before.                                              */
+#define MD_CELL_AFFINE 0
+#define MD_CELL_LATTICE 1
+int md_set_cell(md_ctx *ctx, const double *box, int mode);
+
+/* Displacement since a mark with the affine part taken out (same section).
+ * md_nonaffine_mark stores, by particle index, the fractional coordinate U^-1 x (a double) and the image count (an int32)
+ * of every particle, separately, so that the image difference is exact.  Allocates N * D * 12 bytes on the first call.
+ * md_nonaffine: u_i = U_now ((frac_i - frac0_i) + (img_i - img0_i)).  An affine cell change keeps fractional coordinates,
+ * so u is exactly the non-affine part of the displacement since the mark; a lattice change transforms the mark and leaves
+ * u unchanged to rounding.  sums[8] = sum u_x, sum u_y, sum u_z (0 in an unused dimension), sum |u|^2, sum |u|^4,
+ * max |u|^2, the index of the particle attaining it (the lowest on a tie; as a double), N.  Block partials in a fixed order
+ * and a small second pass (one block per sum); the maximum through an integer atomic on the double's bits; no
+ * floating-point atomics.  u is [N][D] by particle index or NULL (N * D * 8 bytes more on the first call with u).  Waits.
+ * md_nonaffine without a mark, or after md_upload of positions (the mark would describe another frame), is an error.
+ * Single-GPU handles only.                                                                                             */
+int md_nonaffine_mark(md_ctx *ctx);
+int md_nonaffine(md_ctx *ctx, double *sums, double *u);
+
 /* Library build info: returns e.g. "mdhip 0.1 gfx950". */
 const char *md_version(void);
 

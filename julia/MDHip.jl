@@ -21,7 +21,9 @@ export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, Pseudo
        FourPoint, overlap, chi4, s4, s4_vectors, write_chi4, write_s4, chi4_last,
        StructureFactor, select_wave_vectors, compute_sq, sofq, fqt, fqt_normalised, write_sq, write_fqt,
        CurrentCorrelations, current_cl, current_ct, current_cl0, current_ct0, vacf, vacf0, write_currents, write_vacf,
-       cur_last, mpc_setup!, mpc_marks!, mpc_sample!, mpc_reset!, mpc_last, mpc_read
+       cur_last, mpc_setup!, mpc_marks!, mpc_sample!, mpc_reset!, mpc_last, mpc_read,
+       simple_shear, pure_shear, volumetric, set_unitcell!, deform!, reduce_cell!, gauss_reduce, nonaffine_mark!, nonaffine,
+       athermal_quasistatic_shear!
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -1469,6 +1471,165 @@ function minimize!(state::SimulationState, params::Parameters, pathname::String,
     X = pack(state.system.positions, state.dimension)
     write_to_file(joinpath(pathname, save_config), 0, state.unitcell, params.n_particles, X, state.diameters, dimension)
     return nothing
+end
+
+# ---- deformation of a live sample: md_set_cell, md_nonaffine_*, AQS (moleculardynamics/jl_amd/deformation.py) ----
+# The unit cell has the lattice vectors in its columns; F acts from the left, U' = F U.  params is never touched: after a
+# change of volume params.ρ is the caller's to keep consistent, the reference's own convention.
+const MD_CELL_AFFINE = 0
+const MD_CELL_LATTICE = 1
+
+function simple_shear(d::Int, gamma::Real; plane=(1, 2))                           # axes are 1-based here
+    F = Matrix{Float64}(I, d, d); F[plane[1], plane[2]] = gamma; return F
+end
+function pure_shear(d::Int, eps::Real; plane=(1, 2))
+    1.0 + eps > 0.0 || error("eps must be > -1")
+    F = Matrix{Float64}(I, d, d); F[plane[1], plane[1]] = 1.0 + eps; F[plane[2], plane[2]] = 1.0 / (1.0 + eps); return F
+end
+function volumetric(d::Int, eps::Real)
+    1.0 + eps > 0.0 || error("eps must be > -1")
+    return Matrix{Float64}(I, d, d) .* (1.0 + eps)
+end
+
+function device_set_cell!(state::SimulationState, U::AbstractMatrix, mode::Integer)
+    dev = state.system.device
+    box = Matrix{Float64}(U)
+    check(dev, ccall((:md_set_cell, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), dev.h, box, mode))
+    state.unitcell = box; state.system.unitcell = box
+    return nothing
+end
+
+"mark the frame the device holds: fractional coordinates and image counts by particle index"
+nonaffine_mark!(dev::Device) = (check(dev, ccall((:md_nonaffine_mark, LIB), Cint, (Ptr{Cvoid},), dev.h)); nothing)
+
+"(sums[8], u d x N or nothing): the displacement since the mark with the affine part taken out (md_nonaffine)"
+function nonaffine(dev::Device; fields::Bool=false)
+    sums = zeros(8)
+    u = fields ? Matrix{Float64}(undef, dev.dim, dev.n) : nothing
+    check(dev, ccall((:md_nonaffine, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), dev.h, sums, fields ? u : C_NULL))
+    return sums, u
+end
+
+"set_unitcell!(state, params, unitcell; remap=:affine | :lattice, upload=true): see deformation.py set_unitcell"
+function set_unitcell!(state::SimulationState, params::Parameters, unitcell::AbstractMatrix; remap::Symbol=:affine,
+                       upload::Bool=true)
+    remap in (:affine, :lattice) || error("remap must be :affine or :lattice")
+    dev = state.system.device; d = state.dimension
+    configure!(dev, params.potential)
+    if upload
+        X = pack(state.system.positions, d)
+        check(dev, ccall((:md_upload, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                         dev.h, X, C_NULL, C_NULL, state.images, state.diameters))
+    end
+    device_set_cell!(state, unitcell, remap == :affine ? MD_CELL_AFFINE : MD_CELL_LATTICE)
+    X, _, _, IM = download(dev)
+    unpack!(state.system.positions, X); state.images .= IM
+    return nothing
+end
+
+deform!(state::SimulationState, params::Parameters, F::AbstractMatrix; upload::Bool=true) =
+    set_unitcell!(state, params, F * state.unitcell; remap=:affine, upload=upload)
+
+face_distances(U::AbstractMatrix) = (Ui = inv(U); [1.0 / norm(Ui[r, :]) for r in 1:size(U, 1)])
+
+"(U * M, M): pairwise Gauss reduction of the columns of U; a step that would shrink a face distance is not taken"
+function gauss_reduce(U::AbstractMatrix)
+    d = size(U, 1); M = Matrix{Int64}(I, d, d); W = Matrix{Float64}(U)
+    for _ in 1:64
+        changed = false
+        for a in 1:d, b in 1:d
+            a == b && continue
+            k = round(Int64, dot(W[:, b], W[:, a]) / dot(W[:, a], W[:, a]), RoundNearest)
+            k == 0 && continue
+            M2 = copy(M); M2[:, b] .-= k .* M2[:, a]
+            W2 = Matrix{Float64}(U) * Float64.(M2)
+            any(face_distances(W2) .< face_distances(W) .* (1.0 - 1e-12)) && continue
+            M = M2; W = W2; changed = true
+        end
+        changed || break
+    end
+    return W, M
+end
+
+"reduce_cell!(state, params): the reduced cell of the same lattice, particles where they are; the integer matrix or nothing"
+function reduce_cell!(state::SimulationState, params::Parameters; upload::Bool=true)
+    W, M = gauss_reduce(state.unitcell)
+    M == Matrix{Int64}(I, state.dimension, state.dimension) && return nothing
+    set_unitcell!(state, params, W; remap=:lattice, upload=upload)
+    return M
+end
+
+function aqs_columns(d::Int)
+    comps = d == 3 ? ((1, 1), (2, 2), (3, 3), (1, 2), (1, 3), (2, 3)) : ((1, 1), (2, 2), (1, 2))
+    return vcat(["step", "strain", "energy"], ["stress_" * "xyz"[a] * "xyz"[b] for (a, b) in comps],
+                ["pressure", "fire_steps", "converged", "d2_nonaffine", "participation", "max_u", "flips"]), comps
+end
+
+"athermal_quasistatic_shear!(state, params, pathname, strain_step, nsteps; mode, plane, tol, reduce, mark, on_step,
+max_steps, dt_initial, dt_max, alpha0, f_inc, f_dec, Nmin): deformation.py athermal_quasistatic_shear, the same aqs.txt.
+The handle's pressure-tensor sampler is set up afresh (md_stress_setup, no lags): an earlier setup and its sums are discarded."
+function athermal_quasistatic_shear!(state::SimulationState, params::Parameters, pathname::String, strain_step::Real,
+                                     nsteps::Int; mode::Symbol=:simple, plane=(1, 2), tol::Float64=1e-9, reduce::Bool=true,
+                                     mark::Symbol=:previous, on_step=nothing, max_steps::Int=10000,
+                                     dt_initial::Float64=0.01, dt_max::Float64=0.1, alpha0::Float64=0.1,
+                                     f_inc::Float64=1.2, f_dec::Float64=0.2, Nmin::Int=5)
+    mark in (:previous, :start) || error("mark must be :previous or :start")
+    mode in (:simple, :pure, :volumetric) || error("mode must be :simple, :pure or :volumetric")
+    nsteps >= 1 || error("nsteps must be >= 1")
+    tol > 0.0 || error("tol must be > 0")
+    dev = state.system.device; d = state.dimension; n = params.n_particles
+    F = mode == :simple ? simple_shear(d, strain_step; plane=plane) :
+        mode == :pure ? pure_shear(d, strain_step; plane=plane) : volumetric(d, strain_step)
+    configure!(dev, params.potential)
+    X = pack(state.system.positions, d); Fo = pack(state.system.energy_and_forces.forces, d)
+    check(dev, ccall((:md_upload, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                     dev.h, X, C_NULL, Fo, state.images, state.diameters))
+    check(dev, ccall((:md_stress_setup, LIB), Cint, (Ptr{Cvoid}, Cint), dev.h, 0))
+    names, comps = aqs_columns(d)
+    nc = length(comps)
+    rows = Vector{Vector{Float64}}()
+    mark == :start && nonaffine_mark!(dev)
+    kin = zeros(nc); vir = zeros(nc)
+    eye = Matrix{Int64}(I, d, d)
+    for k in 1:nsteps
+        device_set_cell!(state, F * state.unitcell, MD_CELL_AFFINE)
+        flips = 0
+        if reduce
+            W, M = gauss_reduce(state.unitcell)
+            if M != eye
+                device_set_cell!(state, W, MD_CELL_LATTICE); flips = 1
+            end
+        end
+        mark == :previous && nonaffine_mark!(dev)
+        steps = Ref{Int64}(0); conv = Ref{Cint}(0); energy = Ref{Float64}(0.0); frms = Ref{Float64}(0.0)
+        rc = @ccall gc_safe=true LIB.md_fire_minimize(dev.h::Ptr{Cvoid}, max_steps::Int64, tol::Float64, dt_initial::Float64,
+                          dt_max::Float64, alpha0::Float64, f_inc::Float64, f_dec::Float64, Nmin::Cint, steps::Ptr{Int64},
+                          conv::Ptr{Cint}, energy::Ptr{Float64}, frms::Ptr{Float64})::Cint
+        check(dev, rc)
+        check(dev, ccall((:md_stress_sample, LIB), Cint, (Ptr{Cvoid},), dev.h))
+        check(dev, ccall((:md_stress_tensor, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), dev.h, kin, vir))
+        volume = abs(det(state.unitcell))
+        stress = -vir ./ volume
+        sums, _ = nonaffine(dev)
+        s2 = sums[4]; s4 = sums[5]
+        pressure = -sum(stress[i] for (i, (a, b)) in enumerate(comps) if a == b) / d
+        row = vcat([k, k * strain_step, energy[] / n], stress,
+                   [pressure, steps[], conv[] != 0 ? 1 : 0, s2 / n, s4 > 0.0 ? s2 * s2 / (n * s4) : 0.0, sqrt(sums[6]), flips])
+        push!(rows, row)
+        on_step === nothing || on_step(Dict(zip(names, row)))
+    end
+    X, _, Fd, IM = download(dev)
+    unpack!(state.system.positions, X); unpack!(state.system.energy_and_forces.forces, Fd); state.images .= IM
+    state.system.energy_and_forces.energy = rows[end][3] * n
+    mkpath(pathname)
+    ints = Set(["step", "fire_steps", "converged", "flips"])
+    open(joinpath(pathname, "aqs.txt"), "w") do io
+        println(io, "# " * join(names, " "))
+        for row in rows
+            println(io, join([nm in ints ? @sprintf("%d", Int(v)) : @sprintf("%.17g", v) for (nm, v) in zip(names, row)], " "))
+        end
+    end
+    return Dict(nm => [row[i] for row in rows] for (i, nm) in enumerate(names))
 end
 
 end # module

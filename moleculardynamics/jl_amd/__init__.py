@@ -15,6 +15,8 @@ from .analysis import (RadialDistribution, compute_rdf, SelfDynamics, StructureF
 from .minimize import fire_minimize, minimize
 from .montecarlo import SwapMonteCarlo, swap_rounds
 from .vibrations import HessianOperator, elastic_moduli, lowest_modes, participation_ratio
+from .deformation import (simple_shear, pure_shear, volumetric, set_unitcell, deform, reduce_cell, gauss_reduce,
+                          athermal_quasistatic_shear)
 from .device import MDDevice
 from ._lib import MdhipError
 
@@ -27,5 +29,6 @@ __all__ = [
     "StressTensor", "compute_stress", "BondOrder", "compute_bond_order", "ClusterAnalysis", "compute_clusters", "CageDynamics",
     "FourPoint", "CurrentCorrelations", "OrientationalCorrelation", "compute_orientational_correlation",
     "compute_marked_correlation", "SwapMonteCarlo", "swap_rounds", "HessianOperator", "lowest_modes", "participation_ratio",
-    "elastic_moduli",
+    "elastic_moduli", "simple_shear", "pure_shear", "volumetric", "set_unitcell", "deform", "reduce_cell", "gauss_reduce",
+    "athermal_quasistatic_shear",
 ]

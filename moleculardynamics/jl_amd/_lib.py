@@ -15,6 +15,7 @@ MD_CLUSTER_ALL, MD_CLUSTER_SOLID = 0, 1
 MD_MPC_BOO, MD_MPC_USER = 0, 1
 MD_LIST_ROWS_INFO = 16
 MD_ELAS_CONVERGED, MD_ELAS_MAX_ITER, MD_ELAS_INDEFINITE = 1, 2, 4
+MD_CELL_AFFINE, MD_CELL_LATTICE = 0, 1
 
 # every symbol include/mdhip.h declares
 EXPORTS = [
@@ -41,6 +42,7 @@ EXPORTS = [
     "md_swap_setup", "md_swap_rounds", "md_swap_last", "md_diameters",
     "md_hess_setup", "md_hess_apply", "md_hess_blocks", "md_hess_lanczos", "md_hess_ritz",
     "md_elas_affine", "md_elas_solve",
+    "md_set_cell", "md_nonaffine_mark", "md_nonaffine",
 ]
 
 
@@ -279,6 +281,12 @@ def load():
     L.md_elas_affine.restype = C.c_int
     L.md_elas_solve.argtypes = [vp, C.c_double, C.c_int64, i64p, dp, dp, C.POINTER(C.c_int), dp, dp]
     L.md_elas_solve.restype = C.c_int
+    L.md_set_cell.argtypes = [vp, dp, C.c_int]
+    L.md_set_cell.restype = C.c_int
+    L.md_nonaffine_mark.argtypes = [vp]
+    L.md_nonaffine_mark.restype = C.c_int
+    L.md_nonaffine.argtypes = [vp, dp, dp]
+    L.md_nonaffine.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

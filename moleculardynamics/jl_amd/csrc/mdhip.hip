@@ -24,6 +24,7 @@
 #include "md_swap.hpp"
 #include "md_hess.hpp"
 #include "md_elas.hpp"
+#include "md_cell.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -602,6 +603,17 @@ struct md_ctx {
         DBuf<int32_t> bonded;
         DBuf<ElasScal> sc;
     } elas;
+
+    // Non-affine displacement since a mark (md_nonaffine_*): the mark by particle id -- fractional coordinates and image
+    // counts, kept apart so that the image difference is exact -- the per-particle u (when asked for), block partials of
+    // the sums, per-block maximum bits and ids, the global maximum's bits, the finished sums.
+    struct Naff {
+        bool marked = false;
+        DBuf<double> frac, u, part, out;  // n x dim; n x dim; MD_NAFF_NSUM x nblk; 8
+        DBuf<int32_t> img, pid;           // n x dim; nblk
+        DBuf<unsigned long long> pmax, gmax; // nblk; 1
+        DBuf<int> range_error;            // md_set_cell, MD_CELL_LATTICE: an image count would leave int32
+    } naff;
 
     std::string err;
     // A failure inside a fused step loop (between fused_enter and fused_leave) leaves the live state in the step
@@ -2691,6 +2703,7 @@ int md_upload(md_ctx *ctx, const double *x, const double *v, const double *f, co
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st)); // host buffers are only borrowed for this call
     if (x || diameters) ctx->list_valid = false;
+    if (x) ctx->naff.marked = false; // (md_nonaffine_mark described the frame these positions replace)
     if (x && v && f) {
         // a complete new state: whatever a failed step loop left behind is gone
         ctx->state_invalid = false;
@@ -4772,6 +4785,260 @@ int md_elas_solve(md_ctx *ctx, double tol, int64_t max_iter, int64_t *iters, dou
         elas_solve_t<3>(ctx, tol, max_iter, iters, resid, xi_norm, status, nonaffine, u);
     else
         elas_solve_t<2>(ctx, tol, max_iter, iters, resid, xi_norm, status, nonaffine, u);
+    API_END
+}
+
+// ---------------------------------------------------------------------------------------------
+// Cell changes of a live handle and the non-affine displacement since a mark (md_cell.hpp)
+static NaffCell naff_cell(const md_ctx *ctx)
+{
+    NaffCell c{};
+    c.tric = ctx->tric;
+    for (int i = 0; i < 9; ++i) {
+        c.a[i] = ctx->A[i];
+        c.inv[i] = ctx->Ainv[i];
+    }
+    return c;
+}
+
+int md_set_cell(md_ctx *ctx, const double *box, int mode)
+{
+    API_BEGIN
+    if (mode != MD_CELL_AFFINE && mode != MD_CELL_LATTICE) throw HipError("md_set_cell: mode must be MD_CELL_AFFINE or MD_CELL_LATTICE");
+    if (!box) throw HipError("md_set_cell: box is null");
+    if (ctx->dom.on) throw HipError("md_set_cell: not available on a slab-decomposition handle");
+    require_state(ctx, "md_set_cell");
+    if (ctx->snap_pending) throw HipError("md_set_cell: a frame is in flight (collect it with md_snapshot_end first)");
+    const char *holder = ctx->dyn.on ? "md_dyn" : ctx->sq.on ? "md_sq" : ctx->current.on ? "md_cur" : ctx->chi4.on ? "md_chi4"
+                         : ctx->cage.on ? "md_cage" : nullptr;
+    if (holder)
+        throw HipError(std::string("md_set_cell: the ") + holder + "_ sampler is set up on this handle; its stored origins or "
+                       "wave vectors belong to the cell it was set up in");
+    const int dim = ctx->dim;
+    CellGeom cg;
+    if (const char *why = cell_geometry(dim, box, cg)) {
+        std::string w(why);
+        throw HipError("md_set_cell" + w.substr(w.find(':')));
+    }
+    for (int c = 0; c < dim; ++c)
+        if (cg.perp[c] / 3.0 < ctx->rc) {
+            char b[320];
+            snprintf(b, sizeof b,
+                     "md_set_cell: the new cell is too small for the linked-cell build: the face distance %.17g of lattice "
+                     "direction %d must be >= 3*list_cutoff = %.17g",
+                     cg.perp[c], c, 3.0 * ctx->rc);
+            throw HipError(b);
+        }
+    CellMap m{};
+    m.tric_old = ctx->tric;
+    m.tric_new = cg.tric;
+    for (int i = 0; i < 9; ++i) {
+        m.inv_old[i] = ctx->Ainv[i];
+        m.a_new[i] = cg.A[i];
+        m.inv_new[i] = cg.Ainv[i];
+        m.minv[i] = (i % 4 == 0) ? 1 : 0;
+    }
+    if (mode == MD_CELL_LATTICE) {
+        // M = U_old^-1 U_new: integer, unimodular, and U_old M = U_new again
+        long long M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+        for (int r = 0; r < dim; ++r)
+            for (int c = 0; c < dim; ++c) {
+                double v = 0.0;
+                for (int k = 0; k < dim; ++k) v += ctx->Ainv[r * 3 + k] * cg.A[k * 3 + c];
+                const double q = std::nearbyint(v);
+                if (!(std::fabs(v - q) <= 1e-9) || std::fabs(q) > 1024.0) {
+                    char b[256];
+                    snprintf(b, sizeof b, "md_set_cell: MD_CELL_LATTICE needs U_old^-1 U_new integer (entries up to 2^10); entry (%d, %d) is %.17g", r, c, v);
+                    throw HipError(b);
+                }
+                M[r * 3 + c] = (long long)q;
+            }
+        const long long c00 = M[4] * M[8] - M[5] * M[7], c01 = M[5] * M[6] - M[3] * M[8], c02 = M[3] * M[7] - M[4] * M[6];
+        const long long det = M[0] * c00 + M[1] * c01 + M[2] * c02;
+        if (det != 1 && det != -1) {
+            char b[200];
+            snprintf(b, sizeof b, "md_set_cell: MD_CELL_LATTICE needs |det(U_old^-1 U_new)| = 1, got %lld: the new cell generates another lattice", det);
+            throw HipError(b);
+        }
+        for (int r = 0; r < dim; ++r)
+            for (int c = 0; c < dim; ++c) {
+                double v = 0.0, scale = 0.0;
+                for (int k = 0; k < dim; ++k) {
+                    v += ctx->A[r * 3 + k] * (double)M[k * 3 + c];
+                    scale = std::max(scale, std::fabs(ctx->A[r * 3 + k] * (double)M[k * 3 + c]));
+                }
+                if (!(std::fabs(v - cg.A[r * 3 + c]) <= 8.0 * 2.220446049250313e-16 * scale))
+                    throw HipError("md_set_cell: MD_CELL_LATTICE: U_old M does not give back the new cell; the new cell generates another lattice");
+            }
+        // the integer inverse: adjugate times det (det = +-1).  |M| <= 2^10 keeps its entries below 2^21, so that M^-1 img
+        // (three terms of at most 2^21 2^31) stays far inside 64 bits in the kernel
+        m.minv[0] = det * c00;
+        m.minv[1] = det * (M[2] * M[7] - M[1] * M[8]);
+        m.minv[2] = det * (M[1] * M[5] - M[2] * M[4]);
+        m.minv[3] = det * c01;
+        m.minv[4] = det * (M[0] * M[8] - M[2] * M[6]);
+        m.minv[5] = det * (M[2] * M[3] - M[0] * M[5]);
+        m.minv[6] = det * c02;
+        m.minv[7] = det * (M[1] * M[6] - M[0] * M[7]);
+        m.minv[8] = det * (M[0] * M[4] - M[1] * M[3]);
+    }
+    hipStream_t st = ctx->stream;
+    md_ctx::Naff &Q = ctx->naff;
+    const int n = (int)ctx->n, nb = ctx->nblk;
+    double *mf = Q.marked ? Q.frac.p : nullptr;
+    int32_t *mi = Q.marked ? Q.img.p : nullptr;
+    auto launch = [&](int commit) {
+        DevState s = ctx->dev(ctx->cur);
+        if (mode == MD_CELL_AFFINE) {
+            if (dim == 3)
+                k_set_cell<3, MD_CELL_AFFINE_MODE><<<nb, MD_BLOCK, 0, st>>>(n, s, m, commit, Q.range_error.p, mf, mi);
+            else
+                k_set_cell<2, MD_CELL_AFFINE_MODE><<<nb, MD_BLOCK, 0, st>>>(n, s, m, commit, Q.range_error.p, mf, mi);
+        } else {
+            if (dim == 3)
+                k_set_cell<3, MD_CELL_LATTICE_MODE><<<nb, MD_BLOCK, 0, st>>>(n, s, m, commit, Q.range_error.p, mf, mi);
+            else
+                k_set_cell<2, MD_CELL_LATTICE_MODE><<<nb, MD_BLOCK, 0, st>>>(n, s, m, commit, Q.range_error.p, mf, mi);
+        }
+        HIPCHK(hipGetLastError());
+    };
+    if (mode == MD_CELL_LATTICE) {
+        Q.range_error.ensure(1);
+        HIPCHK(hipMemsetAsync(Q.range_error.p, 0, sizeof(int), st));
+        launch(0);
+        int bad = 0;
+        HIPCHK(hipMemcpyAsync(&bad, Q.range_error.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (bad) throw HipError("md_set_cell: MD_CELL_LATTICE: an image count would leave the int32 range in the new basis");
+    }
+    // the host side first, so that a refusal from the grids leaves the particles where they are
+    struct Saved {
+        double L[3], A[9], Ainv[9], perp[3], volume, skin, rl;
+        int tric, ncell_ext;
+        BoxGrid grid;
+        bool list_valid;
+    } old;
+    for (int c = 0; c < 3; ++c) old.L[c] = ctx->L[c], old.perp[c] = ctx->perp[c];
+    for (int c = 0; c < 9; ++c) old.A[c] = ctx->A[c], old.Ainv[c] = ctx->Ainv[c];
+    old.volume = ctx->volume, old.skin = ctx->skin, old.rl = ctx->rl, old.tric = ctx->tric, old.ncell_ext = ctx->ncell_ext;
+    old.grid = ctx->grid, old.list_valid = ctx->list_valid;
+    auto put = [&](const double *L, const double *A, const double *Ainv, const double *perp, double volume, int tric) {
+        for (int c = 0; c < 3; ++c) ctx->L[c] = L[c], ctx->perp[c] = perp[c];
+        for (int c = 0; c < 9; ++c) ctx->A[c] = A[c], ctx->Ainv[c] = Ainv[c];
+        ctx->volume = volume;
+        ctx->tric = tric;
+    };
+    double Lnew[3] = {1, 1, 1};
+    for (int c = 0; c < dim; ++c) Lnew[c] = cg.A[c * 3 + c];
+    put(Lnew, cg.A, cg.Ainv, cg.perp, cg.volume, cg.tric);
+    // the grid of a pair-walk sampler (md_rdf_, md_mpc_) in the new cell, its cell ranges and sort scratch grown to fit
+    auto regrid_pair_walk = [](md_ctx *c, auto &R, const char *who) {
+        const RdfGrid g = pair_walk_grid(c, who, R.r_max);
+        R.cell_start.ensure((size_t)g.ncell + 1);
+        R.cell_end.ensure((size_t)g.ncell + 1);
+        size_t tmp_bytes = 0;
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, R.keys_in.p, R.keys_out.p, R.vals_in.p, R.vals_out.p,
+                                         (size_t)c->n, 0u, (unsigned)std::max(1, ceil_log2((uint64_t)g.ncell)), c->stream));
+        R.sort_tmp.ensure(tmp_bytes);
+        R.grid = g;
+    };
+    const RdfGrid old_rdf = ctx->rdf.grid, old_mpc = ctx->mpc.grid;
+    const double4 *old_pos[2] = {ctx->sb[0].pos.p, ctx->sb[1].pos.p};
+    try {
+        configure_grid(ctx);
+        if (ctx->rdf.on) regrid_pair_walk(ctx, ctx->rdf, "md_set_cell (md_rdf_ sampler)");
+        if (ctx->mpc.on) regrid_pair_walk(ctx, ctx->mpc, "md_set_cell (md_mpc_ sampler)");
+        // capacities after the new grid and density, as create_common and md_set_skin derive them (buffers only grow; the
+        // rows are allocated aside and swapped in, so that a failed allocation leaves the old ones in place)
+        double frac = 1.0;
+        for (int c = 0; c < dim; ++c) frac *= (double)ctx->grid.ncx[c] / ctx->grid.nc[c];
+        const int64_t gcap = (int64_t)((frac - 1.0) * 1.3 * ctx->ncap) + 4096;
+        ensure_capacity(ctx, ctx->ncap + gcap);
+        double dens = (double)ctx->n_global;
+        dens /= ctx->volume;
+        double vol = (dim == 3) ? 4.18879020478639 * ctx->rl * ctx->rl * ctx->rl : 3.14159265358979 * ctx->rl * ctx->rl;
+        int maxn = ((int)(dens * vol * 1.35) + 24 + 3) & ~3;
+        if (maxn > ctx->maxn) {
+            DBuf<uint32_t> rows;
+            DBuf<uint16_t> rows16;
+            rows.alloc((size_t)ctx->ntiles * maxn * 64);
+            rows16.alloc((size_t)ctx->ntiles * maxn * 64);
+            std::swap(ctx->nlist.p, rows.p);
+            std::swap(ctx->nlist.n, rows.n);
+            std::swap(ctx->nlist16.p, rows16.p);
+            std::swap(ctx->nlist16.n, rows16.n);
+            ctx->maxn = maxn;
+            old.list_valid = false; // (the rows of the old list went with the old buffers)
+        }
+    } catch (...) {
+        (void)hipGetLastError();
+        put(old.L, old.A, old.Ainv, old.perp, old.volume, old.tric);
+        ctx->skin = old.skin, ctx->rl = old.rl, ctx->ncell_ext = old.ncell_ext, ctx->grid = old.grid;
+        // (a state buffer that was grown before the failure holds the owned particles only: the list's ghosts are gone)
+        ctx->list_valid = old.list_valid && ctx->sb[0].pos.p == old_pos[0] && ctx->sb[1].pos.p == old_pos[1];
+        ctx->rdf.grid = old_rdf, ctx->mpc.grid = old_mpc;
+        throw;
+    }
+    launch(1);
+    ctx->list_valid = false;
+    ctx->inner_valid = false;
+    ctx->hess.frozen = false;
+    ctx->target_interval = 8;
+    ctx->rate_known = false;
+    HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+int md_nonaffine_mark(md_ctx *ctx)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_nonaffine_mark: not available on a slab-decomposition handle");
+    require_state(ctx, "md_nonaffine_mark");
+    md_ctx::Naff &Q = ctx->naff;
+    const size_t nd = (size_t)ctx->n * ctx->dim;
+    Q.marked = false;
+    Q.frac.ensure(nd);
+    Q.img.ensure(nd);
+    DevState s = ctx->dev(ctx->cur);
+    if (ctx->dim == 3)
+        k_naff_mark<3><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, naff_cell(ctx), Q.frac.p, Q.img.p);
+    else
+        k_naff_mark<2><<<ctx->nblk, MD_BLOCK, 0, ctx->stream>>>((int)ctx->n, s, naff_cell(ctx), Q.frac.p, Q.img.p);
+    HIPCHK(hipGetLastError());
+    Q.marked = true;
+    API_END
+}
+
+int md_nonaffine(md_ctx *ctx, double *sums, double *u)
+{
+    API_BEGIN
+    if (ctx->dom.on) throw HipError("md_nonaffine: not available on a slab-decomposition handle");
+    require_state(ctx, "md_nonaffine");
+    md_ctx::Naff &Q = ctx->naff;
+    if (!Q.marked)
+        throw HipError("md_nonaffine: no mark (call md_nonaffine_mark first; an md_upload of positions discards the mark)");
+    if (!sums) throw HipError("md_nonaffine: sums is null");
+    const size_t nd = (size_t)ctx->n * ctx->dim;
+    const int nb = ctx->nblk;
+    hipStream_t st = ctx->stream;
+    if (u) Q.u.ensure(nd);
+    Q.part.ensure((size_t)MD_NAFF_NSUM * nb);
+    Q.pmax.ensure(nb);
+    Q.pid.ensure(nb);
+    Q.gmax.ensure(1);
+    Q.out.ensure(8);
+    HIPCHK(hipMemsetAsync(Q.gmax.p, 0, sizeof(unsigned long long), st));
+    DevState s = ctx->dev(ctx->cur);
+    double *uo = u ? Q.u.p : nullptr;
+    if (ctx->dim == 3)
+        k_naff<3><<<nb, MD_BLOCK, 0, st>>>((int)ctx->n, s, naff_cell(ctx), Q.frac.p, Q.img.p, uo, Q.part.p, Q.pmax.p, Q.pid.p, Q.gmax.p);
+    else
+        k_naff<2><<<nb, MD_BLOCK, 0, st>>>((int)ctx->n, s, naff_cell(ctx), Q.frac.p, Q.img.p, uo, Q.part.p, Q.pmax.p, Q.pid.p, Q.gmax.p);
+    k_naff_finish<<<MD_NAFF_NSUM + 1, MD_BLOCK, 0, st>>>(nb, (int)ctx->n, Q.part.p, Q.pmax.p, Q.pid.p, Q.gmax.p, Q.out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(sums, Q.out.p, sizeof(double) * 8, hipMemcpyDeviceToHost, st));
+    if (u) HIPCHK(hipMemcpyAsync(u, Q.u.p, sizeof(double) * nd, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     API_END
 }
 

@@ -94,6 +94,40 @@ class MDDevice:
     def set_inner_skin(self, inner_skin):
         self._chk(self._L.md_set_inner_skin(self._h, float(inner_skin)))
 
+    # -- the cell of a live handle -----------------------------------------------------------
+    CELL_AFFINE, CELL_LATTICE = _lib.MD_CELL_AFFINE, _lib.MD_CELL_LATTICE
+
+    def set_cell(self, unitcell, mode=_lib.MD_CELL_AFFINE):
+        """Change the unit cell of the handle (md_set_cell) and carry the particles along: CELL_AFFINE keeps fractional
+        coordinates (forces stay those of the old cell until the next evaluation), CELL_LATTICE keeps Cartesian positions
+        in a cell that generates the same lattice.  unitcell: a box length, d lengths or a d x d matrix (columns = lattice
+        vectors), as the constructor takes.  A refusal (MdhipError) leaves the handle as it was."""
+        box = np.asarray(unitcell, dtype=np.float64)
+        if box.ndim == 0:
+            box = np.eye(self.dim) * float(box)
+        elif box.ndim == 1:
+            box = np.diag(box)
+        cell = np.ascontiguousarray(box[: self.dim, : self.dim])
+        cm = np.ascontiguousarray(cell.T)
+        self._chk(self._L.md_set_cell(self._h, _dp(cm), int(mode)))
+        self.unitcell = cell
+
+    def nonaffine_mark(self):
+        """Mark the current frame (md_nonaffine_mark): fractional coordinates and image counts by particle id."""
+        self._chk(self._L.md_nonaffine_mark(self._h))
+
+    def nonaffine(self, fields=False):
+        """The displacement since the mark with the affine part taken out (md_nonaffine): dict(sum_u float64[d], sum_u2,
+        sum_u4, max_u2, argmax (particle id), n) and with fields=True u float64[N, d] by particle id; waits."""
+        sums = np.zeros(8)
+        u = np.empty((self.n, self.dim)) if fields else None
+        self._chk(self._L.md_nonaffine(self._h, _dp(sums), _dp(u)))
+        out = dict(sum_u=sums[: self.dim].copy(), sum_u2=sums[3], sum_u4=sums[4], max_u2=sums[5], argmax=int(sums[6]),
+                   n=int(sums[7]), sums=sums)
+        if fields:
+            out["u"] = u
+        return out
+
     # -- state ----------------------------------------------------------------------------
     def upload(self, x=None, v=None, f=None, images=None, diameters=None):
         shp = (self.n, self.dim)
