@@ -893,6 +893,33 @@ int md_set_cell(md_ctx *ctx, const double *box, int mode);
 int md_nonaffine_mark(md_ctx *ctx);
 int md_nonaffine(md_ctx *ctx, double *sums, double *u);
 
+/* Scale the whole frame of a live handle isotropically and KEEP the Verlet rows (new relative to the reference, which has no
+ * barostat).  About the origin of the handle's own unwrapped frame: every entry of the cell matrix is
+ * multiplied by mu (one rounding each; the result is validated and inverted exactly as in md_create / md_set_cell), and one
+ * pass over the state records does x <- mu x (the diameter untouched), v <- vscale v, one product per component, no fma --
+ * numpy's mu * x reproduces both bit for bit.  Image counts, ids and forces are untouched (FORCES ARE THOSE OF THE OLD CELL
+ * until the next evaluation, as with md_set_cell); nothing is wrapped, so frac + img is kept up to the rounding of the
+ * products and a mark of md_nonaffine_mark stays valid.  The result differs from md_set_cell(mu U, MD_CELL_AFFINE) by
+ * rounding only (that one wraps, and goes through fractional coordinates).
+ * The rows: the same pass scales the reference positions of the outer rows (x0, list build) and of the inner rows (x1,
+ * last prune).  Rows built at radius rl are the rows of radius mu rl in the scaled frame, so they stay, and the step loop
+ * gets the skins they still leave beyond the cutoff, which does not scale: with m0 (m1) the product of the factors since the
+ * build (the last prune), skin_eff = m0 (cutoff + skin) - cutoff, inner_eff = m1 (cutoff + inner skin) - cutoff, and the
+ * displacement d1 between the two reference frames times mu, rounded up.  md_list_rows reports these.  *rows_kept = 1 when
+ * the outer rows stayed; 0 when the list was retired and the next evaluation builds in the new cell with the full skin:
+ * skin_eff below two thirds of the configured skin, some particle further than skin_eff / 2 from its scaled x0 (measured in the
+ * same pass), no valid list, or a handle whose rows are not the tiled two-level kind (user potential, skin 0, rows that do
+ * not fit LDS).  The inner rows alone are dropped (the next step prunes) when inner_eff falls below two thirds of the inner skin or a
+ * particle is beyond min(inner_eff / 2, skin_eff / 2 - d1) of its scaled x1.  The cell grid of the list, and the buffer
+ * capacities that follow it, are derived again at the next build, not here; the grids of md_rdf_ / md_mpc_ are derived
+ * again here; the frozen operator of md_hess_ / md_elas_ is dropped; md_stress_, md_boo_, md_cluster_ read the records of
+ * the moment.  rows_kept may be NULL.  Waits.
+ * Refused, with the handle exactly as before: mu or vscale not finite, mu <= 0; a slab handle; a handle whose state a
+ * failed step loop left incomplete; a frame in flight; a new face distance below 3 * list_cutoff, or below 3 * r_max of
+ * md_rdf_ / md_mpc_; a handle with md_dyn_, md_sq_, md_cur_, md_chi4_ or md_cage_ set up (the message names the sampler).
+ * A handle on which md_scale_cell is never called behaves exactly as before.                                             */
+int md_scale_cell(md_ctx *ctx, double mu, double vscale, int *rows_kept);
+
 /* Library build info: returns e.g. "mdhip 0.1 gfx950". */
 const char *md_version(void);
 

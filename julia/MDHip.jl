@@ -23,7 +23,7 @@ export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, Pseudo
        CurrentCorrelations, current_cl, current_ct, current_cl0, current_ct0, vacf, vacf0, write_currents, write_vacf,
        cur_last, mpc_setup!, mpc_marks!, mpc_sample!, mpc_reset!, mpc_last, mpc_read,
        simple_shear, pure_shear, volumetric, set_unitcell!, deform!, reduce_cell!, gauss_reduce, nonaffine_mark!, nonaffine,
-       athermal_quasistatic_shear!
+       athermal_quasistatic_shear!, scale_cell!
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -1497,6 +1497,24 @@ function device_set_cell!(state::SimulationState, U::AbstractMatrix, mode::Integ
     check(dev, ccall((:md_set_cell, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Cint), dev.h, box, mode))
     state.unitcell = box; state.system.unitcell = box
     return nothing
+end
+
+# ---- constant pressure: md_scale_cell (moleculardynamics/jl_amd/barostat.py, DESIGN.md section 26) ----
+# The device call of stochastic cell rescaling.  run_simulation!'s barostat keyword exists in the Python driver only: the
+# Julia run loop does not drive the coupling.
+"""
+    scale_cell!(state, mu, vscale=1.0) -> rows_kept
+
+Scale the whole frame isotropically: cell and positions times mu, velocities times vscale, nothing wrapped; the Verlet rows
+are kept with the skins they still leave (1) or retired (0).  Forces are those of the old cell until the next evaluation.
+"""
+function scale_cell!(state::SimulationState, mu::Real, vscale::Real=1.0)
+    dev = state.system.device
+    kept = Ref{Cint}(0)
+    check(dev, ccall((:md_scale_cell, LIB), Cint, (Ptr{Cvoid}, Float64, Float64, Ptr{Cint}), dev.h, mu, vscale, kept))
+    box = Float64(mu) .* Matrix{Float64}(state.unitcell)
+    state.unitcell = box; state.system.unitcell = box
+    return Int(kept[])
 end
 
 "mark the frame the device holds: fractional coordinates and image counts by particle index"

@@ -43,6 +43,7 @@ EXPORTS = [
     "md_hess_setup", "md_hess_apply", "md_hess_blocks", "md_hess_lanczos", "md_hess_ritz",
     "md_elas_affine", "md_elas_solve",
     "md_set_cell", "md_nonaffine_mark", "md_nonaffine",
+    "md_scale_cell",
 ]
 
 
@@ -287,6 +288,8 @@ def load():
     L.md_nonaffine_mark.restype = C.c_int
     L.md_nonaffine.argtypes = [vp, dp, dp]
     L.md_nonaffine.restype = C.c_int
+    L.md_scale_cell.argtypes = [vp, C.c_double, C.c_double, C.POINTER(C.c_int)]
+    L.md_scale_cell.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -25,6 +25,7 @@
 #include "md_hess.hpp"
 #include "md_elas.hpp"
 #include "md_cell.hpp"
+#include "md_baro.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -375,6 +376,13 @@ struct md_ctx {
     bool rate_known = false;
     double safety = 0.97;       // fraction of the validity radii the plan uses
     int64_t st_prunes = 0;
+    // md_scale_cell (md_baro.hpp): the product of its factors since the outer build (m0) and since the last prune (m1),
+    // and whether there was any -- a list that was never scaled uses skin and inner_skin as they are, not times 1.0.
+    // grid_stale: the cell changed under live rows; the cell grid and the capacities follow at the next build.
+    double m0 = 1.0, m1 = 1.0;
+    bool scaled0 = false, scaled1 = false;
+    bool grid_stale = false;
+    DBuf<unsigned long long> scale_dmax; // what the last md_scale_cell's pass reported (md_baro.hpp, MD_SCALE_NOUT words)
 
     // stats / profiling
     int64_t st_steps = 0, st_rebuilds = 0, st_viol = 0;
@@ -645,6 +653,14 @@ namespace {
 
 inline int nblocks(int64_t n) { return (int)((n + MD_BLOCK - 1) / MD_BLOCK); }
 
+// What the rows in use still allow.  Rows built at radius rl are, after isotropic scales of the
+// frame by a total of m0, complete about the scaled x0 to m0 * rl; the inner rows likewise to m1 * (cutoff + inner skin)
+// about the scaled x1.  The cutoff does not scale, so the skins left are these.  Without a scale since the build (the
+// prune) they are the configured doubles themselves.
+inline double rl_eff(const md_ctx *c) { return c->scaled0 ? c->m0 * c->rl : c->rl; }
+inline double skin_eff(const md_ctx *c) { return c->scaled0 ? c->m0 * c->rl - c->rc : c->skin; }
+inline double inner_eff(const md_ctx *c) { return c->scaled1 ? c->m1 * (c->rc + c->inner_skin) - c->rc : c->inner_skin; }
+
 __global__ void k_init_state(int n, int64_t cap, DevState s, int dim)
 {
     int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -835,6 +851,7 @@ void configure_grid(md_ctx *c)
     c->cell_start.ensure(ncell + 1);
     c->cell_end.ensure(ncell + 1);
     c->list_valid = false;
+    c->grid_stale = false;
 }
 
 // Smallest double t with sqrt(t) >= r (sqrt correctly rounded, as IEEE and Julia's sqrt are): the reference
@@ -1108,6 +1125,8 @@ void rebuild_t(md_ctx *c)
     c->list_valid = true;
     c->steps_since_build = 0;
     c->st_rebuilds++;
+    c->m0 = c->m1 = 1.0; // (md_scale_cell: fresh rows, the full skin again)
+    c->scaled0 = c->scaled1 = false;
     c->inner_valid = false; // the next force evaluation is a prune step
     // (a slab handle prunes only when its caller schedules prune steps: md_dom_enable_pruning)
     c->prune_on = c->use_tiles && (!c->dom.on || c->dom.prune_enabled) && c->skin > 0.0 && c->inner_skin_req > 0.0 &&
@@ -1129,8 +1148,30 @@ void rebuild_t(md_ctx *c)
     }
 }
 
+// md_scale_cell changed the cell under live rows and left the cell grid alone (ghost slots, gowner and the halo lists
+// belong to the grid they were built on): the grid of the new cell, and the capacities that follow it as in md_set_skin /
+// md_set_cell, just ahead of the build that needs them.  (No row is live here: plain reallocation.)
+void regrid_after_scale(md_ctx *c)
+{
+    configure_grid(c);
+    double frac = 1.0;
+    for (int d = 0; d < c->dim; ++d) frac *= (double)c->grid.ncx[d] / c->grid.nc[d];
+    const int64_t gcap = (int64_t)((frac - 1.0) * 1.3 * c->ncap) + 4096;
+    ensure_capacity(c, c->ncap + gcap);
+    double dens = (double)c->n_global;
+    dens /= c->volume;
+    double vol = (c->dim == 3) ? 4.18879020478639 * c->rl * c->rl * c->rl : 3.14159265358979 * c->rl * c->rl;
+    int maxn = ((int)(dens * vol * 1.35) + 24 + 3) & ~3;
+    if (maxn > c->maxn) {
+        c->maxn = maxn;
+        c->nlist.alloc((size_t)c->ntiles * c->maxn * 64);
+        c->nlist16.alloc((size_t)c->ntiles * c->maxn * 64);
+    }
+}
+
 void rebuild(md_ctx *c)
 {
+    if (c->grid_stale) regrid_after_scale(c);
     if (c->dim == 3)
         rebuild_t<3>(c);
     else
@@ -1281,6 +1322,8 @@ void launch_force_tpu(md_ctx *c, bool want_uw, bool kick, double dt, int step, i
 #undef LT
     if (prune_step) {
         c->inner_valid = true;
+        c->m1 = 1.0; // (md_scale_cell: fresh inner rows, the full inner skin again)
+        c->scaled1 = false;
         c->steps_since_prune = 0;
         c->st_prunes++;
     }
@@ -1374,8 +1417,8 @@ void launch_kickdrift(md_ctx *c, bool nvt, double dt, bool check, int step, Buss
     DevState s = c->dev(c->cur);
     int nb = c->nblk;
     // displacement limits (see k_kickdrift); INFINITY disables the check (rebuild-every-step mode)
-    double skin_half = check ? 0.5 * c->skin : INFINITY;
-    double inner_half = check ? (c->inner_valid ? 0.5 * c->inner_skin : 0.5 * c->skin) : INFINITY;
+    double skin_half = check ? 0.5 * skin_eff(c) : INFINITY;
+    double inner_half = check ? (c->inner_valid ? 0.5 * inner_eff(c) : 0.5 * skin_eff(c)) : INFINITY;
     int use_d1 = c->inner_valid ? 1 : 0;
     prof_begin(c, 1);
     if (c->dim == 3) {
@@ -1501,8 +1544,8 @@ void launch_step_tpu(md_ctx *c, bool want_uw, double dt, int step)
     const uint16_t *rows16 = use_inner ? c->nlist16_in.p : c->nlist16.p;
     const int32_t *rowmax = use_inner ? c->nmax_tile_in.p : c->nmax_tile.p;
     // displacement limits of the rows this step walks (k_kickdrift's rule)
-    double skin_half = 0.5 * c->skin;
-    double inner_half = use_inner ? 0.5 * c->inner_skin : 0.5 * c->skin;
+    double skin_half = 0.5 * skin_eff(c);
+    double inner_half = use_inner ? 0.5 * inner_eff(c) : 0.5 * skin_eff(c);
     int use_d1 = use_inner ? 1 : 0;
     DevState s = c->dev(c->cur); // x1 = the prune positions while the inner rows are valid, else x0
     double rin = c->rc + c->inner_skin;
@@ -1578,6 +1621,8 @@ void launch_step_tpu(md_ctx *c, bool want_uw, double dt, int step)
     c->fz_a ^= 1;
     if (prune_step) {
         c->inner_valid = true;
+        c->m1 = 1.0; // (md_scale_cell: fresh inner rows, the full inner skin again)
+        c->scaled1 = false;
         c->steps_since_prune = 0;
         c->st_prunes++;
     }
@@ -2865,7 +2910,10 @@ int md_list_rows(md_ctx *ctx, int which, double *info, int32_t *entries, int64_t
             memcpy(&d12, &bits, sizeof d12);
             d1 = std::sqrt(d12);
         }
-        const double v[MD_LIST_ROWS_INFO] = {ctx->rc, ctx->skin, ctx->rl, inner ? ctx->inner_skin : 0.0, d1,
+        // (after md_scale_cell: what the kept rows still cover -- the effective skin, list radius and inner skin; d1 was
+        // scaled on the device)
+        const double v[MD_LIST_ROWS_INFO] = {ctx->rc, valid ? skin_eff(ctx) : ctx->skin, valid ? rl_eff(ctx) : ctx->rl,
+                                             inner ? inner_eff(ctx) : 0.0, d1,
                                              valid ? 1.0 : 0.0, inner ? 1.0 : 0.0, (valid && ctx->use_tiles) ? 1.0 : 0.0,
                                              (valid && ctx->use_tiles && !ctx->have_nlist32) ? 1.0 : 0.0,
                                              (valid && ctx->own_first) ? 1.0 : 0.0,
@@ -4801,6 +4849,18 @@ static NaffCell naff_cell(const md_ctx *ctx)
     return c;
 }
 
+// the grid of a pair-walk sampler (md_rdf_, md_mpc_) in the new cell, its cell ranges and sort scratch grown to fit
+static const auto regrid_pair_walk = [](md_ctx *c, auto &R, const char *who) {
+    const RdfGrid g = pair_walk_grid(c, who, R.r_max);
+    R.cell_start.ensure((size_t)g.ncell + 1);
+    R.cell_end.ensure((size_t)g.ncell + 1);
+    size_t tmp_bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, R.keys_in.p, R.keys_out.p, R.vals_in.p, R.vals_out.p,
+                                     (size_t)c->n, 0u, (unsigned)std::max(1, ceil_log2((uint64_t)g.ncell)), c->stream));
+    R.sort_tmp.ensure(tmp_bytes);
+    R.grid = g;
+};
+
 int md_set_cell(md_ctx *ctx, const double *box, int mode)
 {
     API_BEGIN
@@ -4931,19 +4991,9 @@ int md_set_cell(md_ctx *ctx, const double *box, int mode)
     double Lnew[3] = {1, 1, 1};
     for (int c = 0; c < dim; ++c) Lnew[c] = cg.A[c * 3 + c];
     put(Lnew, cg.A, cg.Ainv, cg.perp, cg.volume, cg.tric);
-    // the grid of a pair-walk sampler (md_rdf_, md_mpc_) in the new cell, its cell ranges and sort scratch grown to fit
-    auto regrid_pair_walk = [](md_ctx *c, auto &R, const char *who) {
-        const RdfGrid g = pair_walk_grid(c, who, R.r_max);
-        R.cell_start.ensure((size_t)g.ncell + 1);
-        R.cell_end.ensure((size_t)g.ncell + 1);
-        size_t tmp_bytes = 0;
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, R.keys_in.p, R.keys_out.p, R.vals_in.p, R.vals_out.p,
-                                         (size_t)c->n, 0u, (unsigned)std::max(1, ceil_log2((uint64_t)g.ncell)), c->stream));
-        R.sort_tmp.ensure(tmp_bytes);
-        R.grid = g;
-    };
     const RdfGrid old_rdf = ctx->rdf.grid, old_mpc = ctx->mpc.grid;
     const double4 *old_pos[2] = {ctx->sb[0].pos.p, ctx->sb[1].pos.p};
+    const bool old_stale = ctx->grid_stale; // (md_scale_cell: the grid put back below may still be owed to a build)
     try {
         configure_grid(ctx);
         if (ctx->rdf.on) regrid_pair_walk(ctx, ctx->rdf, "md_set_cell (md_rdf_ sampler)");
@@ -4977,6 +5027,7 @@ int md_set_cell(md_ctx *ctx, const double *box, int mode)
         // (a state buffer that was grown before the failure holds the owned particles only: the list's ghosts are gone)
         ctx->list_valid = old.list_valid && ctx->sb[0].pos.p == old_pos[0] && ctx->sb[1].pos.p == old_pos[1];
         ctx->rdf.grid = old_rdf, ctx->mpc.grid = old_mpc;
+        ctx->grid_stale = old_stale;
         throw;
     }
     launch(1);
@@ -4986,6 +5037,151 @@ int md_set_cell(md_ctx *ctx, const double *box, int mode)
     ctx->target_interval = 8;
     ctx->rate_known = false;
     HIPCHK(hipStreamSynchronize(st));
+    API_END
+}
+
+// Isotropic scale of the whole frame that keeps the Verlet rows (md_baro.hpp).
+int md_scale_cell(md_ctx *ctx, double mu, double vscale, int *rows_kept)
+{
+    API_BEGIN
+    if (!std::isfinite(mu) || !(mu > 0.0)) throw HipError("md_scale_cell: mu must be finite and > 0");
+    if (!std::isfinite(vscale)) throw HipError("md_scale_cell: vscale must be finite");
+    if (ctx->dom.on) throw HipError("md_scale_cell: not available on a slab-decomposition handle");
+    require_state(ctx, "md_scale_cell");
+    if (ctx->snap_pending) throw HipError("md_scale_cell: a frame is in flight (collect it with md_snapshot_end first)");
+    const char *holder = ctx->dyn.on ? "md_dyn" : ctx->sq.on ? "md_sq" : ctx->current.on ? "md_cur" : ctx->chi4.on ? "md_chi4"
+                         : ctx->cage.on ? "md_cage" : nullptr;
+    if (holder)
+        throw HipError(std::string("md_scale_cell: the ") + holder + "_ sampler is set up on this handle; its stored origins or "
+                       "wave vectors belong to the cell it was set up in");
+    const int dim = ctx->dim;
+    double box[9];
+    {
+#pragma clang fp contract(off)
+        for (int c = 0; c < dim; ++c)
+            for (int r = 0; r < dim; ++r) box[c * dim + r] = mu * ctx->A[r * 3 + c];
+    }
+    CellGeom cg;
+    if (const char *why = cell_geometry(dim, box, cg)) {
+        std::string w(why);
+        throw HipError("md_scale_cell" + w.substr(w.find(':')));
+    }
+    for (int c = 0; c < dim; ++c) {
+        const double need = std::max({ctx->rc, ctx->rdf.on ? ctx->rdf.r_max : 0.0, ctx->mpc.on ? ctx->mpc.r_max : 0.0});
+        if (cg.perp[c] / 3.0 < ctx->rc || cg.perp[c] < 3.0 * need) {
+            char b[360];
+            snprintf(b, sizeof b,
+                     "md_scale_cell: the new cell is too small: the face distance %.17g of lattice direction %d must be >= "
+                     "3*list_cutoff = %.17g%s",
+                     cg.perp[c], c, 3.0 * ctx->rc,
+                     need > ctx->rc ? " and >= 3*r_max of the md_rdf_ / md_mpc_ sampler set up on this handle" : "");
+            throw HipError(b);
+        }
+    }
+    hipStream_t st = ctx->stream;
+    ctx->scale_dmax.ensure(MD_SCALE_NOUT);
+    // the host side first, so that a refusal from the samplers' grids leaves the particles where they are.  The cell grid
+    // of the list is NOT derived again: the live rows' ghost slots and halo lists belong to it (rebuild() does, later);
+    // only the periodic translations in it follow now -- the exports and the ghost refresh read them.
+    struct Saved {
+        double L[3], A[9], Ainv[9], perp[3], volume;
+        BoxGrid grid;
+        RdfGrid rdf, mpc;
+    } old;
+    for (int c = 0; c < 3; ++c) old.L[c] = ctx->L[c], old.perp[c] = ctx->perp[c];
+    for (int c = 0; c < 9; ++c) old.A[c] = ctx->A[c], old.Ainv[c] = ctx->Ainv[c];
+    old.volume = ctx->volume, old.grid = ctx->grid, old.rdf = ctx->rdf.grid, old.mpc = ctx->mpc.grid;
+    for (int c = 0; c < dim; ++c) ctx->L[c] = cg.A[c * 3 + c];
+    for (int c = 0; c < 3; ++c) ctx->perp[c] = cg.perp[c];
+    for (int c = 0; c < 9; ++c) ctx->A[c] = cg.A[c], ctx->Ainv[c] = cg.Ainv[c];
+    ctx->volume = cg.volume;
+    try {
+        if (ctx->rdf.on) regrid_pair_walk(ctx, ctx->rdf, "md_scale_cell (md_rdf_ sampler)");
+        if (ctx->mpc.on) regrid_pair_walk(ctx, ctx->mpc, "md_scale_cell (md_mpc_ sampler)");
+    } catch (...) {
+        (void)hipGetLastError();
+        for (int c = 0; c < 3; ++c) ctx->L[c] = old.L[c], ctx->perp[c] = old.perp[c];
+        for (int c = 0; c < 9; ++c) ctx->A[c] = old.A[c], ctx->Ainv[c] = old.Ainv[c];
+        ctx->volume = old.volume, ctx->rdf.grid = old.rdf, ctx->mpc.grid = old.mpc;
+        throw;
+    }
+    BoxGrid &g = ctx->grid;
+    for (int c = 0; c < dim; ++c) {
+        g.L[c] = ctx->L[c];
+        g.invL[c] = 1.0 / ctx->L[c];
+    }
+    for (int c = 0; c < 9; ++c) g.A[c] = ctx->A[c], g.Ainv[c] = ctx->Ainv[c];
+    ctx->grid_stale = true;
+    ctx->hess.frozen = false;
+
+    // Which rows can stay.  The tiled two-level rows of a built-in potential; anything else (user potentials, skin 0, rows
+    // that did not fit LDS) is scaled and builds again.  Floor: a kept list must leave at least two thirds of the configured
+    // skin (inner skin).  The steps a list lasts are proportional to the skin it has left; couplings of a barostat move it
+    // by parts in a thousand, so a list that has lost a third of its skin has been compressed by hand, and the build it
+    // saves would come a third sooner anyway.  (A non-positive skin covers nothing.)
+    bool keep = ctx->list_valid && ctx->use_tiles && ctx->skin > 0.0 && ctx->pot_kind != POT_CUSTOM;
+    const double m0n = ctx->m0 * mu, m1n = ctx->m1 * mu;
+    const double se = m0n * ctx->rl - ctx->rc, ie = m1n * (ctx->rc + ctx->inner_skin) - ctx->rc;
+    if (keep && !(se >= (2.0 / 3.0) * ctx->skin)) keep = false;
+    bool keep_in = keep && ctx->inner_valid;
+    if (keep_in && !(ie >= (2.0 / 3.0) * ctx->inner_skin)) keep_in = false;
+    if (!keep_in) ctx->inner_valid = false; // (dev(): x1 aliases x0 from here on; the next step prunes, or builds)
+    const int n = (int)ctx->n;
+    const int npos = (keep && !ctx->virtual_ghosts) ? (int)ctx->next : n; // real ghost records go along with their rows
+    const double half_skin = keep ? 0.5 * se : INFINITY, half_inner = keep_in ? 0.5 * ie : INFINITY;
+    unsigned long long hb[MD_SCALE_NOUT] = {0ull, 0ull, 0ull};
+    // From here on the host holds the new cell: a HIP error in the pass or its read-back leaves it unknown whether the
+    // particles went along.  No list is valid then, and every entry that reads the state refuses until a full md_upload
+    // replaces it (state_invalid, as after a failed step loop).
+    try {
+        HIPCHK(hipMemsetAsync(ctx->scale_dmax.p, 0, MD_SCALE_NOUT * sizeof(unsigned long long), st));
+        if (npos > 0) {
+            DevState s = ctx->dev(ctx->cur);
+            const int has_x1 = keep_in ? 1 : 0;
+            if (dim == 3)
+                k_scale_cell<3><<<nblocks(npos), MD_BLOCK, 0, st>>>(n, npos, s, mu, vscale, has_x1, half_skin, half_inner,
+                                                                    ctx->scal.p, ctx->scale_dmax.p);
+            else
+                k_scale_cell<2><<<nblocks(npos), MD_BLOCK, 0, st>>>(n, npos, s, mu, vscale, has_x1, half_skin, half_inner,
+                                                                    ctx->scal.p, ctx->scale_dmax.p);
+            if (keep_in) k_scale_commit<<<1, 1, 0, st>>>(ctx->scal.p, ctx->scale_dmax.p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(hb, ctx->scale_dmax.p, sizeof hb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    } catch (...) {
+        ctx->list_valid = ctx->inner_valid = false;
+        ctx->m0 = ctx->m1 = 1.0;
+        ctx->scaled0 = ctx->scaled1 = false;
+        ctx->state_invalid = true;
+        throw;
+    }
+    double dsq[MD_SCALE_NOUT];
+    memcpy(dsq, hb, sizeof dsq);
+    // the kernel's verdict (k_kickdrift's criterion): dsq[0], dsq[1] are zero unless a particle lies beyond half_skin of
+    // its x0 -- what md_compute_forces and a prune step walk the outer rows on -- or beyond min(half_inner, half_skin - d1)
+    // of its x1; dsq[2] is the d1^2 the kernel formed that limit from
+    if (keep && !(dsq[0] <= half_skin * half_skin)) keep = false;
+    if (keep && keep_in) {
+        const double thr = std::fmin(half_inner, half_skin - std::sqrt(dsq[2]));
+        if (!(thr > 0.0 && dsq[1] <= thr * thr)) keep_in = false;
+    }
+    if (keep) {
+        ctx->m0 = m0n;
+        ctx->scaled0 = true;
+        if (keep_in) {
+            ctx->m1 = m1n;
+            ctx->scaled1 = true;
+        } else {
+            ctx->inner_valid = false;
+        }
+    } else {
+        ctx->list_valid = false;
+        ctx->inner_valid = false;
+    }
+    if (!ctx->inner_valid) ctx->m1 = 1.0, ctx->scaled1 = false;
+    if (!ctx->list_valid) ctx->m0 = 1.0, ctx->scaled0 = false;
+    if (rows_kept) *rows_kept = keep ? 1 : 0;
     API_END
 }
 
@@ -5162,8 +5358,8 @@ int md_run(md_ctx *ctx, int64_t nsteps, double dt, int ensemble, double tau, dou
                 // goes on producing NaNs in that case, it does not stop; an unguarded NaN here ended in a SIGFPE of the
                 // integer divisions below)
                 double r_out = std::isfinite(ctx->d1_rate) ? std::max(ctx->d1_rate, 1e-12) : 1e300;
-                double Rf = std::floor(ctx->safety * 0.5 * ctx->skin / r_out) + 1.0;
-                double Lf = std::floor(ctx->safety * 0.5 * ctx->inner_skin / (1.1 * r_out)) + 1.0;
+                double Rf = std::floor(ctx->safety * 0.5 * skin_eff(ctx) / r_out) + 1.0;
+                double Lf = std::floor(ctx->safety * 0.5 * inner_eff(ctx) / (1.1 * r_out)) + 1.0;
                 int64_t Rmax = (int64_t)std::min(std::max(Rf, 2.0), 4096.0);
                 int64_t Lmax = (int64_t)std::min(std::max(Lf, 2.0), 4096.0);
                 // a build costs about as much as 8 prune steps: take the R <= Rmax with the least
@@ -5268,7 +5464,8 @@ int md_run(md_ctx *ctx, int64_t nsteps, double dt, int ensemble, double tau, dou
                         ctx->d1_rate = 0.5 * (ctx->d1_rate + sample);
                     ctx->rate_known = true;
                     // (a prune this late would buy only a few steps: rebuild unless a full segment still fits)
-                    if (m_was_prune || !(d0 + 0.5 * ctx->inner_skin <= 0.5 * ctx->skin)) {
+                    // (the rows a prune would write have the full inner skin; the outer rows what md_scale_cell left them)
+                    if (m_was_prune || !(d0 + 0.5 * ctx->inner_skin <= 0.5 * skin_eff(ctx))) {
                         if (fused)
                             fused_rebuild();
                         else

@@ -112,6 +112,16 @@ class MDDevice:
         self._chk(self._L.md_set_cell(self._h, _dp(cm), int(mode)))
         self.unitcell = cell
 
+    def scale_cell(self, mu, vscale=1.0):
+        """Scale the whole frame isotropically (md_scale_cell): cell and positions times mu, velocities times vscale, one
+        rounding per component, nothing wrapped -- and the Verlet rows are kept with the skins they still leave (forces stay
+        those of the old cell until the next evaluation).  Returns rows_kept: 1 when the outer rows stayed, 0 when the next
+        evaluation builds the list again.  A refusal (MdhipError) leaves the handle as it was; waits."""
+        kept = C.c_int(0)
+        self._chk(self._L.md_scale_cell(self._h, float(mu), float(vscale), C.byref(kept)))
+        self.unitcell = np.float64(mu) * self.unitcell
+        return int(kept.value)
+
     def nonaffine_mark(self):
         """Mark the current frame (md_nonaffine_mark): fractional coordinates and image counts by particle id."""
         self._chk(self._L.md_nonaffine_mark(self._h))

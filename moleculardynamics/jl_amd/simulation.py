@@ -36,8 +36,8 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, orientational=None, swap=None, sq=None, currents=None, stress=None, four_point=None,
-                   clusters=None, cage=None, bond_order=None):
+                   dynamics=None, orientational=None, swap=None, barostat=None, sq=None, currents=None, stress=None,
+                   four_point=None, clusters=None, cage=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -108,7 +108,32 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     snapshot of that step carries the diameters after the block.  The round counter continues across blocks (and calls
     with the same object).  After each block state.diameters is refreshed, so frames and final.xyz carry the diameters of
     their moment.  Written to pathname/swap.txt.  Not available with a user potential.  With swap=None nothing the run
-    produces changes."""
+    produces changes.
+
+    barostat: a StochasticCellRescaling (barostat.py): after every barostat.every-th step one coupling to its pressure --
+    the cell and the positions are scaled by mu, the velocities by 1 / mu, on the device (md_scale_cell, which keeps the
+    neighbour rows), at the ensemble's target temperature of that step (or barostat.ktemp), and the forces are evaluated
+    in the new cell.  Like swap it CHANGES the run.  Its stops are added to the loop's output steps; at a step it shares it
+    acts after every sampler and after swap, before the thermo line and the frame export of that step, which therefore
+    show the scaled frame.  state.unitcell and state.system.unitcell follow every coupling; the thermo line's density is
+    n / V of the moment; every frame, snapshot and final.xyz carries the cell of its moment.  `params` is not touched
+    (params.rho is the caller's to keep consistent, as with set_unitcell).  Written to pathname/barostat.txt.  Not
+    available with Brownian dynamics.  Refused up front, before any file is opened, together with the samplers that
+    belong to one cell: dynamics=, sq=, currents=, four_point= and cage= store time origins or wave vectors of the cell
+    they were set up in (md_scale_cell refuses them on the device), and rdf=, stress= and orientational= normalise their
+    sums with one volume, which a run whose volume moves does not have.  bond_order=, clusters= and swap= go with it.
+    With barostat=None nothing the run produces changes."""
+    if barostat is not None:
+        one_cell = dict(dynamics=dynamics, sq=sq, currents=currents, four_point=four_point, cage=cage)
+        one_volume = dict(rdf=rdf, stress=stress, orientational=orientational)
+        for name, smp in one_cell.items():
+            if smp is not None:
+                raise ValueError("barostat= cannot be combined with %s=: its stored time origins or wave vectors belong to "
+                                 "the cell it is set up in, and the barostat changes the cell" % name)
+        for name, smp in one_volume.items():
+            if smp is not None:
+                raise ValueError("barostat= cannot be combined with %s=: it normalises its sums with one volume, and the "
+                                 "barostat changes the volume during the run" % name)
     if clusters is not None and clusters.members == "solid":
         if bond_order is None:
             raise ValueError('clusters with members="solid" needs bond_order= in the same run')
@@ -144,11 +169,13 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         samplers.append(orientational)
     run = types.SimpleNamespace(total_steps=total_steps, frequency=frequency, n=n, dim=dim, dt=params.dt,
                                 unitcell=state.unitcell, brownian=brownian, bond_order=bond_order, ensemble=ensemble,
-                                rng=state.rng)
+                                rng=state.rng, potential=pot)
     for s in samplers:
         s._begin(dev, run)
     if swap is not None:
         swap._begin(dev, run)
+    if barostat is not None:
+        barostat._begin(dev, run)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -179,8 +206,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     def collect():
         if pending:
             x, img = dev.snapshot_end()
-            for path, at, mode, diam in pending:
-                writer.submit(_io.write_to_file_lammps, path, at, state.unitcell, n, x, img, diam, dim, mode=mode)
+            for path, at, mode, diam, cell in pending:      # (the cell of the frame's own moment: a barostat moves it)
+                writer.submit(_io.write_to_file_lammps, path, at, cell, n, x, img, diam, dim, mode=mode)
             pending.clear()
 
     step = 0
@@ -190,6 +217,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         stops += [s._next(step) for s in samplers]
         if swap is not None:
             stops.append(swap._next(step))
+        if barostat is not None:
+            stops.append(barostat._next(step))
         last = min(min(t for t in stops if t is not None), total_steps - 1)
         U, W, K = segment(step, last - step + 1)
         collect()                       # the frame exported before this segment: its copy had the whole segment to finish
@@ -203,6 +232,15 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             r = swap._act(dev, last)
             state.diameters = dev.diameters()
             U, W = r["U"], r["W"]
+        if barostat is not None and barostat._next(last) == last:
+            # after every sampler and after swap; no frame is in flight (collect() above).  The cell is replaced by a new
+            # array (never in place: a frame queued earlier keeps the cell of its own moment)
+            r = barostat._act(dev, last, U, W, K, volume)
+            state.unitcell = r["mu"] * np.asarray(state.unitcell, dtype=np.float64)
+            state.system.unitcell = state.unitcell
+            volume = compute_box_volume(state.unitcell)
+            barostat._record(r, volume)
+            U, W, K = r["U"], r["W"], r["K"]
         want_frame = False
         if last % frequency == 0:
             if brownian:
@@ -213,17 +251,18 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             else:
                 temperature = 2.0 * K / state.nf
                 total_energy = (U + pot.energy_lrc(n, volume)) / n      # src/simulation.jl:120-124
-                pressure = W / (dim * volume) + params.rho * temperature    # :128-129
+                rho = params.rho if barostat is None else n / volume
+                pressure = W / (dim * volume) + rho * temperature       # :128-129
                 pressure += pot.pressure_lrc(n, volume)                 # :131
             with open(thermo_file, "a") as io:
                 io.write("%d %.6f %.6f %.6f\n" % (last, total_energy, temperature, pressure))
             state.system.energy_and_forces.energy = U
             state.system.energy_and_forces.virial = W
             if write_trajectory:
-                pending.append((trajectory_file, last, "a", state.diameters))
+                pending.append((trajectory_file, last, "a", state.diameters, state.unitcell))
                 want_frame = True
         if _analysis._next_stop(snapshot_times, last) == last:
-            pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w", state.diameters))
+            pending.append((os.path.join(pathname, f"snapshot.{last}"), last, "w", state.diameters, state.unitcell))
             want_frame = True
         if want_frame:
             dev.snapshot_begin()
@@ -244,6 +283,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         s._finish(dev, run, pathname)
     if swap is not None:
         swap._finish(dev, run, pathname)
+    if barostat is not None:
+        barostat._finish(dev, run, pathname)
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
