@@ -920,6 +920,34 @@ int md_nonaffine(md_ctx *ctx, double *sums, double *u);
  * A handle on which md_scale_cell is never called behaves exactly as before.                                             */
 int md_scale_cell(md_ctx *ctx, double mu, double vscale, int *rows_kept);
 
+/* Map the whole frame of a live handle by a deformation gradient F and KEEP the Verlet rows (new relative to the reference,
+ * which fixes its cell at initialisation, src/initialization.jl:7-18).  F and G are D x D, row-major;
+ * G may be NULL.  About the origin of the handle's own unwrapped frame: the cell becomes F U (row times column, left to
+ * right, every product and sum rounded; validated and inverted as in md_create / md_set_cell), and one pass over the state
+ * records does x <- F x (the diameter untouched) and, with G, v <- G v: row times vector, left to right, every product and
+ * sum rounded, no fma -- the arithmetic of md_set_cell's general branch, which numpy reproduces bit for bit.  G = F^-1 makes
+ * the stored velocities peculiar ones (SLLOD).  Image counts, ids and forces are untouched (FORCES ARE THOSE OF THE OLD CELL
+ * until the next evaluation); nothing is wrapped, so frac + img is kept up to rounding and a mark of md_nonaffine_mark stays
+ * valid.  The result differs from md_set_cell(F U, MD_CELL_AFFINE) by rounding only.
+ * The rows: the same pass maps x0 (list build) and, while the inner rows are valid, x1 (last prune).  With M0 (M1) the product
+ * of the F's since the build (the last prune), s0 <= sigma_min(M0), s1 <= sigma_min(M1) and S >= sigma_max(F) -- exact
+ * singular values from the symmetric eigenproblem of M^T M, widened by a relative 2^-40 in the safe direction --
+ *     skin_eff = s0 (cutoff + skin) - cutoff,  inner_eff = s1 (cutoff + inner skin) - cutoff,  d1 <- S d1 (rounded up),
+ * which md_list_rows reports as after md_scale_cell; its scalars m0, m1 multiply s0, s1 on a handle that sees both calls,
+ * and a handle that sees md_scale_cell alone gets the doubles it always got.  *rows_kept = 0 and both lists retire (the next
+ * evaluation builds in the new cell with the full skin) when skin_eff falls below two thirds of the configured skin, a
+ * particle lies beyond skin_eff / 2 of its mapped x0 (measured in the same pass), the rows are not the tiled two-level kind
+ * (user potential, skin 0, rows that do not fit LDS; the frame is simply mapped), or the call changes the cell between
+ * diagonal and general (kernels that read the live rows branch on that: the first shear of an orthorhombic box costs one
+ * build).  The inner rows alone are dropped by the corresponding inner conditions.  Grids, capacities, md_rdf_ / md_mpc_,
+ * md_hess_ / md_elas_: as md_scale_cell.  rows_kept may be NULL.  Waits.
+ * Refused, with the handle exactly as before: md_scale_cell's refusals, and F or G not finite, det F <= 0.
+ * md_deform_state (read-only): m0[9], m1[9] = M0, M1 as row-major 3 x 3 (identity when nothing was mapped since the build /
+ * prune, or without valid rows; md_scale_cell's factors included), sig[4] = s0, S0, s1, S1 with S0 >= sigma_max(M0),
+ * S1 >= sigma_max(M1).  Any of the three may be NULL.                                                                     */
+int md_deform_cell(md_ctx *ctx, const double *F, const double *G, int *rows_kept);
+int md_deform_state(md_ctx *ctx, double *m0, double *m1, double *sig);
+
 /* Library build info: returns e.g. "mdhip 0.1 gfx950". */
 const char *md_version(void);
 

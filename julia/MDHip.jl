@@ -23,7 +23,7 @@ export Parameters, NVT, NVE, Brownian, Potential, evaluate, LennardJones, Pseudo
        CurrentCorrelations, current_cl, current_ct, current_cl0, current_ct0, vacf, vacf0, write_currents, write_vacf,
        cur_last, mpc_setup!, mpc_marks!, mpc_sample!, mpc_reset!, mpc_last, mpc_read,
        simple_shear, pure_shear, volumetric, set_unitcell!, deform!, reduce_cell!, gauss_reduce, nonaffine_mark!, nonaffine,
-       athermal_quasistatic_shear!, scale_cell!
+       athermal_quasistatic_shear!, scale_cell!, deform_cell!, deform_state
 
 const LIB = get(ENV, "MDHIP_LIB", joinpath(@__DIR__, "..", "moleculardynamics", "jl_amd", "csrc", "libmdhip.so"))
 
@@ -1515,6 +1515,35 @@ function scale_cell!(state::SimulationState, mu::Real, vscale::Real=1.0)
     box = Float64(mu) .* Matrix{Float64}(state.unitcell)
     state.unitcell = box; state.system.unitcell = box
     return Int(kept[])
+end
+
+# ---- shear flow: md_deform_cell (moleculardynamics/jl_amd/deformation.py ShearFlow, DESIGN.md section 27) ----
+# The device call of SLLOD in a deforming cell.  run_simulation!'s shear keyword exists in the Python driver only: the Julia
+# run loop does not drive the flow.
+"""
+    deform_cell!(state, F, G=nothing) -> rows_kept
+
+Map the whole frame by the deformation gradient F: the cell becomes F U, positions F x and, with G, velocities G v
+(G = inv(F): peculiar velocities), nothing wrapped; the Verlet rows are kept with the skins they still leave (1) or retired
+(0).  Forces are those of the old cell until the next evaluation.
+"""
+function deform_cell!(state::SimulationState, F::AbstractMatrix, G::Union{AbstractMatrix,Nothing}=nothing)
+    dev = state.system.device
+    kept = Ref{Cint}(0)
+    Fr = Matrix{Float64}(permutedims(F))           # row-major for the C side
+    Gr = G === nothing ? C_NULL : Matrix{Float64}(permutedims(G))
+    check(dev, ccall((:md_deform_cell, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Cint}), dev.h, Fr, Gr, kept))
+    box = Matrix{Float64}(F) * Matrix{Float64}(state.unitcell)
+    state.unitcell = box; state.system.unitcell = box
+    return Int(kept[])
+end
+
+"(M0, M1, sig): the maps since the list build and the last prune (d x d) and the singular-value bounds s0, S0, s1, S1"
+function deform_state(dev::Device)
+    m0 = zeros(9); m1 = zeros(9); sig = zeros(4)
+    check(dev, ccall((:md_deform_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), dev.h, m0, m1, sig))
+    d = dev.dim
+    return permutedims(reshape(m0, 3, 3))[1:d, 1:d], permutedims(reshape(m1, 3, 3))[1:d, 1:d], sig
 end
 
 "mark the frame the device holds: fractional coordinates and image counts by particle index"

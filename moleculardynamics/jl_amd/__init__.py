@@ -16,7 +16,7 @@ from .minimize import fire_minimize, minimize
 from .montecarlo import SwapMonteCarlo, swap_rounds
 from .vibrations import HessianOperator, elastic_moduli, lowest_modes, participation_ratio
 from .deformation import (simple_shear, pure_shear, volumetric, set_unitcell, deform, reduce_cell, gauss_reduce,
-                          athermal_quasistatic_shear)
+                          athermal_quasistatic_shear, ShearFlow, shear_flow_update, shear_columns)
 from .barostat import StochasticCellRescaling, crescale_factor
 from .device import MDDevice
 from ._lib import MdhipError
@@ -31,5 +31,6 @@ __all__ = [
     "FourPoint", "CurrentCorrelations", "OrientationalCorrelation", "compute_orientational_correlation",
     "compute_marked_correlation", "SwapMonteCarlo", "swap_rounds", "HessianOperator", "lowest_modes", "participation_ratio",
     "elastic_moduli", "simple_shear", "pure_shear", "volumetric", "set_unitcell", "deform", "reduce_cell", "gauss_reduce",
-    "athermal_quasistatic_shear", "StochasticCellRescaling", "crescale_factor",
+    "athermal_quasistatic_shear", "StochasticCellRescaling", "crescale_factor", "ShearFlow", "shear_flow_update",
+    "shear_columns",
 ]

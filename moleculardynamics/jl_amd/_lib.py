@@ -44,6 +44,7 @@ EXPORTS = [
     "md_elas_affine", "md_elas_solve",
     "md_set_cell", "md_nonaffine_mark", "md_nonaffine",
     "md_scale_cell",
+    "md_deform_cell", "md_deform_state",
 ]
 
 
@@ -290,6 +291,10 @@ def load():
     L.md_nonaffine.restype = C.c_int
     L.md_scale_cell.argtypes = [vp, C.c_double, C.c_double, C.POINTER(C.c_int)]
     L.md_scale_cell.restype = C.c_int
+    L.md_deform_cell.argtypes = [vp, dp, dp, C.POINTER(C.c_int)]
+    L.md_deform_cell.restype = C.c_int
+    L.md_deform_state.argtypes = [vp, dp, dp, dp]
+    L.md_deform_state.restype = C.c_int
     for name in EXPORTS:
         if name.startswith("md_dom_") or name in ("md_create_domain", "md_set_stream"):
             getattr(L, name).restype = C.c_int

@@ -26,6 +26,7 @@
 #include "md_elas.hpp"
 #include "md_cell.hpp"
 #include "md_baro.hpp"
+#include "md_deform.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -383,6 +384,12 @@ struct md_ctx {
     bool scaled0 = false, scaled1 = false;
     bool grid_stale = false;
     DBuf<unsigned long long> scale_dmax; // what the last md_scale_cell's pass reported (md_baro.hpp, MD_SCALE_NOUT words)
+    // md_deform_cell (md_deform.hpp): the product of its F's since the outer build (Md0) and since the
+    // last prune (Md1), row-major 3 x 3, and rigorous bounds on their singular values: ds <= sigma_min, dS >= sigma_max.
+    // A list that was never deformed uses none of them (deformed0 / deformed1 false): md_scale_cell's doubles as they were.
+    double Md0[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, Md1[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double ds0 = 1.0, dS0 = 1.0, ds1 = 1.0, dS1 = 1.0;
+    bool deformed0 = false, deformed1 = false;
 
     // stats / profiling
     int64_t st_steps = 0, st_rebuilds = 0, st_viol = 0;
@@ -657,9 +664,35 @@ inline int nblocks(int64_t n) { return (int)((n + MD_BLOCK - 1) / MD_BLOCK); }
 // frame by a total of m0, complete about the scaled x0 to m0 * rl; the inner rows likewise to m1 * (cutoff + inner skin)
 // about the scaled x1.  The cutoff does not scale, so the skins left are these.  Without a scale since the build (the
 // prune) they are the configured doubles themselves.
-inline double rl_eff(const md_ctx *c) { return c->scaled0 ? c->m0 * c->rl : c->rl; }
-inline double skin_eff(const md_ctx *c) { return c->scaled0 ? c->m0 * c->rl - c->rc : c->skin; }
-inline double inner_eff(const md_ctx *c) { return c->scaled1 ? c->m1 * (c->rc + c->inner_skin) - c->rc : c->inner_skin; }
+// After md_deform_cell (section 27) the factor is a lower bound on the smallest singular value of the accumulated map: the
+// scalar of md_scale_cell times ds0 (ds1).  A list that was only ever scaled takes the first branch: the doubles of section 26.
+inline double rl_eff(const md_ctx *c)
+{
+    if (c->deformed0) return (c->m0 * c->ds0) * c->rl;
+    return c->scaled0 ? c->m0 * c->rl : c->rl;
+}
+inline double skin_eff(const md_ctx *c)
+{
+    if (c->deformed0) return (c->m0 * c->ds0) * c->rl - c->rc;
+    return c->scaled0 ? c->m0 * c->rl - c->rc : c->skin;
+}
+inline double inner_eff(const md_ctx *c)
+{
+    if (c->deformed1) return (c->m1 * c->ds1) * (c->rc + c->inner_skin) - c->rc;
+    return c->scaled1 ? c->m1 * (c->rc + c->inner_skin) - c->rc : c->inner_skin;
+}
+inline void deform_reset1(md_ctx *c)
+{
+    for (int i = 0; i < 9; ++i) c->Md1[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    c->ds1 = c->dS1 = 1.0;
+    c->deformed1 = false;
+}
+inline void deform_reset0(md_ctx *c)
+{
+    for (int i = 0; i < 9; ++i) c->Md0[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    c->ds0 = c->dS0 = 1.0;
+    c->deformed0 = false;
+}
 
 __global__ void k_init_state(int n, int64_t cap, DevState s, int dim)
 {
@@ -1127,6 +1160,7 @@ void rebuild_t(md_ctx *c)
     c->st_rebuilds++;
     c->m0 = c->m1 = 1.0; // (md_scale_cell: fresh rows, the full skin again)
     c->scaled0 = c->scaled1 = false;
+    deform_reset0(c), deform_reset1(c);
     c->inner_valid = false; // the next force evaluation is a prune step
     // (a slab handle prunes only when its caller schedules prune steps: md_dom_enable_pruning)
     c->prune_on = c->use_tiles && (!c->dom.on || c->dom.prune_enabled) && c->skin > 0.0 && c->inner_skin_req > 0.0 &&
@@ -1323,6 +1357,7 @@ void launch_force_tpu(md_ctx *c, bool want_uw, bool kick, double dt, int step, i
     if (prune_step) {
         c->inner_valid = true;
         c->m1 = 1.0; // (md_scale_cell: fresh inner rows, the full inner skin again)
+        deform_reset1(c);
         c->scaled1 = false;
         c->steps_since_prune = 0;
         c->st_prunes++;
@@ -1622,6 +1657,7 @@ void launch_step_tpu(md_ctx *c, bool want_uw, double dt, int step)
     if (prune_step) {
         c->inner_valid = true;
         c->m1 = 1.0; // (md_scale_cell: fresh inner rows, the full inner skin again)
+        deform_reset1(c);
         c->scaled1 = false;
         c->steps_since_prune = 0;
         c->st_prunes++;
@@ -5121,7 +5157,10 @@ int md_scale_cell(md_ctx *ctx, double mu, double vscale, int *rows_kept)
     // saves would come a third sooner anyway.  (A non-positive skin covers nothing.)
     bool keep = ctx->list_valid && ctx->use_tiles && ctx->skin > 0.0 && ctx->pot_kind != POT_CUSTOM;
     const double m0n = ctx->m0 * mu, m1n = ctx->m1 * mu;
-    const double se = m0n * ctx->rl - ctx->rc, ie = m1n * (ctx->rc + ctx->inner_skin) - ctx->rc;
+    // (a list md_deform_cell has mapped carries its singular-value bound along; one that was only scaled: the doubles as ever)
+    const double se = ctx->deformed0 ? (m0n * ctx->ds0) * ctx->rl - ctx->rc : m0n * ctx->rl - ctx->rc;
+    const double ie = ctx->deformed1 ? (m1n * ctx->ds1) * (ctx->rc + ctx->inner_skin) - ctx->rc
+                                     : m1n * (ctx->rc + ctx->inner_skin) - ctx->rc;
     if (keep && !(se >= (2.0 / 3.0) * ctx->skin)) keep = false;
     bool keep_in = keep && ctx->inner_valid;
     if (keep_in && !(ie >= (2.0 / 3.0) * ctx->inner_skin)) keep_in = false;
@@ -5153,6 +5192,7 @@ int md_scale_cell(md_ctx *ctx, double mu, double vscale, int *rows_kept)
         ctx->list_valid = ctx->inner_valid = false;
         ctx->m0 = ctx->m1 = 1.0;
         ctx->scaled0 = ctx->scaled1 = false;
+        deform_reset0(ctx), deform_reset1(ctx);
         ctx->state_invalid = true;
         throw;
     }
@@ -5179,9 +5219,272 @@ int md_scale_cell(md_ctx *ctx, double mu, double vscale, int *rows_kept)
         ctx->list_valid = false;
         ctx->inner_valid = false;
     }
-    if (!ctx->inner_valid) ctx->m1 = 1.0, ctx->scaled1 = false;
-    if (!ctx->list_valid) ctx->m0 = 1.0, ctx->scaled0 = false;
+    if (!ctx->inner_valid) ctx->m1 = 1.0, ctx->scaled1 = false, deform_reset1(ctx);
+    if (!ctx->list_valid) ctx->m0 = 1.0, ctx->scaled0 = false, deform_reset0(ctx);
     if (rows_kept) *rows_kept = keep ? 1 : 0;
+    API_END
+}
+
+// General affine map of the whole frame that keeps the Verlet rows (md_deform.hpp).
+namespace {
+
+// Extreme eigenvalues of the symmetric d x d matrix C (row-major 3 x 3, d <= 3) by cyclic Jacobi rotations: each rotation
+// is orthogonal to rounding, the off-diagonal mass falls quadratically; ten sweeps leave it below 1e-30 of the trace.
+void sym_eig_minmax(const double *Cin, int d, double &lmin, double &lmax)
+{
+    double a[9];
+    for (int i = 0; i < 9; ++i) a[i] = Cin[i];
+    for (int sweep = 0; sweep < 16; ++sweep) {
+        double off = 0.0, tr = 0.0;
+        for (int p = 0; p < d; ++p) {
+            tr += std::fabs(a[p * 3 + p]);
+            for (int q = p + 1; q < d; ++q) off += a[p * 3 + q] * a[p * 3 + q];
+        }
+        if (!(off > 1e-60 * tr * tr)) break;
+        for (int p = 0; p < d; ++p)
+            for (int q = p + 1; q < d; ++q) {
+                const double apq = a[p * 3 + q];
+                if (apq == 0.0) continue;
+                const double theta = (a[q * 3 + q] - a[p * 3 + p]) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
+                for (int k = 0; k < d; ++k) { // columns p, q
+                    const double akp = a[k * 3 + p], akq = a[k * 3 + q];
+                    a[k * 3 + p] = cs * akp - sn * akq;
+                    a[k * 3 + q] = sn * akp + cs * akq;
+                }
+                for (int k = 0; k < d; ++k) { // rows p, q
+                    const double apk = a[p * 3 + k], aqk = a[q * 3 + k];
+                    a[p * 3 + k] = cs * apk - sn * aqk;
+                    a[q * 3 + k] = sn * apk + cs * aqk;
+                }
+            }
+    }
+    lmin = lmax = a[0];
+    for (int p = 1; p < d; ++p) lmin = std::min(lmin, a[p * 3 + p]), lmax = std::max(lmax, a[p * 3 + p]);
+}
+
+// lo <= sigma_min(M), hi >= sigma_max(M): the singular values from the eigenproblem of M^T M, widened by a relative 2^-40
+// in the safe direction (the product, the rotations and the root err by a few 2^-52 of sigma_max^2; for the maps rows
+// survive -- condition numbers within a few per cent of 1 -- that is twelve bits inside the margin).
+void singular_bounds(const double *M, int d, double &lo, double &hi)
+{
+    double C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int r = 0; r < d; ++r)
+        for (int c = 0; c < d; ++c) {
+            double v = 0.0;
+            for (int k = 0; k < d; ++k) v += M[k * 3 + r] * M[k * 3 + c];
+            C[r * 3 + c] = v;
+        }
+    double l0, l1;
+    sym_eig_minmax(C, d, l0, l1);
+    lo = std::sqrt(std::max(l0, 0.0)) * (1.0 - 0x1p-40);
+    hi = std::sqrt(std::max(l1, 0.0)) * (1.0 + 0x1p-40);
+}
+
+// (every product and sum rounded, k ascending: a test restates the product of its own F's bit for bit)
+void mat3_mul(const double *A, const double *B, int d, double *out) // out = A B (row-major 3 x 3, upper left d x d)
+{
+#pragma clang fp contract(off)
+    double t[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int r = 0; r < d; ++r)
+        for (int c = 0; c < d; ++c) {
+            double v = 0.0;
+            for (int k = 0; k < d; ++k) v += A[r * 3 + k] * B[k * 3 + c];
+            t[r * 3 + c] = v;
+        }
+    for (int i = 0; i < 9; ++i) out[i] = t[i];
+}
+
+} // namespace
+
+int md_deform_cell(md_ctx *ctx, const double *F, const double *G, int *rows_kept)
+{
+    API_BEGIN
+    if (!F) throw HipError("md_deform_cell: F is null");
+    const int dim = ctx->dim;
+    DeformMap m{};
+    for (int i = 0; i < 9; ++i) m.F[i] = m.G[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    for (int r = 0; r < dim; ++r)
+        for (int c = 0; c < dim; ++c) {
+            m.F[r * 3 + c] = F[r * dim + c];
+            if (G) m.G[r * 3 + c] = G[r * dim + c];
+            if (!std::isfinite(m.F[r * 3 + c])) throw HipError("md_deform_cell: the entries of F must be finite");
+            if (!std::isfinite(m.G[r * 3 + c])) throw HipError("md_deform_cell: the entries of G must be finite");
+        }
+    {
+        const double *f = m.F;
+        const double det = f[0] * (f[4] * f[8] - f[5] * f[7]) - f[1] * (f[3] * f[8] - f[5] * f[6]) + f[2] * (f[3] * f[7] - f[4] * f[6]);
+        if (!(det > 0.0) || !std::isfinite(det)) throw HipError("md_deform_cell: det F must be finite and > 0");
+    }
+    if (ctx->dom.on) throw HipError("md_deform_cell: not available on a slab-decomposition handle");
+    require_state(ctx, "md_deform_cell");
+    if (ctx->snap_pending) throw HipError("md_deform_cell: a frame is in flight (collect it with md_snapshot_end first)");
+    const char *holder = ctx->dyn.on ? "md_dyn" : ctx->sq.on ? "md_sq" : ctx->current.on ? "md_cur" : ctx->chi4.on ? "md_chi4"
+                         : ctx->cage.on ? "md_cage" : nullptr;
+    if (holder)
+        throw HipError(std::string("md_deform_cell: the ") + holder + "_ sampler is set up on this handle; its stored origins or "
+                       "wave vectors belong to the cell it was set up in");
+    double box[9];
+    {
+#pragma clang fp contract(off)
+        // F U, row times column, left to right, every product and sum rounded (numpy restates it entry by entry)
+        for (int c = 0; c < dim; ++c)
+            for (int r = 0; r < dim; ++r) {
+                double t = m.F[r * 3 + 0] * ctx->A[0 * 3 + c] + m.F[r * 3 + 1] * ctx->A[1 * 3 + c];
+                if (dim == 3) t = t + m.F[r * 3 + 2] * ctx->A[2 * 3 + c];
+                box[c * dim + r] = t;
+            }
+    }
+    CellGeom cg;
+    if (const char *why = cell_geometry(dim, box, cg)) {
+        std::string w(why);
+        throw HipError("md_deform_cell" + w.substr(w.find(':')));
+    }
+    for (int c = 0; c < dim; ++c) {
+        const double need = std::max({ctx->rc, ctx->rdf.on ? ctx->rdf.r_max : 0.0, ctx->mpc.on ? ctx->mpc.r_max : 0.0});
+        if (cg.perp[c] / 3.0 < ctx->rc || cg.perp[c] < 3.0 * need) {
+            char b[360];
+            snprintf(b, sizeof b,
+                     "md_deform_cell: the new cell is too small: the face distance %.17g of lattice direction %d must be >= "
+                     "3*list_cutoff = %.17g%s",
+                     cg.perp[c], c, 3.0 * ctx->rc,
+                     need > ctx->rc ? " and >= 3*r_max of the md_rdf_ / md_mpc_ sampler set up on this handle" : "");
+            throw HipError(b);
+        }
+    }
+    // the singular-value bounds of this call's F and of the accumulated maps (host arithmetic only: nothing is committed)
+    double Fs, FS, M0n[9], M1n[9], s0n, S0n, s1n, S1n;
+    singular_bounds(m.F, dim, Fs, FS);
+    mat3_mul(m.F, ctx->Md0, dim, M0n);
+    mat3_mul(m.F, ctx->Md1, dim, M1n);
+    singular_bounds(M0n, dim, s0n, S0n);
+    singular_bounds(M1n, dim, s1n, S1n);
+    if (!(Fs > 0.0) || !(s0n > 0.0) || !(s1n > 0.0) || !std::isfinite(FS))
+        throw HipError("md_deform_cell: F is singular to working precision");
+
+    hipStream_t st = ctx->stream;
+    ctx->scale_dmax.ensure(MD_SCALE_NOUT);
+    // the host side first, as md_scale_cell: a refusal from the samplers' grids leaves the particles where they are; the
+    // cell grid of the list is not derived again (rebuild() does), only its periodic translations follow now
+    struct Saved {
+        double L[3], A[9], Ainv[9], perp[3], volume;
+        int tric;
+        RdfGrid rdf, mpc;
+    } old;
+    for (int c = 0; c < 3; ++c) old.L[c] = ctx->L[c], old.perp[c] = ctx->perp[c];
+    for (int c = 0; c < 9; ++c) old.A[c] = ctx->A[c], old.Ainv[c] = ctx->Ainv[c];
+    old.volume = ctx->volume, old.tric = ctx->tric, old.rdf = ctx->rdf.grid, old.mpc = ctx->mpc.grid;
+    for (int c = 0; c < dim; ++c) ctx->L[c] = cg.A[c * 3 + c];
+    for (int c = 0; c < 3; ++c) ctx->perp[c] = cg.perp[c];
+    for (int c = 0; c < 9; ++c) ctx->A[c] = cg.A[c], ctx->Ainv[c] = cg.Ainv[c];
+    ctx->volume = cg.volume;
+    ctx->tric = cg.tric;
+    try {
+        if (ctx->rdf.on) regrid_pair_walk(ctx, ctx->rdf, "md_deform_cell (md_rdf_ sampler)");
+        if (ctx->mpc.on) regrid_pair_walk(ctx, ctx->mpc, "md_deform_cell (md_mpc_ sampler)");
+    } catch (...) {
+        (void)hipGetLastError();
+        for (int c = 0; c < 3; ++c) ctx->L[c] = old.L[c], ctx->perp[c] = old.perp[c];
+        for (int c = 0; c < 9; ++c) ctx->A[c] = old.A[c], ctx->Ainv[c] = old.Ainv[c];
+        ctx->volume = old.volume, ctx->tric = old.tric, ctx->rdf.grid = old.rdf, ctx->mpc.grid = old.mpc;
+        throw;
+    }
+    BoxGrid &g = ctx->grid;
+    for (int c = 0; c < dim; ++c) {
+        g.L[c] = ctx->L[c];
+        g.invL[c] = 1.0 / ctx->L[c];
+    }
+    for (int c = 0; c < 9; ++c) g.A[c] = ctx->A[c], g.Ainv[c] = ctx->Ainv[c];
+    g.tric = ctx->tric;
+    ctx->grid_stale = true;
+    ctx->hess.frozen = false;
+
+    // Which rows can stay: md_scale_cell's rule, and the cell must stay of its kind -- tric selects code paths in the
+    // kernels that read the live rows (shift codes of a diagonal cell are box lengths, of a general one lattice vectors).
+    bool keep = ctx->list_valid && ctx->use_tiles && ctx->skin > 0.0 && ctx->pot_kind != POT_CUSTOM && cg.tric == old.tric;
+    const double se = (ctx->m0 * s0n) * ctx->rl - ctx->rc, ie = (ctx->m1 * s1n) * (ctx->rc + ctx->inner_skin) - ctx->rc;
+    if (keep && !(se >= (2.0 / 3.0) * ctx->skin)) keep = false;
+    bool keep_in = keep && ctx->inner_valid;
+    if (keep_in && !(ie >= (2.0 / 3.0) * ctx->inner_skin)) keep_in = false;
+    if (!keep_in) ctx->inner_valid = false; // (dev(): x1 aliases x0 from here on; the next step prunes, or builds)
+    const int n = (int)ctx->n;
+    const int npos = (keep && !ctx->virtual_ghosts) ? (int)ctx->next : n; // real ghost records go along with their rows
+    const double half_skin = keep ? 0.5 * se : INFINITY, half_inner = keep_in ? 0.5 * ie : INFINITY;
+    unsigned long long hb[MD_SCALE_NOUT] = {0ull, 0ull, 0ull};
+    // From here on the host holds the new cell: a HIP error leaves it unknown whether the particles went along
+    // (state_invalid, as md_scale_cell).
+    try {
+        HIPCHK(hipMemsetAsync(ctx->scale_dmax.p, 0, MD_SCALE_NOUT * sizeof(unsigned long long), st));
+        if (npos > 0) {
+            DevState s = ctx->dev(ctx->cur);
+            const int has_x1 = keep_in ? 1 : 0, has_g = G ? 1 : 0;
+            if (dim == 3)
+                k_deform_cell<3><<<nblocks(npos), MD_BLOCK, 0, st>>>(n, npos, s, m, has_g, has_x1, half_skin, half_inner, FS,
+                                                                     ctx->scal.p, ctx->scale_dmax.p);
+            else
+                k_deform_cell<2><<<nblocks(npos), MD_BLOCK, 0, st>>>(n, npos, s, m, has_g, has_x1, half_skin, half_inner, FS,
+                                                                     ctx->scal.p, ctx->scale_dmax.p);
+            if (keep_in) k_scale_commit<<<1, 1, 0, st>>>(ctx->scal.p, ctx->scale_dmax.p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipMemcpyAsync(hb, ctx->scale_dmax.p, sizeof hb, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    } catch (...) {
+        ctx->list_valid = ctx->inner_valid = false;
+        ctx->m0 = ctx->m1 = 1.0;
+        ctx->scaled0 = ctx->scaled1 = false;
+        deform_reset0(ctx), deform_reset1(ctx);
+        ctx->state_invalid = true;
+        throw;
+    }
+    double dsq[MD_SCALE_NOUT];
+    memcpy(dsq, hb, sizeof dsq);
+    if (keep && !(dsq[0] <= half_skin * half_skin)) keep = false;
+    if (keep && keep_in) {
+        const double thr = std::fmin(half_inner, half_skin - std::sqrt(dsq[2]));
+        if (!(thr > 0.0 && dsq[1] <= thr * thr)) keep_in = false;
+    }
+    if (keep) {
+        for (int i = 0; i < 9; ++i) ctx->Md0[i] = M0n[i];
+        ctx->ds0 = s0n, ctx->dS0 = S0n;
+        ctx->deformed0 = true;
+        if (keep_in) {
+            for (int i = 0; i < 9; ++i) ctx->Md1[i] = M1n[i];
+            ctx->ds1 = s1n, ctx->dS1 = S1n;
+            ctx->deformed1 = true;
+        } else {
+            ctx->inner_valid = false;
+        }
+    } else {
+        ctx->list_valid = false;
+        ctx->inner_valid = false;
+    }
+    if (!ctx->inner_valid) ctx->m1 = 1.0, ctx->scaled1 = false, deform_reset1(ctx);
+    if (!ctx->list_valid) ctx->m0 = 1.0, ctx->scaled0 = false, deform_reset0(ctx);
+    if (rows_kept) *rows_kept = keep ? 1 : 0;
+    API_END
+}
+
+int md_deform_state(md_ctx *ctx, double *m0, double *m1, double *sig)
+{
+    API_BEGIN
+    // (md_scale_cell's scalars are part of the accumulated maps: a handle that was only scaled reports mu 1)
+    const bool v0 = ctx->list_valid, v1 = ctx->list_valid && ctx->inner_valid;
+    const double a0 = v0 ? ctx->m0 : 1.0, a1 = v1 ? ctx->m1 : 1.0;
+    for (int i = 0; i < 9; ++i) {
+        const double id = (i % 4 == 0) ? 1.0 : 0.0;
+        const bool used = i / 3 < ctx->dim && i % 3 < ctx->dim; // (2-D: the third row and column stay those of the identity)
+        if (m0) m0[i] = used ? a0 * ((v0 && ctx->deformed0) ? ctx->Md0[i] : id) : id;
+        if (m1) m1[i] = used ? a1 * ((v1 && ctx->deformed1) ? ctx->Md1[i] : id) : id;
+    }
+    if (sig) {
+        const bool d0 = v0 && ctx->deformed0, d1 = v1 && ctx->deformed1;
+        sig[0] = d0 ? a0 * ctx->ds0 : a0;
+        sig[1] = d0 ? a0 * ctx->dS0 : a0;
+        sig[2] = d1 ? a1 * ctx->ds1 : a1;
+        sig[3] = d1 ? a1 * ctx->dS1 : a1;
+    }
     API_END
 }
 

@@ -1,5 +1,6 @@
 """Deformation of a live sample: cell changes in place (md_set_cell), lattice reduction of a sheared cell, the non-affine
-displacement since a mark (md_nonaffine_*) and the athermal quasi-static (AQS) strain loop on top of the device's FIRE.
+displacement since a mark (md_nonaffine_*), the athermal quasi-static (AQS) strain loop on top of the device's FIRE, and
+shear flow at a finite rate and temperature (ShearFlow: SLLOD on md_deform_cell).
 New relative to the reference, which fixes the unit cell at initialisation.
 
 Conventions.  The unit cell U is d x d with the lattice vectors in its COLUMNS (src/initialization.jl:7-18); a deformation
@@ -11,6 +12,7 @@ import os
 import numpy as np
 
 from . import _lib
+from .analysis import _next_multiple
 from .simulation import _configure_device
 
 _REDUCE_MAX_SWEEPS = 64
@@ -246,3 +248,138 @@ def athermal_quasistatic_shear(state, params, pathname, strain_step, nsteps, mod
     for name in ("step", "fire_steps", "converged", "flips"):
         out[name] = out[name].astype(np.int64)
     return out
+
+
+def shear_columns():
+    """The column names of shear.txt, in order."""
+    return ["step", "strain", "tilt", "sigma_ab", "pressure", "K_ab", "rows_kept", "flips"]
+
+
+def shear_flow_update(cell, rate, dt_flow, plane):
+    """The pure part of one application of the flow operator: (F, G, F U) for the elapsed time dt_flow.
+    F = simple_shear(d, rate dt_flow, plane); G = F^-1 = 1 - rate dt_flow e_a e_b^T, exact for simple shear; F U in the
+    device's arithmetic (row times column, left to right, every product and sum rounded)."""
+    U = np.asarray(cell, dtype=np.float64)
+    d = U.shape[0]
+    dgamma = float(rate) * float(dt_flow)
+    F = simple_shear(d, dgamma, plane)
+    G = simple_shear(d, -dgamma, plane)
+    new = F[:, 0:1] * U[0:1, :] + F[:, 1:2] * U[1:2, :]
+    if d == 3:
+        new = new + F[:, 2:3] * U[2:3, :]
+    return F, G, new
+
+
+class ShearFlow:
+    """Homogeneous simple shear at the rate `rate` (strain per unit time) in plane = (a, b) -- the streaming velocity is
+    u_a = rate x_b -- by the SLLOD equations of motion in a deforming cell, on the device's md_deform_cell (DESIGN.md
+    section 27).  New relative to the reference, which fixes its cell at initialisation.
+
+    After every `every`-th MD step the flow operator is applied for the elapsed time Dt = every dt: with
+    F = simple_shear(d, rate Dt, plane) the cell becomes F U, every position F x and every velocity F^-1 v, in one device
+    pass that keeps the neighbour rows; then the forces are evaluated in the new cell.  The velocities the handle stores
+    are therefore PECULIAR velocities (relative to the streaming motion); the thermostat of the MD step acts on them, which
+    is what SLLOD asks for; the ordinary drift x += v dt plus the flow operator is the streaming motion.  With flip=True
+    the sheared cell is replaced by the reduced cell of the same lattice when reduce_cell's rule says so (once per half
+    box length of strain; particles stay where they are, velocities need no change, the neighbour lists are rebuilt).
+
+    This is the Lie splitting exp(L_md Dt) exp(L_flow Dt) of the SLLOD propagator: its error is FIRST ORDER in
+    rate * every * dt.  every=1 is the plain one-step splitting; a larger `every` trades accuracy in the rate for fewer
+    force evaluations.
+
+    Stress: at every stress_every-th coupling, BEFORE the flow is applied, the stress tensor of the moment is read through
+    the handle's md_stress_ sums (set up afresh at the start of the run, as athermal_quasistatic_shear does):
+    sigma = -(sum v v + sum (f/r) del del) / V, aqs.txt's sign and normalisation (tension positive, per unit volume) plus
+    the kinetic part.  Couplings without a reading record nan.
+
+    Fields, accumulated over the runs until reset(): records (one dict per coupling, the columns of shear.txt: step,
+    strain -- the accumulated rate * time, monotone across flips --, tilt -- the entry U[a, b] of the cell after the
+    coupling --, sigma_ab, pressure = -trace(sigma) / d, K_ab -- the kinetic part -sum v_a v_b / V of sigma_ab --,
+    rows_kept, flips), strain, n_stress, sum_sigma; mean_stress(), viscosity() = <sigma_ab> / rate."""
+
+    def __init__(self, rate, every=10, plane=(0, 1), stress_every=1, flip=True):
+        rate, every, stress_every = float(rate), int(every), int(stress_every)
+        if not np.isfinite(rate):
+            raise ValueError("rate must be finite")
+        if every < 1:
+            raise ValueError("every must be >= 1")
+        if stress_every < 1:
+            raise ValueError("stress_every must be >= 1")
+        a, b = int(plane[0]), int(plane[1])
+        if a == b or a < 0 or b < 0:
+            raise ValueError(f"plane must name two different axes, got {plane}")
+        self.rate, self.every, self.plane, self.stress_every, self.flip = rate, every, (a, b), stress_every, bool(flip)
+        self.reset()
+
+    def reset(self):
+        self.records = []
+        self.strain = 0.0
+        self.n_couplings = 0
+        self.n_stress = 0
+        self.sum_sigma = 0.0
+
+    def mean_stress(self):
+        return self.sum_sigma / self.n_stress if self.n_stress else float("nan")
+
+    def viscosity(self):
+        return self.mean_stress() / self.rate if self.rate != 0.0 else float("nan")
+
+    def write(self, path):
+        with open(path, "w") as io:
+            io.write("# " + " ".join(shear_columns()) + "\n")
+            for c in self.records[self._first:]:
+                io.write("%d %.17g %.17g %.17g %.17g %.17g %d %d\n" % (c["step"], c["strain"], c["tilt"], c["sigma_ab"],
+                                                                      c["pressure"], c["K_ab"], c["rows_kept"], c["flips"]))
+
+    # -- run_simulation's protocol: one application of the flow operator after every `every`-th step -----------------------
+    def _begin(self, dev, run):
+        if run.brownian:
+            raise ValueError("shear= is not available with Brownian dynamics (no velocities: SLLOD maps peculiar velocities)")
+        self._dim = run.dim
+        _plane(self._dim, self.plane)
+        self._total_steps = run.total_steps
+        self._dt_flow = self.every * run.dt
+        self._first = len(self.records)
+        dev.stress_setup(0)
+        a, b = min(self.plane), max(self.plane)
+        self._comp = list(dev.elas_components).index((a, b))
+        self._diag = [i for i, (p, q) in enumerate(dev.elas_components) if p == q]
+
+    def _next(self, step):
+        s = _next_multiple(step + 1, self.every, self._total_steps + 1)
+        return None if s is None else s - 1
+
+    def _act(self, dev, step, U, W, K, volume):
+        """One application on the frame the segment (or the swap block) left: returns dict(step, cell, U, W, K, rows_kept,
+        flips, ...) with the cell after the flow (and the flip), U, W of that cell and K of the mapped velocities."""
+        d = self._dim
+        a, b = self.plane
+        sigma = pressure = k_ab = float("nan")
+        if self.n_couplings % self.stress_every == 0:
+            dev.stress_sample()
+            kin, vir = dev.stress_tensor()
+            st = -(kin + vir) / volume
+            sigma, k_ab = float(st[self._comp]), float(-kin[self._comp] / volume)
+            pressure = -float(sum(st[i] for i in self._diag)) / d
+            self.n_stress += 1
+            self.sum_sigma += sigma
+        F, G, _ = shear_flow_update(dev.unitcell, self.rate, self._dt_flow, self.plane)
+        kept = dev.deform_cell(F, G)
+        flips = 0
+        if self.flip:
+            Wc, M = gauss_reduce(dev.unitcell)
+            if not np.array_equal(M, np.eye(d, dtype=np.int64)):
+                dev.set_cell(Wc, _lib.MD_CELL_LATTICE)
+                flips = 1
+        U, W = dev.compute_forces()                         # the next half-kick needs the new cell's forces
+        K = dev.kinetic()
+        self.n_couplings += 1
+        self.strain += self.rate * self._dt_flow
+        cell = np.array(dev.unitcell)
+        rec = dict(step=step, strain=self.strain, tilt=float(cell[a, b]), sigma_ab=sigma, pressure=pressure, K_ab=k_ab,
+                   rows_kept=int(kept), flips=flips)
+        self.records.append(rec)
+        return dict(rec, cell=cell, U=U, W=W, K=K)
+
+    def _finish(self, dev, run, pathname):
+        self.write(os.path.join(pathname, "shear.txt"))

@@ -122,6 +122,40 @@ class MDDevice:
         self.unitcell = np.float64(mu) * self.unitcell
         return int(kept.value)
 
+    def deform_cell(self, F, G=None):
+        """Map the whole frame by the deformation gradient F (md_deform_cell): the cell becomes F U, x <- F x and, with G,
+        v <- G v (G = inv(F): the stored velocities become peculiar ones, SLLOD), row times vector with every product and
+        sum rounded, nothing wrapped -- and the Verlet rows are kept with the skins they still leave (forces stay those of
+        the old cell until the next evaluation).  F, G: d x d.  Returns rows_kept: 1 when the outer rows stayed, 0 when the
+        next evaluation builds the list again.  A refusal (MdhipError) leaves the handle as it was; waits."""
+        d = self.dim
+        Fm = np.ascontiguousarray(np.asarray(F, dtype=np.float64))
+        if Fm.shape != (d, d):
+            raise ValueError(f"F must have shape ({d}, {d})")
+        Gm = None
+        if G is not None:
+            Gm = np.ascontiguousarray(np.asarray(G, dtype=np.float64))
+            if Gm.shape != (d, d):
+                raise ValueError(f"G must have shape ({d}, {d})")
+        kept = C.c_int(0)
+        self._chk(self._L.md_deform_cell(self._h, _dp(Fm), None if Gm is None else _dp(Gm), C.byref(kept)))
+        # F U in the library's arithmetic: row times column, left to right, every product and sum rounded
+        U = np.asarray(self.unitcell, dtype=np.float64)
+        new = Fm[:, 0:1] * U[0:1, :] + Fm[:, 1:2] * U[1:2, :]
+        if d == 3:
+            new = new + Fm[:, 2:3] * U[2:3, :]
+        self.unitcell = np.ascontiguousarray(new)
+        return int(kept.value)
+
+    def deform_state(self):
+        """(M0, M1, sig) of md_deform_state: the products of the maps since the list build and since the last prune (d x d;
+        identity when nothing was mapped) and sig = (s0, S0, s1, S1), the bounds on their singular values the skins left
+        to the rows are formed from."""
+        m0, m1, sig = np.zeros(9), np.zeros(9), np.zeros(4)
+        self._chk(self._L.md_deform_state(self._h, _dp(m0), _dp(m1), _dp(sig)))
+        d = self.dim
+        return m0.reshape(3, 3)[:d, :d].copy(), m1.reshape(3, 3)[:d, :d].copy(), sig
+
     def nonaffine_mark(self):
         """Mark the current frame (md_nonaffine_mark): fractional coordinates and image counts by particle id."""
         self._chk(self._L.md_nonaffine_mark(self._h))

@@ -36,8 +36,8 @@ def _configure_device(state, params):
 
 def run_simulation(state, params, ensemble, total_steps, frequency, pathname, traj_name="trajectory.xyz",
                    thermo_name="thermo.txt", compress=False, log_times=False, write_trajectory=True, rdf=None,
-                   dynamics=None, orientational=None, swap=None, barostat=None, sq=None, currents=None, stress=None,
-                   four_point=None, clusters=None, cage=None, bond_order=None):
+                   dynamics=None, orientational=None, swap=None, barostat=None, shear=None, sq=None, currents=None,
+                   stress=None, four_point=None, clusters=None, cage=None, bond_order=None):
     """Python spelling of run_simulation! (mutates `state`, returns None).
 
     rdf: a RadialDistribution (analysis.py) to sample g(r) into, on the device, at every rdf.every-th output step
@@ -122,7 +122,32 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
     belong to one cell: dynamics=, sq=, currents=, four_point= and cage= store time origins or wave vectors of the cell
     they were set up in (md_scale_cell refuses them on the device), and rdf=, stress= and orientational= normalise their
     sums with one volume, which a run whose volume moves does not have.  bond_order=, clusters= and swap= go with it.
-    With barostat=None nothing the run produces changes."""
+    With barostat=None nothing the run produces changes.
+
+    shear: a ShearFlow (deformation.py): after every shear.every-th step the flow operator of SLLOD for the elapsed time --
+    the cell becomes F U, positions F x, velocities F^-1 v with F the simple shear of rate * every * dt, on the device
+    (md_deform_cell, which keeps the neighbour rows) -- a lattice flip of the cell when it is due, and the forces of the
+    new cell.  The velocities the run holds, exports and thermostats are peculiar velocities.  The splitting is first
+    order in rate * every * dt (every=1: the plain one-step splitting).  Like swap and barostat it CHANGES the run; its
+    stops are added to the loop's output steps and it acts where the barostat acts: after every sampler and after swap,
+    before the thermo line and the frame export of that step.  state.unitcell and state.system.unitcell follow; every
+    frame, snapshot and final.xyz carries the cell of its moment.  Written to pathname/shear.txt.  Refused up front,
+    before any file is opened: Brownian dynamics; barostat=; stress= (one handle has one set of md_stress_ sums and the
+    shear reads its stress through them; sharing them is left for later); dynamics=, sq=, currents=, four_point= and
+    cage=, which are bound to the cell they were set up in.  rdf=, bond_order=, clusters=, orientational= and swap= go
+    with it: the volume is constant.  With shear=None nothing the run produces changes."""
+    if shear is not None:
+        if isinstance(ensemble, Brownian):
+            raise ValueError("shear= is not available with Brownian dynamics (no velocities: SLLOD maps peculiar velocities)")
+        if barostat is not None:
+            raise ValueError("shear= cannot be combined with barostat=: both own the cell of the run")
+        if stress is not None:
+            raise ValueError("shear= cannot be combined with stress=: one handle has one set of md_stress_ sums and the "
+                             "shear reads its stress through them; sharing them is left for later")
+        for name, smp in dict(dynamics=dynamics, sq=sq, currents=currents, four_point=four_point, cage=cage).items():
+            if smp is not None:
+                raise ValueError("shear= cannot be combined with %s=: its stored time origins or wave vectors belong to "
+                                 "the cell it is set up in, and the shear changes the cell" % name)
     if barostat is not None:
         one_cell = dict(dynamics=dynamics, sq=sq, currents=currents, four_point=four_point, cage=cage)
         one_volume = dict(rdf=rdf, stress=stress, orientational=orientational)
@@ -176,6 +201,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         swap._begin(dev, run)
     if barostat is not None:
         barostat._begin(dev, run)
+    if shear is not None:
+        shear._begin(dev, run)
     vir_acc = [0.0, 0.0]
 
     nvt = isinstance(ensemble, NVT)
@@ -219,6 +246,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             stops.append(swap._next(step))
         if barostat is not None:
             stops.append(barostat._next(step))
+        if shear is not None:
+            stops.append(shear._next(step))
         last = min(min(t for t in stops if t is not None), total_steps - 1)
         U, W, K = segment(step, last - step + 1)
         collect()                       # the frame exported before this segment: its copy had the whole segment to finish
@@ -240,6 +269,13 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
             state.system.unitcell = state.unitcell
             volume = compute_box_volume(state.unitcell)
             barostat._record(r, volume)
+            U, W, K = r["U"], r["W"], r["K"]
+        if shear is not None and shear._next(last) == last:
+            # where the barostat acts (the two exclude each other); the cell is replaced by a new array, never in place
+            r = shear._act(dev, last, U, W, K, volume)
+            state.unitcell = r["cell"]
+            state.system.unitcell = state.unitcell
+            volume = compute_box_volume(state.unitcell)
             U, W, K = r["U"], r["W"], r["K"]
         want_frame = False
         if last % frequency == 0:
@@ -285,6 +321,8 @@ def run_simulation(state, params, ensemble, total_steps, frequency, pathname, tr
         swap._finish(dev, run, pathname)
     if barostat is not None:
         barostat._finish(dev, run, pathname)
+    if shear is not None:
+        shear._finish(dev, run, pathname)
     if compress and os.path.isfile(trajectory_file):
         _io.compress_zstd(trajectory_file)
     return None
